@@ -416,6 +416,37 @@ def host_path_rate(x_dev, chr_start, refs, hmm, cells=20000):
     return res
 
 
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs: under the 64 MB the files may take together
+DUMP_SEED = 20260101
+
+
+def sample_outputs(arrays, global_cell):
+    """--dump-outputs: a fixed, seeded sample of whole cells (rows) of the step's (cells x genes) outputs, copied to the host
+    as float64 (f64 data) or float32 (state calls).  The rows depend only on the shape, so two builds run with the same
+    arguments dump the same cells.  `global_cell(rows)` maps local rows to global cell indices (saved as `sample_cells`)."""
+    import numpy as np
+    import torch
+    C, G = next(iter(arrays.values())).shape
+    width = {name: 8 if a.dtype == torch.float64 else 4 for name, a in arrays.items()}
+    per_elem = sum(width.values())
+    cols = min(G, max(1, DUMP_BUDGET_BYTES // per_elem))
+    k = min(C, max(1, DUMP_BUDGET_BYTES // (per_elem * cols + 8)))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(C, size=k, replace=False))
+    ri = torch.from_numpy(rows).to(next(iter(arrays.values())).device)
+    out = {"sample_cells": np.asarray(global_cell(rows), dtype=np.float64)}
+    for name, a in arrays.items():
+        s = a.index_select(0, ri)[:, :cols]
+        out[name] = s.to(torch.float64 if width[name] == 8 else torch.float32).cpu().numpy()
+    return out
+
+
+def write_outputs(directory, sample):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in sample.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def run_group_config(args, world, rank):
     """BASELINE configs 4 (i3 HMM at subcluster level) and 5 (2-D median filter): subclusters / tiles are whole on their
     rank (contiguous cell blocks cut at subcluster boundaries, sharded.align_to_groups); the inputs -- the smoothing
@@ -476,6 +507,9 @@ def run_group_config(args, world, rank):
     fence()
     elapsed = time.perf_counter() - t0
     device.timing_enable(False)
+    # the last timed step's output, before the side legs below reuse the buffers
+    dumped = (sample_outputs({"states" if args.config == 4 else "filtered": result[0]}, lambda rows: rows + c0)
+              if args.dump_outputs and rank == 0 else None)
     no_ties_ms = None
     if args.config == 5 and not args.no_side_legs:
         step_no_ties()
@@ -537,6 +571,9 @@ def run_group_config(args, world, rank):
                                              "runs on the denoised matrix, as BASELINE config 5 and apply_median_filtering's use specify, where "
                                              "the majority shortcut decides most windows"}} if no_ties_ms else {}),
                "checksums": {"per_rank": checks, "meaning": "sum of the step's output (states, or the filtered matrix) over the rank's cells"}}
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
+            res["dump_outputs"] = {"dir": args.dump_outputs, "files": sorted(n + ".npy" for n in dumped), "cells": len(dumped["sample_cells"])}
         print(json.dumps(res))
 
 
@@ -582,7 +619,13 @@ def main():
                     help="with --checksum: also write, per rank / per residue class r, DIR/states_r.npy (uint8 state calls), "
                          "DIR/pre_cellsums_r.npy and DIR/out_cellsums_r.npy (per-cell sums of the HMM input and of the denoised matrix): "
                          "what tests/test_gpu_entrypoints.py compares element by element between an N-rank and a one-rank run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64 data, state calls "
+                         "as float32): a fixed, seeded sample of whole cells of rank 0 (at most 64 MB in all) and their global indices "
+                         "(sample_cells.npy) -- config 2 / 3: denoised, hmm_input, states; config 4: states; config 5: filtered")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: no launcher has set the rank environment, so this process becomes the launcher
@@ -679,6 +722,9 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     device.timing_enable(False)
+    # the last timed step's outputs, before the detail pass and the checksum step below rewrite the buffers
+    dumped = (sample_outputs({"denoised": out, "hmm_input": pre_buf, "states": states}, lambda rows: rank + rows * world)
+              if args.dump_outputs and rank == 0 else None)
     hot = {}
     if not args.no_kernel_timing:
         for k in ("chain_apply", "viterbi"):
@@ -878,6 +924,9 @@ def main():
         }
         if checksums is not None:
             res["checksums"] = {"per_part": checksums, "meaning": "[sum(denoised), sum(hmm_input), sum(states)] of the cells of rank r"}
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
+            res["dump_outputs"] = {"dir": args.dump_outputs, "files": sorted(n + ".npy" for n in dumped), "cells": len(dumped["sample_cells"])}
         if not args.no_cpu_baseline and world == 1 and args.config == 3:
             # the oracle runs over [all reference cells | sampled observation cells] of THIS matrix: timed, it is the
             # cpu_baseline sample; compared with the step's outputs, it is the parity block

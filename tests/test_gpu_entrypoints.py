@@ -600,23 +600,24 @@ print("MULTI_OK")
     assert res.returncode == 0 and "MULTI_OK" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
 
 
-@pytest.mark.parametrize("world,launch", [(2, "torchrun"), (8, "torchrun"), (2, "self"), (8, "self")])
+@pytest.mark.parametrize("world,launch", [(2, "torchrun"), (3, "torchrun"), (2, "self"), (3, "self")])
 def test_bench_two_ranks_equal_one_rank(dev, world, launch, tmp_path):
     """The N > 1 path of bench.py (one process per rank, torch.distributed, reference statistics all-reduced between the
-    rounds) on the hardware at hand: 2 and 8 ranks on ONE GPU over gloo (ICNV_BENCH_ONE_DEVICE=1), cells dealt round-robin,
+    rounds) on the hardware at hand: 2 and 3 ranks on ONE GPU over gloo (ICNV_BENCH_ONE_DEVICE=1), cells dealt round-robin,
     against one rank holding all of them.  Both launch styles: under `python -m torch.distributed.run` (the driver's
     documented form) and as plain `python bench.py --gpus N` (bench.py starts its own ranks -- self_launch).  Compared
     ELEMENT BY ELEMENT per rank (bench.py --dump): every state call (0 mismatches), the per-cell sums of the HMM input
     (rounding of the rank-ordered reference sums only) and of the denoised matrix.  (RCCL on N GPUs needs a multi-GPU node:
-    that is the driver's scaling run.)"""
+    that is the driver's scaling run.)  At most 3 ranks and no memory-system microbenchmarks (ICNV_BENCH_NO_UBENCH: they
+    only set the line's ceilings): with this process and the launcher, no more than 5 processes hold the GPU at once."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, ICNV_BENCH_ONE_DEVICE="1", ICNV_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
+    env = dict(os.environ, ICNV_BENCH_ONE_DEVICE="1", ICNV_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", ICNV_BENCH_NO_UBENCH="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    per_rank = 12000 if world == 2 else 3000
+    per_rank = 24000 // world
     d_many, d_one = str(tmp_path / "many"), str(tmp_path / "one")
     common = ["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-kernel-timing", "--checksum", str(world)]
     tail = [os.path.join(root, "bench.py"), "--gpus", str(world), "--cells", str(per_rank), "--dump", d_many] + common
@@ -681,6 +682,46 @@ def test_bench_collectives_over_rccl_with_one_rank(dev):
                            env=dict(os.environ, ICNV_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29578"),
                            capture_output=True, text=True, timeout=600, cwd=root)
         assert r.returncode == 0 and line(r)["n_gpus"] == 1, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+def test_bench_dump_outputs(dev, tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's outputs (a fixed sample of whole cells) as float .npy files under
+    64 MB -- the same files from two runs with the same arguments, the same values as the full per-cell dump (--dump) of
+    those cells; `steps` and `ms_per_step` in the line.  Config 5 dumps its filtered matrix."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, ICNV_BENCH_NO_UBENCH="1")
+    common = ["--gpus", "1", "--cells", "3000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-timing"]
+    line = lambda r: json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    runs = []
+    for i, extra in enumerate((["--checksum", "1", "--dump", str(tmp_path / "full")], [])):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + extra + ["--dump-outputs", str(d)],
+                           env=env, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        res = line(r)
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        files = {f: np.load(d / f) for f in os.listdir(d)}
+        assert sorted(files) == ["denoised.npy", "hmm_input.npy", "sample_cells.npy", "states.npy"] == res["dump_outputs"]["files"]
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert files["denoised.npy"].dtype == files["hmm_input.npy"].dtype == np.float64 and files["states.npy"].dtype == np.float32
+        runs.append(files)
+    for f in runs[0]:
+        np.testing.assert_array_equal(runs[0][f], runs[1][f])
+    cells = runs[0]["sample_cells.npy"].astype(np.int64)
+    assert len(cells) > 0 and runs[0]["states.npy"].shape == (len(cells), res["config"]["genes"])
+    full = tmp_path / "full"
+    np.testing.assert_array_equal(runs[0]["states.npy"], np.load(full / "states_0.npy")[cells].astype(np.float32))
+    np.testing.assert_allclose(runs[0]["hmm_input.npy"].sum(axis=1), np.load(full / "pre_cellsums_0.npy")[cells], rtol=1e-12)
+    np.testing.assert_allclose(runs[0]["denoised.npy"].sum(axis=1), np.load(full / "out_cellsums_0.npy")[cells], rtol=1e-12)
+    d5 = tmp_path / "out5"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "5", "--genes", "4000", "--no-side-legs"] + common
+                       + ["--dump-outputs", str(d5)], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    filt = np.load(d5 / "filtered.npy")
+    assert filt.dtype == np.float64 and filt.shape == (len(np.load(d5 / "sample_cells.npy")), 4000) and np.isfinite(filt).all()
 
 
 def test_i6_whole_samples_without_cluster_by_groups_is_one_sample_per_observation_cell(dev):
