@@ -284,6 +284,37 @@ int icnv_cell_distances(const double *expr, int64_t G, int64_t C, const int32_t 
 int icnv_cell_distances_dev(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, int64_t n, double *dist_out,
                             void *stream);
 
+/* ---- exact k nearest neighbours ---------------------------------------- */
+/* RANN::nn2(t(expr_data), k = k_nn)$nn.idx / $nn.dists with query = data, as the reference's Leiden subclustering calls it in
+ * .leiden_simple_snn (R/inferCNV_tumor_subclusters.R:726; per chromosome x group at :646-697), for a BATCH of problems.
+ * Problem p: genes gene_idx[gene_off[p] .. gene_off[p+1]), cells cell_idx[cell_off[p] .. cell_off[p+1]) (HOST, 0-based, any
+ * order; the gene order is the summation order).  For every cell i of problem p (query row cell_off[p] + i) the k cells j of
+ * the problem ordered by the key (d2_ij, j) ascending; self included (normally the first neighbour):
+ *   d2_ij = the SEQUENTIAL fp64 sum over the problem's genes in list order, s = 0; s = s + t * t with t = x[g,i] - x[g,j],
+ *           every operation rounded, no FMA -- bit for bit; nn_dist = sqrt(d2) (IEEE).  (That ANN, RANN's library, sums
+ *           this way is believed, not verified against its source.)
+ *   Ties: lower cell position first.  RANN orders exactly equal distances by its kd-tree walk, which cannot be restated;
+ *   the neighbour SET equals RANN's whenever the k-th and (k+1)-th distances differ.
+ * nn_idx [total cells * k] int32: positions within the problem's cell list (0-based; R's are 1-based); nn_dist likewise.
+ * 1 <= k <= n_p for every problem (ICNV_ERR_ARG; the caller applies R's skip rules), k <= 128 (ICNV_ERR_UNSUPPORTED).
+ * Every offset, gene and cell index is validated before any device work.  Matrix-core screen with a rigorous error bound,
+ * exact recomputation of the candidates; a row with too many candidates takes an exhaustive exact pass.
+ * Developer switches: ICNV_KNN_EXHAUSTIVE=1 (every row through the exhaustive pass), ICNV_KNN_SCRATCH_MB (screen
+ * budget per row block, default 4096), ICNV_KNN_CAP (candidates per row, default 256, at most 1024). */
+int icnv_knn(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off, const int32_t *cell_idx,
+             const int32_t *cell_off, int32_t n_prob, int32_t k, int32_t *nn_idx, double *nn_dist);
+/* Same contract on device pointers (expr, nn_idx, nn_dist) + hipStream_t; the index lists stay on the HOST
+ * (R/inferCNV_tumor_subclusters.R:726). */
+int icnv_knn_dev(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off, const int32_t *cell_idx,
+                 const int32_t *cell_off, int32_t n_prob, int32_t k, int32_t *nn_idx, double *nn_dist, void *stream);
+/* Counters of the kNN calls since the last reset (R/inferCNV_tumor_subclusters.R:726), n = int64 slots of `out` (<= 9 written):
+ *   out[0] calls   out[1] problems   out[2] query rows   out[3] row blocks   out[4] rows through the screen
+ *   out[5] candidates refined exactly   out[6] screened rows whose candidates overflowed the capacity
+ *   out[7] rows through the exhaustive pass   out[8] rows sent there by ICNV_KNN_EXHAUSTIVE
+ * Synchronises the devices the calls ran on. */
+int icnv_knn_stats(int64_t *out, int32_t n);
+void icnv_knn_stats_reset(void);   /* R/inferCNV_tumor_subclusters.R:726 */
+
 /* ---- HMM ---------------------------------------------------------------- */
 /* Viterbi.dthmm.adj (R/inferCNV_HMM.R:1101-1176) for every (cell, chromosome):
  * predict_CNV_via_HMM_on_indiv_cells (R/inferCNV_HMM.R:284-324) with K = 6 and

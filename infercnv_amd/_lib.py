@@ -110,6 +110,10 @@ PROTOTYPES = {
     "icnv_hmm_emission_scores": (ct.c_int, [_i32, _dp, _dbl, _dp, _i64, _i32, _dp, _vp]),
     "icnv_cell_distances": (ct.c_int, [_vp, _i64, _i64, _ip, _i64, _vp]),
     "icnv_cell_distances_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _i64, _vp, _vp]),
+    "icnv_knn": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _ip, _ip, _i32, _i32, _vp, _vp]),
+    "icnv_knn_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _ip, _ip, _i32, _i32, _vp, _vp, _vp]),
+    "icnv_knn_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_knn_stats_reset": (None, []),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

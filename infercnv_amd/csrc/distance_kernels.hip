@@ -12,27 +12,25 @@
 // depends on them); the fp64 MFMA rate equals the fp64 vector rate on gfx950 (78.6 TFLOP/s), the matrix cores'
 // gain here is the operand reuse: one 8-byte LDS read per lane feeds 2 x 16 x 16 x 4 multiply-adds.
 #include "icnv_internal.h"
+#include "gram_mfma.h"
 
 namespace icnv {
 
 namespace {
 
-typedef double dbl4_t __attribute__((ext_vector_type(4)));
-
-constexpr int KC = 32;        // genes per LDS stage
-constexpr int LDR = KC + 2;   // LDS row stride in doubles: (4 row + 2 k) dwords mod 64 are distinct within a 32-lane group
+using gram::dbl4_t;
+using gram::LDR;
 
 // One workgroup = 4 wavefronts = 2 x 2 sub-tiles; a wavefront holds WM x WM MFMA accumulators (16 x 16 each), so the
 // workgroup's output tile is DT = 32 WM cells square: WM = 2 for small groups (enough tiles to fill 256 CUs),
 // WM = 4 for large ones (each 8-byte LDS operand read then feeds four matrix instructions instead of two).
+// The staging and the MFMA loop are gram::tile_product (gram_mfma.h), shared with the kNN screen (knn_kernels.hip).
 template <int WM>
 __global__ void __launch_bounds__(256, (WM == 4 ? 2 : 4)) gram_tiles_kernel(const double *__restrict__ x, int G, const int32_t *__restrict__ idx,
                                                          int n, const double *__restrict__ mean, double *__restrict__ S) {
     constexpr int DT = 32 * WM;
     constexpr int RPT = DT / 64;          // rows staged per thread and tile
     extern __shared__ __attribute__((aligned(16))) double smem_d[];
-    double *As = smem_d;
-    double *Bs = smem_d + DT * LDR;
     // upper-triangular tile pair (bi <= bj) of this workgroup
     const int nt = (n + DT - 1) / DT;
     int bi = 0, rem = blockIdx.x;
@@ -41,16 +39,7 @@ __global__ void __launch_bounds__(256, (WM == 4 ? 2 : 4)) gram_tiles_kernel(cons
 
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int wr = w >> 1, wc = w & 1;
-    dbl4_t acc[WM][WM];
-#pragma unroll
-    for (int a = 0; a < WM; ++a)
-#pragma unroll
-        for (int b = 0; b < WM; ++b) acc[a][b] = (dbl4_t){0.0, 0.0, 0.0, 0.0};
-
-    // staging: thread t loads 8 consecutive genes of rows t / 4 (+ 64) of each tile.  The next stage is requested into
-    // registers before the current stage's MFMAs and parked in LDS after them: its HBM/L2 latency hides behind the
-    // matrix instructions instead of standing between barriers.
-    const int lrow = t >> 2, lseg = (t & 3) * 8;
+    const int lrow = t >> 2;
     const double *pa[RPT], *pb[RPT];
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
@@ -59,66 +48,8 @@ __global__ void __launch_bounds__(256, (WM == 4 ? 2 : 4)) gram_tiles_kernel(cons
         pb[r] = rb < n ? x + (int64_t)idx[rb] * G : nullptr;
     }
     const bool even = (G & 1) == 0;   // 16-byte loads: every row starts at an even element and g is even
-
-    double ra_v[RPT][8], rb_v[RPT][8];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {
-            if (even) {
-#pragma unroll
-                for (int j = 0; j < 8; j += 2) {
-                    const int g = k0 + lseg + j;
-                    const bool in = g < G;
-                    const double2 m = in ? *reinterpret_cast<const double2 *>(mean + g) : make_double2(0.0, 0.0);
-                    const double2 va = (pa[r] && in) ? *reinterpret_cast<const double2 *>(pa[r] + g) : m;
-                    const double2 vb = (pb[r] && in) ? *reinterpret_cast<const double2 *>(pb[r] + g) : m;
-                    ra_v[r][j] = va.x - m.x; ra_v[r][j + 1] = va.y - m.y;
-                    rb_v[r][j] = vb.x - m.x; rb_v[r][j + 1] = vb.y - m.y;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int g = k0 + lseg + j;
-                    const double m = g < G ? mean[g] : 0.0;
-                    ra_v[r][j] = (pa[r] && g < G) ? pa[r][g] - m : 0.0;
-                    rb_v[r][j] = (pb[r] && g < G) ? pb[r][g] - m : 0.0;
-                }
-            }
-        }
-    };
-    auto park = [&]() {
-#pragma unroll
-        for (int r = 0; r < RPT; ++r)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                As[(lrow + 64 * r) * LDR + lseg + j] = ra_v[r][j];
-                Bs[(lrow + 64 * r) * LDR + lseg + j] = rb_v[r][j];
-            }
-    };
-    fetch(0);
-    park();
-    __syncthreads();
-    for (int k0 = 0; k0 < G; k0 += KC) {
-        const bool more = k0 + KC < G;
-        if (more) fetch(k0 + KC);
-#pragma unroll
-        for (int kk = 0; kk < KC; kk += 4) {
-            const int k = kk + (lane >> 4), r = lane & 15;
-            double av[WM], bv[WM];
-#pragma unroll
-            for (int a = 0; a < WM; ++a) {
-                av[a] = As[(wr * 16 * WM + 16 * a + r) * LDR + k];
-                bv[a] = Bs[(wc * 16 * WM + 16 * a + r) * LDR + k];
-            }
-#pragma unroll
-            for (int a = 0; a < WM; ++a)
-#pragma unroll
-                for (int b = 0; b < WM; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
-        __syncthreads();   // every wavefront is done with this stage's tiles
-        if (more) park();
-        __syncthreads();
-    }
+    dbl4_t acc[WM][WM];
+    gram::tile_product<WM, true>(pa, pb, G, even, mean, smem_d, acc);
     // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg
 #pragma unroll
     for (int a = 0; a < WM; ++a)

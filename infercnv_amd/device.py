@@ -349,6 +349,42 @@ def cell_distances(x, cells):
     return out
 
 
+def knn(x, problems, k):
+    """Exact k nearest neighbours per problem: RANN::nn2(t(expr.data[genes, cells]), k = k)
+    (R/inferCNV_tumor_subclusters.R:726) for a batch of problems in one call (icnv_knn_dev, DESIGN K8).
+
+    problems: list of (genes, cells) 0-based index vectors (the gene order is the summation order).  Returns
+    (nn_idx int32, nn_dist float64) CUDA tensors of shape (sum of the problems' cells, k), the rows packed by problem;
+    nn_idx holds positions within the problem's cell list (R: 1-based cell numbers)."""
+    L = _lib.load()
+    C, G = _check_matrix(x)
+    gidx, goff = pack_groups([g for g, _ in problems])
+    cidx, coff = pack_groups([c for _, c in problems])
+    gidx, gp = i32(gidx)
+    goff, gop = i32(goff)
+    cidx, cp = i32(cidx)
+    coff, cop = i32(coff)
+    n = int(coff[-1]) if coff.size else 0
+    nn_idx = torch.empty((n, max(int(k), 0)), dtype=torch.int32, device=x.device)
+    nn_dist = torch.empty((n, max(int(k), 0)), dtype=torch.float64, device=x.device)
+    check(L.icnv_knn_dev(_ptr(x), G, C, gp, gop, cp, cop, len(problems), int(k), _ptr(nn_idx), _ptr(nn_dist), _stream()))
+    return nn_idx, nn_dist
+
+
+KNN_STATS = ("calls", "problems", "query_rows", "row_blocks", "screened_rows", "candidates", "overflow_rows",
+             "exhaustive_rows", "forced_exhaustive_rows")
+
+
+def knn_stats(reset=False):
+    """icnv_knn_stats as a dict (synchronises the device); reset=True zeroes the counters afterwards."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(KNN_STATS))()
+    check(L.icnv_knn_stats(out, len(KNN_STATS)))
+    if reset:
+        L.icnv_knn_stats_reset()
+    return dict(zip(KNN_STATS, (int(v) for v in out)))
+
+
 def state_consensus(states, groups, overwrite=False):
     """.get_state_consensus (R/inferCNV_HMM.R:977-987) per group -> (n_groups, G) uint8; with
     overwrite=True also returns the state matrix with every member cell set to its group's consensus."""
