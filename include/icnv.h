@@ -315,6 +315,57 @@ int icnv_knn_dev(const double *expr, int64_t G, int64_t C, const int32_t *gene_i
 int icnv_knn_stats(int64_t *out, int32_t n);
 void icnv_knn_stats_reset(void);   /* R/inferCNV_tumor_subclusters.R:726 */
 
+/* ---- hierarchical clustering ---------------------------------------------- */
+/* fastcluster::hclust(as.dist(D), method) (the reference's hclust, NAMESPACE:57) as the subclustering calls it on
+ * parallelDist(t(x)): R/inferCNV_tumor_subclusters.R:191, 411, 474, 498, 582, 609; .random_smoothed_trees.R:76, 228, 269;
+ * R/inferCNV_ops.R:1930, 3242; R/inferCNV_heatmap.R:719, 755, 1062, 1079.  Nearest-neighbour chain for every method:
+ *   - Lance-Williams update when clusters x < y (sizes s, t) merge at dissimilarity c, for every other cluster k (size v),
+ *     a = D[x,k], b = D[y,k], evaluated left to right exactly as written (no FMA):
+ *       single  a < b ? a : b            complete  a > b ? a : b          average  (s*a + t*b) / (s+t)
+ *       mcquitty (a + b) * 0.5           ward.D / ward.D2  ((v+s)*a - v*c + (v+t)*b) / (s+t+v)
+ *     ward.D2 squares D on entry (d*d) and reports sqrt of each merge dissimilarity.
+ *   - The chain restarts from the first active index when it is empty (after a merge leaves <= 1 element); extending it,
+ *     the tip's nearest active neighbour is the minimum of the key (D[tip,j], rank j), rank(previous chain element) = -1.
+ *     The merged cluster lives on at the larger index y; x is retired.
+ *   - Merges are stable-sorted by dissimilarity and labelled as R does: singletons -(i+1), clusters the 1-based step that
+ *     made them, per row the singleton first, two singletons by index, two clusters by creation.  order = the left-first
+ *     depth-first walk from the last merge, 1-based.
+ * Outputs: merge int32 [(n-1) x 2] column-major (R's layout), height double [n-1], order int32 [n].
+ * Errors: n < 2 or a non-finite distance ICNV_ERR_ARG (as R / fastcluster stop), an unsupported method
+ * ICNV_ERR_UNSUPPORTED, allocation failure ICNV_ERR_NOMEM.  Every argument is validated before any launch; the finiteness
+ * of the distances is checked on the device before the clustering starts.  Unlike the other *_dev entry points these
+ * synchronise `stream`: the finiteness check and the R labelling of the merge list go through the host.
+ * Developer switch: ICNV_HCLUST_FORCE_HBM=1 sends problems of <= 200 cells down the large-problem (HBM) path. */
+#define ICNV_HCLUST_WARD_D 1
+#define ICNV_HCLUST_WARD_D2 2
+#define ICNV_HCLUST_SINGLE 3
+#define ICNV_HCLUST_COMPLETE 4
+#define ICNV_HCLUST_AVERAGE 5
+#define ICNV_HCLUST_MCQUITTY 6
+#define ICNV_HCLUST_CENTROID 7   /* not reducible: ICNV_ERR_UNSUPPORTED */
+#define ICNV_HCLUST_MEDIAN 8     /* not reducible: ICNV_ERR_UNSUPPORTED */
+/* hclust(as.dist(D), method) of an n x n DEVICE distance matrix (row i at dist + i*ld, symmetric, zero diagonal; it is not
+ * modified).  merge / height / order: DEVICE pointers.  (R/inferCNV_tumor_subclusters.R:191, R/inferCNV_ops.R:3242) */
+int icnv_hclust_dev(const double *dist, int64_t ld, int32_t n, int32_t method, int32_t *merge, double *height, int32_t *order,
+                    void *stream);
+/* hclust(parallelDist(t(expr[genes_p, cells_p])), method) for a BATCH of problems described as for icnv_knn (HOST index
+ * lists, 0-based; the z-score-filtered gene lists of R/inferCNV_tumor_subclusters.R:45-71): the Euclidean distances on the
+ * fp64 matrix cores (K7's tile product, centred cells), then the clustering; the matrices never leave the device.
+ * Problem p has n_p = cell_off[p+1] - cell_off[p] >= 2 cells; its outputs start at merge + 2*(cell_off[p] - p),
+ * height + (cell_off[p] - p) and order + cell_off[p].  (R/inferCNV_tumor_subclusters.R:191, 582, 609) */
+int icnv_hclust_cells(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off,
+                      const int32_t *cell_idx, const int32_t *cell_off, int32_t n_prob, int32_t method, int32_t *merge,
+                      double *height, int32_t *order);
+/* Same contract on device pointers (expr, merge, height, order); the index lists stay on the HOST. */
+int icnv_hclust_cells_dev(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off,
+                          const int32_t *cell_idx, const int32_t *cell_off, int32_t n_prob, int32_t method, int32_t *merge,
+                          double *height, int32_t *order, void *stream);
+/* Counters of the hclust calls since the last reset (R/inferCNV_tumor_subclusters.R:191), n = int64 slots (<= 6 written):
+ *   out[0] calls   out[1] problems   out[2] problems clustered in LDS   out[3] problems clustered in HBM
+ *   out[4] chain steps (nearest-neighbour searches)   out[5] wall time of the calls in microseconds */
+int icnv_hclust_stats(int64_t *out, int32_t n);
+void icnv_hclust_stats_reset(void);   /* R/inferCNV_tumor_subclusters.R:191 */
+
 /* ---- HMM ---------------------------------------------------------------- */
 /* Viterbi.dthmm.adj (R/inferCNV_HMM.R:1101-1176) for every (cell, chromosome):
  * predict_CNV_via_HMM_on_indiv_cells (R/inferCNV_HMM.R:284-324) with K = 6 and

@@ -114,6 +114,11 @@ PROTOTYPES = {
     "icnv_knn_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _ip, _ip, _i32, _i32, _vp, _vp, _vp]),
     "icnv_knn_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_knn_stats_reset": (None, []),
+    "icnv_hclust_dev": (ct.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "icnv_hclust_cells": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _ip, _ip, _i32, _i32, _vp, _vp, _vp]),
+    "icnv_hclust_cells_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _ip, _ip, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "icnv_hclust_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_hclust_stats_reset": (None, []),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

@@ -1,0 +1,50 @@
+// Shared between api.hip (validation, planning, R labelling, stats) and hclust_kernels.hip (K9, the nearest-neighbour
+// chain of hclust).  DESIGN.md section 4 K9.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace icnv {
+
+// LDS path: the condensed matrix (n (n-1) / 2 doubles), the chain, the sizes and the active bitmask of one problem in the
+// 160 KiB of one workgroup.  201 cells would still fit (162 436 B); 200 is the documented limit.
+constexpr int HC_LDS_MAX_N = 200;
+constexpr size_t hc_lds_bytes(int n) { return (size_t)n * (n - 1) / 2 * 8 + (size_t)n * 8 + ((size_t)n + 31) / 32 * 4; }
+static_assert(hc_lds_bytes(HC_LDS_MAX_N) + 256 <= 160 * 1024, "the LDS path must fit one workgroup");
+// HBM path: the active bitmask stays in LDS (n / 8 bytes <= 64 KiB)
+constexpr int HC_HBM_MAX_N = 1 << 19;
+
+struct HclustArgs {           // one launch; every pointer is device memory
+    int32_t n_run;            // problems of this launch (one workgroup each)
+    const int32_t *run;       // [n_run] problem ids
+    const int32_t *n;         // per problem: cells
+    const int64_t *d_off;     // per problem: its n x n row-major matrix at D + d_off[p]
+    double *D;                // mutated by the HBM path, read by the LDS path
+    const int64_t *m_off;     // per problem: its n - 1 raw merges (= cell offset - p)
+    int32_t *mx, *my;         // raw merges in chain order: positions x < y (the cluster lives on at y) ...
+    double *mh;               // ... and their dissimilarity (squared distances for ward.D2)
+    const int64_t *c_off;     // per problem: cell offset; HBM path: chain at work + 2 c_off[p], sizes after it
+    int32_t *work;
+    int64_t *steps;           // per problem: chain steps
+    int32_t method;           // ICNV_HCLUST_*
+};
+
+struct HclustGram {           // fused distances: every problem's upper-triangular DT x DT tiles in one launch
+    int32_t n_prob;
+    const int64_t *tile_off;  // [n_prob + 1]
+    const int32_t *n;         // per problem: cells
+    const double *Y;          // K8's centred compact cells (knn prepare): problem p at y_off[p], rows of ld[p] doubles
+    const int64_t *y_off;
+    const int32_t *ld;
+    const double *norm;       // ||y_i||^2 per packed cell
+    const int64_t *c_off;     // per problem: first packed cell
+    const int64_t *d_off;
+    double *D;
+};
+
+int launch_hclust_prep(double *D, int64_t total, bool square, uint32_t *bad, hipStream_t s);
+int launch_hclust_gram(const HclustGram &g, int64_t n_tiles, int wm, hipStream_t s);
+int launch_hclust_lds(const HclustArgs &a, int max_n, hipStream_t s);
+int launch_hclust_hbm(const HclustArgs &a, int max_n, hipStream_t s);
+
+}  // namespace icnv

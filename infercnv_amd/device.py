@@ -385,6 +385,73 @@ def knn_stats(reset=False):
     return dict(zip(KNN_STATS, (int(v) for v in out)))
 
 
+HCLUST_METHODS = {"ward.D": 1, "ward.D2": 2, "single": 3, "complete": 4, "average": 5, "mcquitty": 6, "centroid": 7,
+                  "median": 8}   # ICNV_HCLUST_* of include/icnv.h
+
+
+def _hclust_code(method):
+    """An R method name -> its ICNV_HCLUST_* code; an unknown name -> -1, which the library refuses (ICNV_ERR_UNSUPPORTED)."""
+    return HCLUST_METHODS.get(method, -1) if isinstance(method, str) else int(method)
+
+
+def hclust(dist, method="ward.D2"):
+    """hclust(as.dist(dist), method) of an (n, n) CUDA float64 distance matrix (rows contiguous; fastcluster's hclust as the
+    reference calls it, R/inferCNV_tumor_subclusters.R:191, R/inferCNV_ops.R:3242) by icnv_hclust_dev (DESIGN K9).
+    Returns CUDA tensors (merge int32 (n-1, 2), height float64 (n-1,), order int32 (n,)) with R's values: merge rows as R
+    stores them (singletons -(i+1), clusters by step), order 1-based.  Synchronises the device."""
+    L = _lib.load()
+    n, n2, ld = _check_matrix_ld(dist)
+    if n != n2:
+        raise ValueError("dist must be square")
+    m = max(n - 1, 0)
+    merge = torch.empty((2, m), dtype=torch.int32, device=dist.device)      # column-major (n-1) x 2
+    height = torch.empty(m, dtype=torch.float64, device=dist.device)
+    order = torch.empty(n, dtype=torch.int32, device=dist.device)
+    check(L.icnv_hclust_dev(_ptr(dist), ld, n, _hclust_code(method), _ptr(merge), _ptr(height), _ptr(order), _stream()))
+    return merge.t(), height, order
+
+
+def hclust_cells(x, problems, method="ward.D2"):
+    """hclust(parallelDist(t(expr.data[genes, cells])), method) for a batch of problems in one call (icnv_hclust_cells_dev,
+    DESIGN K9): the distances on the matrix cores, the clustering in LDS or HBM, nothing but the result leaves the device.
+    problems: list of (genes, cells) 0-based index vectors, at least two cells each.  Returns a list of (merge, height,
+    order) CUDA tensors per problem, as `hclust` returns them."""
+    L = _lib.load()
+    C, G = _check_matrix(x)
+    gidx, goff = pack_groups([g for g, _ in problems])
+    cidx, coff = pack_groups([c for _, c in problems])
+    gidx, gp = i32(gidx)
+    goff, gop = i32(goff)
+    cidx, cp = i32(cidx)
+    coff, cop = i32(coff)
+    cells = int(coff[-1]) if coff.size else 0
+    merges = max(cells - len(problems), 0)
+    merge = torch.empty(2 * merges, dtype=torch.int32, device=x.device)
+    height = torch.empty(merges, dtype=torch.float64, device=x.device)
+    order = torch.empty(cells, dtype=torch.int32, device=x.device)
+    check(L.icnv_hclust_cells_dev(_ptr(x), G, C, gp, gop, cp, cop, len(problems), _hclust_code(method), _ptr(merge),
+                                  _ptr(height), _ptr(order), _stream()))
+    out = []
+    for p in range(len(problems)):
+        n = int(coff[p + 1] - coff[p])
+        m0 = int(coff[p]) - p
+        out.append((merge[2 * m0:2 * (m0 + n - 1)].view(2, n - 1).t(), height[m0:m0 + n - 1], order[int(coff[p]):int(coff[p + 1])]))
+    return out
+
+
+HCLUST_STATS = ("calls", "problems", "lds_problems", "hbm_problems", "chain_steps", "us")
+
+
+def hclust_stats(reset=False):
+    """icnv_hclust_stats as a dict (`us`: wall time of the calls in microseconds); reset=True zeroes the counters afterwards."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(HCLUST_STATS))()
+    check(L.icnv_hclust_stats(out, len(HCLUST_STATS)))
+    if reset:
+        L.icnv_hclust_stats_reset()
+    return dict(zip(HCLUST_STATS, (int(v) for v in out)))
+
+
 def state_consensus(states, groups, overwrite=False):
     """.get_state_consensus (R/inferCNV_HMM.R:977-987) per group -> (n_groups, G) uint8; with
     overwrite=True also returns the state matrix with every member cell set to its group's consensus."""

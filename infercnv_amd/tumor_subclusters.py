@@ -4,8 +4,14 @@ between the cells of one tumor group, computed on the GPU (icnv_cell_distances_d
 clustering itself (hclust / Leiden) stays in R -- SURVEY.md 8f #4 scopes only the dense contraction.
 
 The Leiden route's neighbour search (R/inferCNV_tumor_subclusters.R:646-741, RANN::nn2) is the exact kNN of
-icnv_knn_dev (DESIGN K8): `nn2`, `snn_adjacency`, `knn_per_chr`, with the reference-based gene filter of :45-71."""
+icnv_knn_dev (DESIGN K8): `nn2`, `snn_adjacency`, `knn_per_chr`, with the reference-based gene filter of :45-71.
+
+The hierarchical clustering itself, `hclust(parallelDist(t(x)), method = hclust_method)` (:191, 582, 609 and the other
+call sites of DESIGN K9), runs on the GPU too: `hclust` returns R's hclust object without the distance matrix ever leaving
+the device."""
 from __future__ import annotations
+
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -147,3 +153,31 @@ def knn_per_chr(infercnv_obj: InfercnvObject, tumor_groups, k_nn: int, z_score_f
             results[key] = (idx[r0:r0 + cells.size], dist[r0:r0 + cells.size])
             r0 += cells.size
     return results, skipped
+
+
+# ------------------------------------------------------------------ hierarchical clustering (DESIGN K9)
+@dataclass
+class HClust:
+    """The fields of R's hclust object (stats::hclust, as fastcluster::hclust returns it): merge (n-1, 2) int32 with
+    singletons -(i+1) and clusters by step, height (n-1,), order (n,) 1-based, labels (the cells), method, dist_method."""
+    merge: np.ndarray
+    height: np.ndarray
+    order: np.ndarray
+    labels: np.ndarray
+    method: str
+    dist_method: str = "euclidean"
+
+
+def hclust(infercnv_obj: InfercnvObject, cells, method: str = "ward.D2", genes=None):
+    """hclust(parallelDist(t(expr.data[genes, cells])), method = method) as the subclustering calls it
+    (R/inferCNV_tumor_subclusters.R:191, 582, 609; R/inferCNV_ops.R:1930, 3242), on the GPU (icnv_hclust_cells_dev).
+    genes: 0-based rows (default all; the z-score-filtered genes of :45-71 come from `zscore_kept_genes`).  labels are the
+    cells' column names (InfercnvObject.cells())."""
+    cells = np.asarray(cells, dtype=np.int32)
+    G = np.asarray(infercnv_obj.expr_data).shape[0]
+    genes = np.arange(G, dtype=np.int32) if genes is None else np.asarray(genes, dtype=np.int32)
+    if cells.ndim != 1 or genes.ndim != 1:
+        raise ValueError("cells and genes must be index vectors")
+    (merge, height, order), = device.hclust_cells(_to_device(infercnv_obj), [(genes, cells)], method)
+    labels = np.asarray(infercnv_obj.cells())[cells]
+    return HClust(merge.cpu().numpy(), height.cpu().numpy(), order.cpu().numpy(), labels, method)
