@@ -366,6 +366,47 @@ int icnv_hclust_cells_dev(const double *expr, int64_t G, int64_t C, const int32_
 int icnv_hclust_stats(int64_t *out, int32_t n);
 void icnv_hclust_stats_reset(void);   /* R/inferCNV_tumor_subclusters.R:191 */
 
+/* ---- random-trees subclustering ------------------------------------------- */
+/* The permutation statistic of tumor_subcluster_partition_method = "random_trees"
+ * (R/inferCNV_tumor_subclusters.random_smoothed_trees.R:217-298, .parameterize_random_cluster_heights_smoothed_trees) for
+ * every clade of one recursion level (:127-213) in ONE call.  Clade p (HOST cell list, 0-based, n_p >= 2 cells, all G genes):
+ *   - the observed matrix x[, S_p] and n_iter copies; copy r (0-based) permutes every gene g across the clade's cells with
+ *     NumPy's Generator(Philox(key = [seed, token[p]], counter = [0, g, r, 0])).permutation(n_p)  (:233-246; R's own stream
+ *     depends on its worker threads and is never seeded, so the library defines this one);
+ *   - caTools::runmean(k = window, endrule = "mean") along the genes of every cell (:221, 259): k = min(window, G), k2 = k / 2,
+ *     output o = the sequential sum (gene order, no FMA) of the window [max(0, o - (k - 1 - k2)), min(G - 1, o + k2)] divided by
+ *     its length; k <= 1 leaves the cell unchanged;
+ *   - .center_columns(, "median") per cell (:223, 261): step 11's median (ICNV_ST_CENTER);
+ *   - hclust(parallelDist(t(.)), method) (:226-229, 264-269): K9's fused distances and chain (icnv_hclust_cells_dev).
+ * Outputs (DEVICE): the observed trees in icnv_hclust_cells' layout and offsets (merge + 2 (cell_off[p] - p), height +
+ * (cell_off[p] - p), order + cell_off[p]); rand_max_height [n_prob x n_iter] = max(h_rand$height) of copy r of clade p at
+ * p * n_iter + r (:270).  Permuted trees never leave the device.  Matrices and distance matrices are built in waves within
+ * ICNV_RT_SCRATCH_MB megabytes (default 8192; at least one matrix per wave); results do not depend on the waves.
+ * Errors: ICNV_ERR_ARG for n_p < 2, window < 1, n_iter < 1, an index out of range or a non-finite value among the clades'
+ * cells (checked on the device before anything is clustered); ICNV_ERR_UNSUPPORTED for centroid / median.  Every argument is
+ * validated before any launch.  Synchronises `stream`. */
+#define ICNV_RT_PERMUTE 0x1u
+#define ICNV_RT_SMOOTH  0x2u
+#define ICNV_RT_CENTER  0x4u
+/* expr: G x C column-major DEVICE matrix; cell_idx / cell_off / token: HOST arrays.
+ * (R/inferCNV_tumor_subclusters.random_smoothed_trees.R:217-298) */
+int icnv_random_trees_dev(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, const int32_t *cell_off,
+                          const uint64_t *token, int32_t n_prob, int32_t window, int32_t n_iter, uint64_t seed, int32_t method,
+                          int32_t *merge, double *height, int32_t *order, double *rand_max_height, void *stream);
+/* Same contract on HOST buffers.  (R/inferCNV_tumor_subclusters.random_smoothed_trees.R:217-298) */
+int icnv_random_trees(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, const int32_t *cell_off,
+                      const uint64_t *token, int32_t n_prob, int32_t window, int32_t n_iter, uint64_t seed, int32_t method,
+                      int32_t *merge, double *height, int32_t *order, double *rand_max_height);
+/* Diagnostic: one (clade, iteration) matrix after the stages in `stages` (ICNV_RT_*), written to the DEVICE buffer out
+ * (n x G, a cell's genes contiguous).  iter = -1 is the observed matrix; ICNV_RT_PERMUTE has no effect on it.  cells: HOST.
+ * (R/inferCNV_tumor_subclusters.random_smoothed_trees.R:221-223, 255-261) */
+int icnv_random_trees_matrix_dev(const double *expr, int64_t G, int64_t C, const int32_t *cells, int32_t n, int32_t window,
+                                 uint64_t seed, uint64_t token, int32_t iter, uint32_t stages, double *out, void *stream);
+/* Counters since the last reset (R/inferCNV_tumor_subclusters.random_smoothed_trees.R:255), n = int64 slots (<= 6 written):
+ *   out[0] calls   out[1] clades   out[2] permuted matrices   out[3] waves   out[4] chain steps   out[5] wall microseconds */
+int icnv_random_trees_stats(int64_t *out, int32_t n);
+void icnv_random_trees_stats_reset(void);   /* R/inferCNV_tumor_subclusters.random_smoothed_trees.R:255 */
+
 /* ---- HMM ---------------------------------------------------------------- */
 /* Viterbi.dthmm.adj (R/inferCNV_HMM.R:1101-1176) for every (cell, chromosome):
  * predict_CNV_via_HMM_on_indiv_cells (R/inferCNV_HMM.R:284-324) with K = 6 and

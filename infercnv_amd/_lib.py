@@ -23,6 +23,7 @@ ST_INVERT_LOG2 = 0x20
 ST_DENOISE = 0x40
 ST_ALL = 0x7F
 ST_CENTER_MEAN = 0x80
+RT_PERMUTE, RT_SMOOTH, RT_CENTER = 0x1, 0x2, 0x4   # ICNV_RT_* stages of icnv_random_trees_matrix_dev
 ST_NA_AWARE = 0x100     # the matrix may hold NaN: cells that do are recomputed with the reference's NA semantics
 
 OK, ERR_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_UNDERFLOW, ERR_NOMEM = 0, 1, 2, 3, 4, 5
@@ -60,6 +61,8 @@ class Counts(ct.Structure):
 _vp, _i64, _i32, _dbl = ct.c_void_p, ct.c_int64, ct.c_int32, ct.c_double
 _ip = ct.POINTER(ct.c_int32)
 _dp = ct.POINTER(ct.c_double)
+_u32, _u64 = ct.c_uint32, ct.c_uint64
+_u64p = ct.POINTER(ct.c_uint64)
 
 # name -> (restype, argtypes); every symbol include/icnv.h declares
 PROTOTYPES = {
@@ -119,6 +122,11 @@ PROTOTYPES = {
     "icnv_hclust_cells_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _ip, _ip, _i32, _i32, _vp, _vp, _vp, _vp]),
     "icnv_hclust_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_hclust_stats_reset": (None, []),
+    "icnv_random_trees_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _u64p, _i32, _i32, _i32, _u64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "icnv_random_trees": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _u64p, _i32, _i32, _i32, _u64, _i32, _vp, _vp, _vp, _vp]),
+    "icnv_random_trees_matrix_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _i32, _i32, _u64, _u64, _i32, _u32, _vp, _vp]),
+    "icnv_random_trees_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_random_trees_stats_reset": (None, []),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

@@ -452,6 +452,68 @@ def hclust_stats(reset=False):
     return dict(zip(HCLUST_STATS, (int(v) for v in out)))
 
 
+def _u64(a):
+    arr = np.ascontiguousarray(np.asarray(a, dtype=np.uint64))
+    return arr, arr.ctypes.data_as(ct.POINTER(ct.c_uint64))
+
+
+def random_trees(x, clades, tokens, window_size=101, n_iter=100, seed=0, method="ward.D2"):
+    """The permutation statistic of the random-trees subclustering for a batch of clades in one call
+    (icnv_random_trees_dev, DESIGN K10; R/inferCNV_tumor_subclusters.random_smoothed_trees.R:217-298): per clade the
+    observed tree of its smoothed, median-centred cells and max(height) of n_iter trees of gene-wise permuted copies.
+    clades: list of 0-based cell index vectors (>= 2 cells each); tokens: one uint64 per clade (the permutation stream's
+    second key word).  Returns (trees, rand_max) -- trees a list of (merge, height, order) CUDA tensors per clade as
+    `hclust` returns them, rand_max a CUDA float64 tensor (n_clades, n_iter).  Synchronises the device."""
+    L = _lib.load()
+    C, G = _check_matrix(x)
+    if len(tokens) != len(clades):
+        raise ValueError("one token per clade")
+    cidx, coff = pack_groups(clades)
+    cidx, cp = i32(cidx)
+    coff, cop = i32(coff)
+    tok, tp = _u64(tokens)
+    P = len(clades)
+    cells = int(coff[-1]) if coff.size else 0
+    merges = max(cells - P, 0)
+    merge = torch.empty(max(2 * merges, 1), dtype=torch.int32, device=x.device)
+    height = torch.empty(max(merges, 1), dtype=torch.float64, device=x.device)
+    order = torch.empty(max(cells, 1), dtype=torch.int32, device=x.device)
+    rand = torch.empty((P, max(int(n_iter), 1)), dtype=torch.float64, device=x.device)
+    check(L.icnv_random_trees_dev(_ptr(x), G, C, cp, cop, tp, P, int(window_size), int(n_iter), int(seed) & (2**64 - 1),
+                                  _hclust_code(method), _ptr(merge), _ptr(height), _ptr(order), _ptr(rand), _stream()))
+    trees = []
+    for p in range(P):
+        n = int(coff[p + 1] - coff[p])
+        m0 = int(coff[p]) - p
+        trees.append((merge[2 * m0:2 * (m0 + n - 1)].view(2, n - 1).t(), height[m0:m0 + n - 1], order[int(coff[p]):int(coff[p + 1])]))
+    return trees, rand
+
+
+def random_trees_matrix(x, cells, window_size=101, seed=0, token=0, iteration=-1, stages=_lib.RT_PERMUTE | _lib.RT_SMOOTH | _lib.RT_CENTER):
+    """One (clade, iteration) matrix of `random_trees` after the stages in `stages` (_lib.RT_PERMUTE | RT_SMOOTH |
+    RT_CENTER), as a CUDA (len(cells), G) float64 tensor (icnv_random_trees_matrix_dev).  iteration=-1: the observed matrix."""
+    L = _lib.load()
+    C, G = _check_matrix(x)
+    cidx, cp = i32(cells)
+    out = torch.empty((max(cidx.size, 1), G), dtype=torch.float64, device=x.device)
+    check(L.icnv_random_trees_matrix_dev(_ptr(x), G, C, cp, int(cidx.size), int(window_size), int(seed) & (2**64 - 1),
+                                         int(token) & (2**64 - 1), int(iteration), int(stages), _ptr(out), _stream()))
+    return out[:cidx.size]
+
+
+RANDOM_TREES_STATS = ("calls", "clades", "permuted", "waves", "chain_steps", "us")
+
+
+def random_trees_stats(reset=False):
+    """icnv_random_trees_stats as a dict (`us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(RANDOM_TREES_STATS))()
+    check(L.icnv_random_trees_stats(out, len(RANDOM_TREES_STATS)))
+    if reset:
+        L.icnv_random_trees_stats_reset()
+    return dict(zip(RANDOM_TREES_STATS, (int(v) for v in out)))
+
+
 def state_consensus(states, groups, overwrite=False):
     """.get_state_consensus (R/inferCNV_HMM.R:977-987) per group -> (n_groups, G) uint8; with
     overwrite=True also returns the state matrix with every member cell set to its group's consensus."""

@@ -8,7 +8,11 @@ icnv_knn_dev (DESIGN K8): `nn2`, `snn_adjacency`, `knn_per_chr`, with the refere
 
 The hierarchical clustering itself, `hclust(parallelDist(t(x)), method = hclust_method)` (:191, 582, 609 and the other
 call sites of DESIGN K9), runs on the GPU too: `hclust` returns R's hclust object without the distance matrix ever leaving
-the device."""
+the device.
+
+The random-trees subclustering (R/inferCNV_tumor_subclusters.random_smoothed_trees.R, DESIGN K10) runs its permutation
+statistic on the GPU (icnv_random_trees_dev), one call per recursion level: `define_signif_tumor_subclusters_via_random_smooothed_trees`,
+with the recursion itself in the pure-Python `random_trees_partition`."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -181,3 +185,148 @@ def hclust(infercnv_obj: InfercnvObject, cells, method: str = "ward.D2", genes=N
     (merge, height, order), = device.hclust_cells(_to_device(infercnv_obj), [(genes, cells)], method)
     labels = np.asarray(infercnv_obj.cells())[cells]
     return HClust(merge.cpu().numpy(), height.cpu().numpy(), order.cpu().numpy(), labels, method)
+
+
+# ------------------------------------------------------------------ random-trees subclustering (DESIGN K10)
+RANDOM_TREES_ITERATIONS = 100   # num_rand_iters (R/inferCNV_tumor_subclusters.random_smoothed_trees.R:254)
+
+
+def fnv1a64(name: str) -> int:
+    """FNV-1a-64 of the UTF-8 bytes of a clade name: the clade's token, the second key word of its permutation stream."""
+    h = 0xCBF29CE484222325
+    for b in str(name).encode("utf-8"):
+        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def cutree_h(merge, height, h):
+    """cutree(tree, h = h) (stats::cutree / R_cutree): k = n + 1 - which.max(c(height, Inf) > h) groups, numbered 1.. in order
+    of first appearance among the cells."""
+    merge = np.asarray(merge)
+    height = np.asarray(height, dtype=np.float64)
+    n = merge.shape[0] + 1
+    k = n - int(np.flatnonzero(np.append(height, np.inf) > h)[0])
+    parent = np.arange(2 * n - 1)
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    for step in range(n - k):   # the first n - k merges
+        for v in merge[step]:
+            node = -int(v) - 1 if v < 0 else n + int(v) - 1
+            parent[find(node)] = n + step
+    labels = np.zeros(n, dtype=np.int64)
+    seen = {}
+    for c in range(n):
+        labels[c] = seen.setdefault(find(c), len(seen) + 1)
+    return labels
+
+
+def random_trees_pvalue(max_height: float, rand_max_heights) -> float:
+    """1 - ecdf(rand)(max_height) as R evaluates it (:148-156, 291): 1 - (#{rand <= max_height} / n) in doubles; 1 when the
+    observed tree is flat (max_height == 0)."""
+    rand = np.asarray(rand_max_heights, dtype=np.float64)
+    if not max_height > 0:
+        return 1.0
+    return 1.0 - int(np.count_nonzero(rand <= max_height)) / rand.size
+
+
+def random_trees_partition(groups, clade_fn, p_val, max_recursion_depth=3, min_cluster_size_recurse=10):
+    """The recursion of the random-trees subclustering (R/inferCNV_tumor_subclusters.random_smoothed_trees.R:3-67, 118-213)
+    for every tumor group at once, one `clade_fn` call per recursion level.
+
+    groups: {group: 0-based cell indices} in R's order.  clade_fn(list of (clade name, cell indices)) -> one
+    ((merge, height, order), rand_max_heights) per clade: the clade's observed tree in R's format and the maximum heights of
+    its permuted trees.  Returns (hc, subclusters): hc[group] = the level-1 observed tree, subclusters[group][name] = the
+    group's cells of the final clade `name` in their original order, names sorted (split(grps, grps), C-locale order)."""
+    groups = {g: np.asarray(c, dtype=np.int64) for g, c in groups.items()}
+    for g, c in groups.items():
+        if c.size < 2:   # R stops in apply() / hclust
+            raise ValueError(f"tumor group {g!r} has {c.size} cell(s): at least two are needed to cluster")
+    names = {g: np.array([f"{g}.1"] * c.size, dtype=object) for g, c in groups.items()}
+    pending = [(g, np.arange(c.size), f"{g}.1") for g, c in groups.items()]
+    hc = {}
+    depth = 1
+    while pending and depth <= max_recursion_depth:
+        results = clade_fn([(name, groups[g][pos]) for g, pos, name in pending])
+        nxt = []
+        for (g, pos, name), ((merge, height, order), rand) in zip(pending, results):
+            height = np.asarray(height, dtype=np.float64)
+            if depth == 1:
+                hc[g] = (merge, height, order)
+            max_height = float(np.max(height))
+            if random_trees_pvalue(max_height, rand) > p_val:
+                continue                                      # "No cluster pruning"
+            cut = _r_mean(height[-2:])                        # mean(c(h[n-1], h[n-2])); one value when n == 2
+            labels = cutree_h(merge, height, cut)
+            sizes = np.bincount(labels)[1:]
+            if np.all(sizes < min_cluster_size_recurse):    # none big enough: the clade keeps its name
+                continue
+            for grp in range(1, sizes.size + 1):
+                sub = pos[labels == grp]
+                sub_name = f"{name}.{grp}"
+                names[g][sub] = sub_name
+                if sub.size >= min_cluster_size_recurse:
+                    nxt.append((g, sub, sub_name))
+        pending = nxt
+        depth += 1
+    subclusters = {}
+    for g, c in groups.items():
+        subclusters[g] = {nm: c[names[g] == nm] for nm in sorted(set(names[g].tolist()))}
+    return hc, subclusters
+
+
+def random_trees_groups(infercnv_obj: InfercnvObject, cluster_by_groups):
+    """The tumor groups of the random-trees subclustering (:15-26): every observation and reference group, or
+    all_observations (the observation groups' cells concatenated) and the reference groups."""
+    obs = {k: np.asarray(v, dtype=np.int64) for k, v in infercnv_obj.observation_grouped_cell_indices.items()}
+    ref = {k: np.asarray(v, dtype=np.int64) for k, v in infercnv_obj.reference_grouped_cell_indices.items()}
+    if cluster_by_groups:
+        return {**obs, **ref}
+    allobs = np.concatenate(list(obs.values())) if obs else np.zeros(0, dtype=np.int64)
+    return {"all_observations": allobs, **ref}
+
+
+def define_signif_tumor_subclusters_via_random_smooothed_trees(infercnv_obj: InfercnvObject, p_val, hclust_method,
+                                                               cluster_by_groups, window_size=101, max_recursion_depth=3,
+                                                               min_cluster_size_recurse=10, seed=0):
+    """tumor_subcluster_partition_method = "random_trees" (R/inferCNV_tumor_subclusters.random_smoothed_trees.R:3-67; run()
+    step 7, R/inferCNV_ops.R:716-730) on the GPU: every recursion level of every group in one icnv_random_trees_dev call.
+
+    The statistic works on subtract_ref_expr_from_obs(infercnv_obj, inv_log=TRUE); the returned copy keeps the input's
+    expr_data and gets tumor_subclusters = {"hc": {group: HClust}, "subclusters": {group: {name: cell indices}}}.
+    The null trees come from the library's own stream (icnv.h, K10): NumPy's Philox keyed by (seed, FNV-1a-64 of the clade
+    name); R's is unseeded and thread-dependent.  The hspike mirror uses seed + 1."""
+    import torch
+    from . import ops
+    work = infercnv_obj.copy()
+    work.hspike = None
+    sub = ops.subtract_ref_expr_from_obs(work, inv_log=True)
+    groups = random_trees_groups(infercnv_obj, cluster_by_groups)
+    x = []   # the subtracted matrix on the device, uploaded by the first level
+
+    def clade_fn(clades):
+        if not x:
+            x.append(torch.from_numpy(np.ascontiguousarray(np.asarray(sub.expr_data, dtype=np.float64).T)).cuda())
+        trees, rand = device.random_trees(x[0], [c for _, c in clades], [fnv1a64(n) for n, _ in clades], window_size,
+                                          RANDOM_TREES_ITERATIONS, seed, hclust_method)
+        rand = rand.cpu().numpy()
+        return [((m.cpu().numpy(), h.cpu().numpy(), o.cpu().numpy()), rand[i]) for i, (m, h, o) in enumerate(trees)]
+
+    hc, subclusters = random_trees_partition(groups, clade_fn, p_val, max_recursion_depth, min_cluster_size_recurse)
+    cell_names = np.asarray(infercnv_obj.cells())
+    out = infercnv_obj.copy()
+    out.tumor_subclusters = {
+        "hc": {g: HClust(m, h, o, cell_names[groups[g]], hclust_method) for g, (m, h, o) in hc.items()},
+        "subclusters": subclusters,
+    }
+    if infercnv_obj.hspike is not None:
+        # "-mirroring for hspike" (:49-54), with the reference's positional slip: its call binds cluster_by_groups =
+        # window_size, window_size = max_recursion_depth and max_recursion_depth = min_cluster_size_recurse
+        out.hspike = define_signif_tumor_subclusters_via_random_smooothed_trees(
+            infercnv_obj.hspike, p_val, hclust_method, window_size, max_recursion_depth, min_cluster_size_recurse,
+            seed=seed + 1)
+    return out
