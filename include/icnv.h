@@ -278,8 +278,9 @@ int icnv_normalize_log2(const double *expr_in, double *expr_out, int64_t G, int6
 /* parallelDist(t(expr.data[, cells])), method "euclidean", as the reference calls it before hclust
  * (R/inferCNV_tumor_subclusters.R:191; R/inferCNV_ops.R:1930, 3242; R/inferCNV_heatmap.R:719-1079):
  * dist_out [n x n] (symmetric, zero diagonal; the R `dist` object is its lower triangle in column order).
- * cell_idx [n] HOST, 0-based.  fp64 Gram matrix of the group-centred cells on the matrix cores
- * (v_mfma_f64_16x16x4_f64), D_ij = sqrt(max(0, S_ii + S_jj - 2 S_ij)). */
+ * cell_idx [n] HOST, 0-based.  Bit-equal to R's sequential dist: D_ij = sqrt(d2_ij) (correctly rounded), d2_ij the fp64
+ * sum over the genes in order of fl(fl(x_gi - x_gj)^2) on the raw values (no centring, no FMA); D_ii = 0.  Identical
+ * cells are at distance exactly 0 and the matrix is exactly symmetric. */
 int icnv_cell_distances(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, int64_t n, double *dist_out);
 int icnv_cell_distances_dev(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, int64_t n, double *dist_out,
                             void *stream);
@@ -349,8 +350,9 @@ void icnv_knn_stats_reset(void);   /* R/inferCNV_tumor_subclusters.R:726 */
 int icnv_hclust_dev(const double *dist, int64_t ld, int32_t n, int32_t method, int32_t *merge, double *height, int32_t *order,
                     void *stream);
 /* hclust(parallelDist(t(expr[genes_p, cells_p])), method) for a BATCH of problems described as for icnv_knn (HOST index
- * lists, 0-based; the z-score-filtered gene lists of R/inferCNV_tumor_subclusters.R:45-71): the Euclidean distances on the
- * fp64 matrix cores (K7's tile product, centred cells), then the clustering; the matrices never leave the device.
+ * lists, 0-based; the z-score-filtered gene lists of R/inferCNV_tumor_subclusters.R:45-71): the Euclidean distances
+ * bit-equal to R's sequential dist over the problem's genes in list order (as icnv_cell_distances), then the clustering; the
+ * matrices never leave the device.  So merge, height and order are those of icnv_hclust_dev on that sequential dist.
  * Problem p has n_p = cell_off[p+1] - cell_off[p] >= 2 cells; its outputs start at merge + 2*(cell_off[p] - p),
  * height + (cell_off[p] - p) and order + cell_off[p].  (R/inferCNV_tumor_subclusters.R:191, 582, 609) */
 int icnv_hclust_cells(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off,
@@ -377,7 +379,8 @@ void icnv_hclust_stats_reset(void);   /* R/inferCNV_tumor_subclusters.R:191 */
  *     output o = the sequential sum (gene order, no FMA) of the window [max(0, o - (k - 1 - k2)), min(G - 1, o + k2)] divided by
  *     its length; k <= 1 leaves the cell unchanged;
  *   - .center_columns(, "median") per cell (:223, 261): step 11's median (ICNV_ST_CENTER);
- *   - hclust(parallelDist(t(.)), method) (:226-229, 264-269): K9's fused distances and chain (icnv_hclust_cells_dev).
+ *   - hclust(parallelDist(t(.)), method) (:226-229, 264-269): K9's fused distances, bit-equal to R's sequential dist of the
+ *     matrix above over all G genes in order, and chain (icnv_hclust_cells_dev).
  * Outputs (DEVICE): the observed trees in icnv_hclust_cells' layout and offsets (merge + 2 (cell_off[p] - p), height +
  * (cell_off[p] - p), order + cell_off[p]); rand_max_height [n_prob x n_iter] = max(h_rand$height) of copy r of clade p at
  * p * n_iter + r (:270).  Permuted trees never leave the device.  Matrices and distance matrices are built in waves within

@@ -1707,7 +1707,8 @@ int icnv_group_means_dev(const double *expr, int64_t G, int64_t C, const int32_t
 }
 
 // parallelDist(t(expr[, cells])) (Euclidean) as the reference computes it before hclust
-// (R/inferCNV_tumor_subclusters.R:191, R/inferCNV_ops.R:1930, 3242): full symmetric n x n matrix.
+// (R/inferCNV_tumor_subclusters.R:191, R/inferCNV_ops.R:1930, 3242): full symmetric n x n matrix, R's sequential dist bit
+// for bit (distance_kernels.hip).
 int icnv_cell_distances_dev(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, int64_t n, double *dist_out,
                             void *stream) {
     if (!expr || !dist_out || !cell_idx || G < 1 || G > 0x7fffffff || n < 1 || n > 0x7fffffff)
@@ -1715,19 +1716,19 @@ int icnv_cell_distances_dev(const double *expr, int64_t G, int64_t C, const int3
     int rc = validate_index_list(cell_idx, n, C, "cell");
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    DevBuf d_idx, d_off, d_part, d_mean, d_diag;
-    const int32_t off[2] = {0, (int32_t)n};
-    if ((rc = upload(d_idx, cell_idx, (size_t)n, s))) return rc;
-    if ((rc = upload(d_off, off, 2, s))) return rc;
-    const int ns = group_means_nsplit((int32_t)G, 1);
-    if ((rc = d_part.alloc((size_t)ns * 3 * G * sizeof(double))) || (rc = d_mean.alloc((size_t)G * sizeof(double))) ||
-        (rc = d_diag.alloc((size_t)n * sizeof(double))))
+    const int32_t nn = (int32_t)n;
+    std::vector<int64_t> toff;
+    const int dt = exact_dist_plan(&nn, 1, toff);
+    const int64_t coff[2] = {0, n}, doff[1] = {0};
+    DevBuf d_idx, d_coff, d_n, d_toff, d_doff;
+    if ((rc = upload(d_idx, cell_idx, (size_t)n, s)) || (rc = upload(d_coff, coff, 2, s)) || (rc = upload(d_n, &nn, 1, s)) ||
+        (rc = upload(d_toff, toff.data(), toff.size(), s)) || (rc = upload(d_doff, doff, 1, s)))
         return rc;
-    if ((rc = launch_group_means_ws(expr, (int32_t)G, d_idx.as<int32_t>(), d_off.as<int32_t>(), 1, ns, d_part.as<double>(),
-                                    d_mean.as<double>(), s)))
-        return rc;
-    return launch_cell_distances(expr, (int32_t)G, d_idx.as<int32_t>(), (int32_t)n, d_mean.as<double>(), d_diag.as<double>(),
-                                 dist_out, s);
+    DistArgs a{};
+    a.x = expr; a.ldx = G; a.G = (int32_t)G;
+    a.cell_idx = d_idx.as<int32_t>(); a.cell_off = d_coff.as<int64_t>(); a.n = d_n.as<int32_t>();
+    a.n_prob = 1; a.tile_off = d_toff.as<int64_t>(); a.d_off = d_doff.as<int64_t>(); a.D = dist_out;
+    return launch_exact_dist(a, dt, toff[1], s);
 }
 
 int icnv_cell_distances(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, int64_t n, double *dist_out) {
@@ -2164,53 +2165,29 @@ int icnv_hclust_cells_dev(const double *expr, int64_t G, int64_t C, const int32_
     int rc = hclust_cells_validate(expr, G, C, gene_idx, gene_off, cell_idx, cell_off, n_prob, method, merge, height, order);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    // K8's gather: the problem's cells over its genes, centred, compact rows of even length, and their squared norms
-    std::vector<int64_t> goff(n_prob + 1), coff(n_prob + 1), yoff(n_prob + 1), toff(n_prob + 1), doff(n_prob + 1);
-    std::vector<int32_t> ld(n_prob), n(n_prob);
+    // every problem's distances straight into the workspace, R's sequential dist over the problem's genes (distance_kernels.hip)
+    std::vector<int64_t> goff(n_prob + 1), coff(n_prob + 1), doff(n_prob + 1), toff;
+    std::vector<int32_t> n(n_prob);
     for (int32_t p = 0; p <= n_prob; ++p) { goff[p] = gene_off[p]; coff[p] = cell_off[p]; }
-    yoff[0] = doff[0] = 0;
-    int64_t t128 = 0;
+    doff[0] = 0;
     for (int32_t p = 0; p < n_prob; ++p) {
-        const int64_t Gp = goff[p + 1] - goff[p];
         n[p] = (int32_t)(coff[p + 1] - coff[p]);
-        ld[p] = (int32_t)(Gp + (Gp & 1));
-        yoff[p + 1] = yoff[p] + (int64_t)n[p] * ld[p];
         doff[p + 1] = doff[p] + (int64_t)n[p] * n[p];
-        const int64_t nt = (n[p] + 127) / 128;
-        t128 += nt * (nt + 1) / 2;
     }
-    const int wm = t128 >= 2 * (int64_t)num_cus() ? 4 : 2, DT = 32 * wm;
-    toff[0] = 0;
-    for (int32_t p = 0; p < n_prob; ++p) {
-        const int64_t nt = (n[p] + DT - 1) / DT;
-        toff[p + 1] = toff[p] + nt * (nt + 1) / 2;
-    }
+    const int dt = exact_dist_plan(n.data(), n_prob, toff);
     if (toff[n_prob] > 0x7fffffff || coff[n_prob] > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "hclust: batch too large");
-    const int64_t total_rows = coff[n_prob], total_genes = goff[n_prob];
-    DevBuf d_gidx, d_goff, d_cidx, d_coff, d_yoff, d_ld, d_shift, d_Y, d_norm, d_toff, d_n, d_doff, d_D;
-    if ((rc = upload(d_gidx, gene_idx, (size_t)total_genes, s)) || (rc = upload(d_goff, goff.data(), goff.size(), s)) ||
-        (rc = upload(d_cidx, cell_idx, (size_t)total_rows, s)) || (rc = upload(d_coff, coff.data(), coff.size(), s)) ||
-        (rc = upload(d_yoff, yoff.data(), yoff.size(), s)) || (rc = upload(d_ld, ld.data(), ld.size(), s)) ||
+    DevBuf d_gidx, d_goff, d_cidx, d_coff, d_toff, d_n, d_doff, d_D;
+    if ((rc = upload(d_gidx, gene_idx, (size_t)goff[n_prob], s)) || (rc = upload(d_goff, goff.data(), goff.size(), s)) ||
+        (rc = upload(d_cidx, cell_idx, (size_t)coff[n_prob], s)) || (rc = upload(d_coff, coff.data(), coff.size(), s)) ||
         (rc = upload(d_toff, toff.data(), toff.size(), s)) || (rc = upload(d_n, n.data(), n.size(), s)) ||
-        (rc = upload(d_doff, doff.data(), doff.size(), s)) || (rc = d_shift.alloc((size_t)total_genes * sizeof(double))) ||
-        (rc = d_Y.alloc((size_t)yoff[n_prob] * sizeof(double))) || (rc = d_norm.alloc((size_t)total_rows * sizeof(double))) ||
-        (rc = d_D.alloc((size_t)doff[n_prob] * sizeof(double))))
+        (rc = upload(d_doff, doff.data(), doff.size(), s)) || (rc = d_D.alloc((size_t)doff[n_prob] * sizeof(double))))
         return rc;
-    KnnArgs ka{};
-    ka.x = expr; ka.G = (int32_t)G;
-    ka.gene_idx = d_gidx.as<int32_t>(); ka.gene_off = d_goff.as<int64_t>();
-    ka.cell_idx = d_cidx.as<int32_t>(); ka.cell_off = d_coff.as<int64_t>();
-    ka.n_prob = n_prob; ka.total_genes = total_genes; ka.total_rows = total_rows;
-    ka.shift = d_shift.as<double>(); ka.Y = d_Y.as<double>(); ka.y_off = d_yoff.as<int64_t>(); ka.ld = d_ld.as<int32_t>();
-    ka.norm = d_norm.as<double>();
-    if ((rc = launch_knn_prepare(ka, s))) return rc;
-    HclustGram g;
-    g.n_prob = n_prob; g.tile_off = d_toff.as<int64_t>(); g.n = d_n.as<int32_t>();
-    g.Y = ka.Y; g.y_off = ka.y_off; g.ld = ka.ld; g.norm = ka.norm; g.c_off = d_coff.as<int64_t>();
-    g.d_off = d_doff.as<int64_t>(); g.D = d_D.as<double>();
-    if ((rc = launch_hclust_gram(g, toff[n_prob], wm, s))) return rc;
-    d_shift.release();
-    d_Y.release();
+    DistArgs a{};
+    a.x = expr; a.ldx = G; a.G = (int32_t)G;
+    a.gene_idx = d_gidx.as<int32_t>(); a.gene_off = d_goff.as<int64_t>();
+    a.cell_idx = d_cidx.as<int32_t>(); a.cell_off = d_coff.as<int64_t>(); a.n = d_n.as<int32_t>();
+    a.n_prob = n_prob; a.tile_off = d_toff.as<int64_t>(); a.d_off = d_doff.as<int64_t>(); a.D = d_D.as<double>();
+    if ((rc = launch_exact_dist(a, dt, toff[n_prob], s))) return rc;
     return hclust_run(d_D.as<double>(), n, coff, method, merge, height, order, s, t0);
 }
 
@@ -2368,66 +2345,42 @@ int icnv_random_trees_dev(const double *expr, int64_t G, int64_t C, const int32_
         }
         DevBuf d_D;
         if ((rc = d_D.alloc((size_t)d_off[nw] * sizeof(double)))) return rc;
-        for (int i0 = 0; i0 < nw;) {   // sub-waves: matrices -> K8's centred compact cells -> K7 / K9's tile product into D
+        for (int i0 = 0; i0 < nw;) {   // sub-waves: matrices -> R's sequential dist into D (distance_kernels.hip)
             int i1 = i0;
             int64_t mused = 0;
             while (i1 < nw && (i1 == i0 || mused + m_bytes(n[i1]) <= cap / 2)) mused += m_bytes(n[i1++]);
             const int ns = i1 - i0;
-            std::vector<int32_t> clade(ns), iter(ns), gidx((size_t)ns * G), ldv(ns, (int32_t)ld), ids;
-            std::vector<int64_t> row(ns + 1), goff(ns + 1), yoff(ns + 1), toff(ns + 1), doff(ns + 1);
+            std::vector<int32_t> clade(ns), iter(ns), ids;
+            std::vector<int64_t> row(ns + 1), doff(ns + 1), toff;
             row[0] = 0;
-            int64_t t128 = 0;
             for (int i = 0; i < ns; ++i) {
                 const int64_t q = q0 + i0 + i;
                 clade[i] = (int32_t)(q / (n_iter + 1));
                 iter[i] = (int32_t)(q % (n_iter + 1)) - 1;
                 row[i + 1] = row[i] + n[i0 + i];
-                goff[i] = (int64_t)i * G;
-                yoff[i] = row[i] * ld;
                 doff[i] = d_off[i0 + i] - d_off[i0];
-                std::iota(gidx.begin() + (size_t)i * G, gidx.begin() + (size_t)(i + 1) * G, 0);
-                const int64_t nt = (n[i0 + i] + 127) / 128;
-                t128 += nt * (nt + 1) / 2;
             }
-            goff[ns] = (int64_t)ns * G;
-            yoff[ns] = row[ns] * ld;
             const int64_t rows = row[ns];
             if (rows > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "random_trees: sub-wave too large");
             ids.resize(rows);
             std::iota(ids.begin(), ids.end(), 0);
-            const int wm = t128 >= 2 * (int64_t)num_cus() ? 4 : 2, DT = 32 * wm;
-            toff[0] = 0;
-            for (int i = 0; i < ns; ++i) {
-                const int64_t nt = (n[i0 + i] + DT - 1) / DT;
-                toff[i + 1] = toff[i] + nt * (nt + 1) / 2;
-            }
+            const int dt = exact_dist_plan(n.data() + i0, ns, toff);
             if (toff[ns] > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "random_trees: sub-wave too large");
-            DevBuf d_m, d_z, d_gidx, d_goff, d_ids, d_row, d_yoff, d_ld, d_shift, d_norm, d_toff, d_n, d_doff;
+            DevBuf d_m, d_z, d_ids, d_row, d_toff, d_n, d_doff;
             if ((rc = d_m.alloc((size_t)rows * ld * sizeof(double))) || (rc = d_z.alloc((size_t)rows * G * sizeof(double))))
                 return rc;
             if ((rc = rt_stage(expr, (int32_t)G, cl, seed, window, clade, iter, row, ICNV_RT_PERMUTE | ICNV_RT_SMOOTH | ICNV_RT_CENTER,
                                d_m.as<double>(), ld, d_z.as<double>(), s)))
                 return rc;
-            if ((rc = upload(d_gidx, gidx.data(), gidx.size(), s)) || (rc = upload(d_goff, goff.data(), goff.size(), s)) ||
-                (rc = upload(d_ids, ids.data(), ids.size(), s)) || (rc = upload(d_row, row.data(), row.size(), s)) ||
-                (rc = upload(d_yoff, yoff.data(), yoff.size(), s)) || (rc = upload(d_ld, ldv.data(), ldv.size(), s)) ||
+            if ((rc = upload(d_ids, ids.data(), ids.size(), s)) || (rc = upload(d_row, row.data(), row.size(), s)) ||
                 (rc = upload(d_toff, toff.data(), toff.size(), s)) || (rc = upload(d_n, n.data() + i0, (size_t)ns, s)) ||
-                (rc = upload(d_doff, doff.data(), doff.size(), s)) || (rc = d_shift.alloc((size_t)ns * G * sizeof(double))) ||
-                (rc = d_norm.alloc((size_t)rows * sizeof(double))))
+                (rc = upload(d_doff, doff.data(), doff.size(), s)))
                 return rc;
-            KnnArgs ka{};   // the permuted rows are dead after the smoothing: the compact cells reuse their buffer
-            ka.x = d_z.as<double>(); ka.G = (int32_t)G;
-            ka.gene_idx = d_gidx.as<int32_t>(); ka.gene_off = d_goff.as<int64_t>();
-            ka.cell_idx = d_ids.as<int32_t>(); ka.cell_off = d_row.as<int64_t>();
-            ka.n_prob = ns; ka.total_genes = goff[ns]; ka.total_rows = rows;
-            ka.shift = d_shift.as<double>(); ka.Y = d_m.as<double>(); ka.y_off = d_yoff.as<int64_t>(); ka.ld = d_ld.as<int32_t>();
-            ka.norm = d_norm.as<double>();
-            if ((rc = launch_knn_prepare(ka, s))) return rc;
-            HclustGram g;
-            g.n_prob = ns; g.tile_off = d_toff.as<int64_t>(); g.n = d_n.as<int32_t>();
-            g.Y = ka.Y; g.y_off = ka.y_off; g.ld = ka.ld; g.norm = ka.norm; g.c_off = d_row.as<int64_t>();
-            g.d_off = d_doff.as<int64_t>(); g.D = d_D.as<double>() + d_off[i0];
-            if ((rc = launch_hclust_gram(g, toff[ns], wm, s))) return rc;
+            DistArgs da{};   // the staged cells: row r of the sub-wave at d_z + r G, every gene in order
+            da.x = d_z.as<double>(); da.ldx = G; da.G = (int32_t)G;
+            da.cell_idx = d_ids.as<int32_t>(); da.cell_off = d_row.as<int64_t>(); da.n = d_n.as<int32_t>();
+            da.n_prob = ns; da.tile_off = d_toff.as<int64_t>(); da.d_off = d_doff.as<int64_t>(); da.D = d_D.as<double>() + d_off[i0];
+            if ((rc = launch_exact_dist(da, dt, toff[ns], s))) return rc;
             ICNV_HIP(hipStreamSynchronize(s));   // (the sub-wave's buffers go back to the pool here)
             i0 = i1;
         }

@@ -1,114 +1,144 @@
-// Euclidean distances between the cells of one group: parallelDist(t(expr[, cells])) as the reference calls
-// it before hclust (R/inferCNV_tumor_subclusters.R:191, R/inferCNV_ops.R:1930, 3242) -- the
-// one dense contraction next to the hot path, and the only kernel of this library that belongs on the matrix cores.
+// Euclidean distances between the cells of a group: dist / parallelDist(t(expr[genes, cells])) as the reference calls it
+// before hclust (R/inferCNV_tumor_subclusters.R:191, 582, 609, R/inferCNV_ops.R:1930, 3242).  Used by K7
+// (icnv_cell_distances_dev), by K9's fused hclust (icnv_hclust_cells_dev) and by K10's random trees, which all hold the
+// result bit for bit to R's sequential dist:
 //
-//   y_i = x_i - mean over the group's cells        (per gene; distances are translation invariant, and centring
-//                                                    removes the cancellation of the Gram formulation)
-//   S   = Y Y^T   (n x n Gram matrix)               v_mfma_f64_16x16x4_f64, 64 x 64 output tile per workgroup,
-//                                                    upper-triangular tiles only, mirrored on the way out
-//   D_ij = sqrt(max(0, S_ii + S_jj - 2 S_ij)),  D_ii = 0
+//   d2_ij = sum over the listed genes g, in list order, of fl(fl(x_gi - x_gj)^2)     raw values, no centring, no FMA
+//   D_ij  = sqrt(d2_ij) (correctly rounded),  D_ii = 0
 //
-// fp64 throughout (the reference's distances are doubles and feed a hierarchical clustering whose merge order
-// depends on them); the fp64 MFMA rate equals the fp64 vector rate on gfx950 (78.6 TFLOP/s), the matrix cores'
-// gain here is the operand reuse: one 8-byte LDS read per lane feeds 2 x 16 x 16 x 4 multiply-adds.
+// A Gram formulation (|y_i|^2 + |y_j|^2 - 2 y_i.y_j) cancels: two identical cells come out a few ulps of |y|^2 apart and
+// near-identical ones with relative errors of order 1, which reorders the hierarchical clustering's tied merges.  Here a
+// pair-gene is three fp64 VALU operations (sub, mul, add), in the order above.  This file is compiled with
+// -ffp-contract=off (Makefile): the mul and add must not become an FMA.
+//
+// One workgroup = one DT x DT upper-triangular tile of one problem (tile -> problem through tile_off, so a batch of problems
+// is one launch).  Its 256 threads form a 16 x 16 grid, each owning an R x R register block of pairs; operand chunks of
+// KC genes of the tile's DT row cells and DT column cells are staged gene-major through LDS.
 #include "icnv_internal.h"
-#include "gram_mfma.h"
 
 namespace icnv {
 
 namespace {
 
-using gram::dbl4_t;
-using gram::LDR;
+constexpr int KC = 16;   // genes per LDS stage
 
-// One workgroup = 4 wavefronts = 2 x 2 sub-tiles; a wavefront holds WM x WM MFMA accumulators (16 x 16 each), so the
-// workgroup's output tile is DT = 32 WM cells square: WM = 2 for small groups (enough tiles to fill 256 CUs),
-// WM = 4 for large ones (each 8-byte LDS operand read then feeds four matrix instructions instead of two).
-// The staging and the MFMA loop are gram::tile_product (gram_mfma.h), shared with the kNN screen (knn_kernels.hip).
-template <int WM>
-__global__ void __launch_bounds__(256, (WM == 4 ? 2 : 4)) gram_tiles_kernel(const double *__restrict__ x, int G, const int32_t *__restrict__ idx,
-                                                         int n, const double *__restrict__ mean, double *__restrict__ S) {
-    constexpr int DT = 32 * WM;
-    constexpr int RPT = DT / 64;          // rows staged per thread and tile
-    extern __shared__ __attribute__((aligned(16))) double smem_d[];
-    // upper-triangular tile pair (bi <= bj) of this workgroup
+__device__ __forceinline__ int find_tile_problem(const int64_t *__restrict__ off, int n, int64_t v) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= v) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+template <int R>
+__global__ void __launch_bounds__(256, (R == 8 ? 2 : 4)) exact_dist_kernel(DistArgs a) {
+    constexpr int DT = 16 * R;
+    constexpr int LD = DT + 2;          // LDS stride of one gene's row (doubles): even, so the R-wide reads stay 16-byte aligned
+    constexpr int PER = DT * KC / 256;  // values staged per thread and operand
+    __shared__ __attribute__((aligned(16))) double As[KC * LD], Bs[KC * LD];
+    __shared__ int64_t base_a[DT], base_b[DT];
+
+    const int p = find_tile_problem(a.tile_off, a.n_prob, blockIdx.x);
+    int64_t rem = blockIdx.x - a.tile_off[p];
+    const int n = a.n[p];
     const int nt = (n + DT - 1) / DT;
-    int bi = 0, rem = blockIdx.x;
+    int bi = 0;
     while (rem >= nt - bi) { rem -= nt - bi; ++bi; }
-    const int bj = bi + rem;
+    const int bj = bi + (int)rem;
+    const int32_t *gidx = a.gene_idx ? a.gene_idx + a.gene_off[p] : nullptr;
+    const int G = a.gene_idx ? (int)(a.gene_off[p + 1] - a.gene_off[p]) : a.G;
+    const int32_t *cidx = a.cell_idx + a.cell_off[p];
 
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int wr = w >> 1, wc = w & 1;
-    const int lrow = t >> 2;
-    const double *pa[RPT], *pb[RPT];
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) {
-        const int ra = bi * DT + lrow + 64 * r, rb = bj * DT + lrow + 64 * r;
-        pa[r] = ra < n ? x + (int64_t)idx[ra] * G : nullptr;
-        pb[r] = rb < n ? x + (int64_t)idx[rb] * G : nullptr;
+    const int t = threadIdx.x;
+    for (int r = t; r < DT; r += 256) {   // each row's first value; -1: a row past the problem's end
+        const int ra = bi * DT + r, rb = bj * DT + r;
+        base_a[r] = ra < n ? (int64_t)cidx[ra] * a.ldx : -1;
+        base_b[r] = rb < n ? (int64_t)cidx[rb] * a.ldx : -1;
     }
-    const bool even = (G & 1) == 0;   // 16-byte loads: every row starts at an even element and g is even
-    dbl4_t acc[WM][WM];
-    gram::tile_product<WM, true>(pa, pb, G, even, mean, smem_d, acc);
-    // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg
+    // staging: thread t moves gene k = t % KC of rows t / KC + 16 q -- consecutive lanes read consecutive genes of one cell
+    const int sk = t % KC, sr = t / KC;
+    const int ty = t >> 4, tx = t & 15;
+    double s[R][R];
 #pragma unroll
-    for (int a = 0; a < WM; ++a)
+    for (int i = 0; i < R; ++i)
 #pragma unroll
-        for (int b = 0; b < WM; ++b)
+        for (int j = 0; j < R; ++j) s[i][j] = 0.0;
+
+    for (int k0 = 0; k0 < G; k0 += KC) {
+        __syncthreads();   // the previous stage is consumed (first pass: the row bases are written)
+        const int g = k0 + sk;
+        const int64_t gene = g < G ? (gidx ? gidx[g] : g) : -1;
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int row = bi * DT + wr * 16 * WM + a * 16 + (lane >> 4) + 4 * reg;
-                const int col = bj * DT + wc * 16 * WM + b * 16 + (lane & 15);
-                if (row < n && col < n) {
-                    const double v = acc[a][b][reg];
-                    S[(int64_t)row * n + col] = v;
-                    if (bi != bj) S[(int64_t)col * n + row] = v;
-                }
+        for (int q = 0; q < PER; ++q) {
+            const int r = sr + 16 * q;
+            const int64_t ba = base_a[r], bb = base_b[r];
+            // a gene past the end reads 0 in both operands: fl(0 - 0)^2 = +0 leaves every sum unchanged
+            As[sk * LD + r] = (gene >= 0 && ba >= 0) ? a.x[ba + gene] : 0.0;
+            Bs[sk * LD + r] = (gene >= 0 && bb >= 0) ? a.x[bb + gene] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int k = 0; k < KC; ++k) {
+            double av[R], bv[R];
+#pragma unroll
+            for (int i = 0; i < R; i += 2) {
+                const double2 va = *reinterpret_cast<const double2 *>(&As[k * LD + ty * R + i]);
+                const double2 vb = *reinterpret_cast<const double2 *>(&Bs[k * LD + tx * R + i]);
+                av[i] = va.x; av[i + 1] = va.y;
+                bv[i] = vb.x; bv[i + 1] = vb.y;
             }
-}
-
-__global__ void gram_diag_kernel(const double *__restrict__ S, int n, double *__restrict__ diag) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) diag[i] = S[(int64_t)i * n + i];
-}
-
-// in place: S -> D
-__global__ void gram_to_dist_kernel(double *__restrict__ S, int n, const double *__restrict__ diag) {
-    const int64_t total = (int64_t)n * n;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const int i = (int)(p / n), j = (int)(p - (int64_t)i * n);
-        const double d2 = diag[i] + diag[j] - 2.0 * S[p];
-        S[p] = (i == j) ? 0.0 : sqrt(fmax(d2, 0.0));
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    const double d = __dsub_rn(av[i], bv[j]);
+                    s[i][j] = __dadd_rn(s[i][j], __dmul_rn(d, d));
+                }
+        }
     }
+
+    // one value per pair, mirrored: fl(a - b)^2 == fl(b - a)^2, so the matrix is exactly symmetric either way
+    double *Dp = a.D + a.d_off[p];
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const int row = bi * DT + ty * R + i, col = bj * DT + tx * R + j;
+            if (row < n && col < n && row <= col) {
+                const double v = row == col ? 0.0 : __dsqrt_rn(s[i][j]);
+                Dp[(int64_t)row * n + col] = v;
+                Dp[(int64_t)col * n + row] = v;
+            }
+        }
 }
 
 }  // namespace
 
-int launch_cell_distances(const double *x, int32_t G, const int32_t *idx_dev, int32_t n, const double *mean_dev,
-                          double *diag_dev, double *out, hipStream_t stream) {
-    if (n <= 0) return ICNV_OK;
-    // 128-cell tiles when they still fill the chip twice over, 64-cell tiles otherwise
-    const int64_t nt128 = (n + 127) / 128;
-    const bool big = nt128 * (nt128 + 1) / 2 >= 2 * (int64_t)num_cus();
-    const int DT = big ? 128 : 64;
-    const int64_t nt = (n + DT - 1) / DT;
-    const int64_t tiles = nt * (nt + 1) / 2;
-    if (tiles > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "too many cells for one distance matrix");
-    {
-        KernelTimer kt("cell_distances_gram", stream);
-        const size_t lds = (size_t)2 * DT * LDR * sizeof(double);
-        if (big) {
-            static DeviceOnce once;
-            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(gram_tiles_kernel<4>), 80 * 1024, once)) return rc;
-            hipLaunchKernelGGL(gram_tiles_kernel<4>, dim3((unsigned)tiles), dim3(256), lds, stream, x, G, idx_dev, n, mean_dev, out);
-        } else {
-            hipLaunchKernelGGL(gram_tiles_kernel<2>, dim3((unsigned)tiles), dim3(256), lds, stream, x, G, idx_dev, n, mean_dev, out);
-        }
+int exact_dist_plan(const int32_t *n, int32_t n_prob, std::vector<int64_t> &tile_off) {
+    // 128-cell tiles (8 x 8 pairs per thread) when they still fill the chip twice over, 64-cell tiles (4 x 4) otherwise
+    int64_t t128 = 0;
+    for (int32_t p = 0; p < n_prob; ++p) {
+        const int64_t nt = (n[p] + 127) / 128;
+        t128 += nt * (nt + 1) / 2;
     }
-    hipLaunchKernelGGL(gram_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, out, n, diag_dev);
-    int64_t blocks = ((int64_t)n * n + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(gram_to_dist_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, out, n, diag_dev);
+    const int DT = t128 >= 2 * (int64_t)num_cus() ? 128 : 64;
+    tile_off.assign((size_t)n_prob + 1, 0);
+    for (int32_t p = 0; p < n_prob; ++p) {
+        const int64_t nt = (n[p] + DT - 1) / DT;
+        tile_off[p + 1] = tile_off[p] + nt * (nt + 1) / 2;
+    }
+    return DT;
+}
+
+int launch_exact_dist(const DistArgs &a, int dt, int64_t n_tiles, hipStream_t stream) {
+    if (n_tiles <= 0) return ICNV_OK;
+    if (n_tiles > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "too many cells for one distance launch");
+    KernelTimer kt("exact_dist", stream);
+    if (dt == 128)
+        hipLaunchKernelGGL(exact_dist_kernel<8>, dim3((unsigned)n_tiles), dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL(exact_dist_kernel<4>, dim3((unsigned)n_tiles), dim3(256), 0, stream, a);
     ICNV_HIP(hipGetLastError());
     return ICNV_OK;
 }

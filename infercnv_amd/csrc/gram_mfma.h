@@ -1,7 +1,6 @@
-// The fp64 matrix-core tile product shared by the cell-cell distances (distance_kernels.hip, K7) and the exact kNN's
-// screen (knn_kernels.hip, K8): one workgroup of 4 wavefronts accumulates the DT x DT block  A B^T  of two row sets,
-// DT = 32 WM, with v_mfma_f64_16x16x4_f64.  A row is given by a pointer to its first element (nullptr: a row past the
-// end, read as zeros after centring); the rows' elements 0 .. G-1 are contracted.
+// The fp64 matrix-core tile product of the exact kNN's screen (knn_kernels.hip, K8): one workgroup of 4 wavefronts
+// accumulates the DT x DT block  A B^T  of two row sets, DT = 32 WM, with v_mfma_f64_16x16x4_f64.  A row is given by a
+// pointer to its first element (nullptr: a row past the end, read as zeros); the rows' elements 0 .. G-1 are contracted.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,13 +15,12 @@ constexpr int LDR = KC + 2;   // LDS row stride in doubles: (4 row + 2 k) dwords
 constexpr size_t lds_bytes(int WM) { return (size_t)2 * 32 * WM * LDR * sizeof(double); }
 
 // One workgroup = 4 wavefronts = 2 x 2 sub-tiles; a wavefront holds WM x WM MFMA accumulators (16 x 16 each).
-// CENTRE: subtract mean[g] from every element on the way in (K7 centres while it stages); otherwise the rows are read as
-// they are.  even: every row starts at an even element and G is even (16-byte loads).
+// Every row starts at an even element and G is even (16-byte loads).
 // C/D layout of the result: acc[a][b][reg] is row wr * 16 WM + 16 a + (lane >> 4) + 4 reg, column wc * 16 WM + 16 b + (lane & 15)
 // of the tile, with w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1.
-template <int WM, bool CENTRE>
-__device__ __forceinline__ void tile_product(const double *const (&pa)[WM / 2], const double *const (&pb)[WM / 2], int G, bool even,
-                                             const double *__restrict__ mean, double *smem_d, dbl4_t (&acc)[WM][WM]) {
+template <int WM>
+__device__ __forceinline__ void tile_product(const double *const (&pa)[WM / 2], const double *const (&pb)[WM / 2], int G,
+                                             double *smem_d, dbl4_t (&acc)[WM][WM]) {
     constexpr int DT = 32 * WM;
     constexpr int RPT = DT / 64;          // rows staged per thread and tile
     double *As = smem_d;
@@ -42,25 +40,14 @@ __device__ __forceinline__ void tile_product(const double *const (&pa)[WM / 2], 
     auto fetch = [&](int k0) {
 #pragma unroll
         for (int r = 0; r < RPT; ++r) {
-            if (even) {
 #pragma unroll
-                for (int j = 0; j < 8; j += 2) {
-                    const int g = k0 + lseg + j;
-                    const bool in = g < G;
-                    const double2 m = (CENTRE && in) ? *reinterpret_cast<const double2 *>(mean + g) : make_double2(0.0, 0.0);
-                    const double2 va = (pa[r] && in) ? *reinterpret_cast<const double2 *>(pa[r] + g) : m;
-                    const double2 vb = (pb[r] && in) ? *reinterpret_cast<const double2 *>(pb[r] + g) : m;
-                    ra_v[r][j] = va.x - m.x; ra_v[r][j + 1] = va.y - m.y;
-                    rb_v[r][j] = vb.x - m.x; rb_v[r][j + 1] = vb.y - m.y;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int g = k0 + lseg + j;
-                    const double m = (CENTRE && g < G) ? mean[g] : 0.0;
-                    ra_v[r][j] = (pa[r] && g < G) ? pa[r][g] - m : 0.0;
-                    rb_v[r][j] = (pb[r] && g < G) ? pb[r][g] - m : 0.0;
-                }
+            for (int j = 0; j < 8; j += 2) {
+                const int g = k0 + lseg + j;
+                const bool in = g < G;
+                const double2 va = (pa[r] && in) ? *reinterpret_cast<const double2 *>(pa[r] + g) : make_double2(0.0, 0.0);
+                const double2 vb = (pb[r] && in) ? *reinterpret_cast<const double2 *>(pb[r] + g) : make_double2(0.0, 0.0);
+                ra_v[r][j] = va.x; ra_v[r][j + 1] = va.y;
+                rb_v[r][j] = vb.x; rb_v[r][j + 1] = vb.y;
             }
         }
     };

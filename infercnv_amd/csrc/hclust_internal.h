@@ -29,21 +29,7 @@ struct HclustArgs {           // one launch; every pointer is device memory
     int32_t method;           // ICNV_HCLUST_*
 };
 
-struct HclustGram {           // fused distances: every problem's upper-triangular DT x DT tiles in one launch
-    int32_t n_prob;
-    const int64_t *tile_off;  // [n_prob + 1]
-    const int32_t *n;         // per problem: cells
-    const double *Y;          // K8's centred compact cells (knn prepare): problem p at y_off[p], rows of ld[p] doubles
-    const int64_t *y_off;
-    const int32_t *ld;
-    const double *norm;       // ||y_i||^2 per packed cell
-    const int64_t *c_off;     // per problem: first packed cell
-    const int64_t *d_off;
-    double *D;
-};
-
 int launch_hclust_prep(double *D, int64_t total, bool square, uint32_t *bad, hipStream_t s);
-int launch_hclust_gram(const HclustGram &g, int64_t n_tiles, int wm, hipStream_t s);
 int launch_hclust_lds(const HclustArgs &a, int max_n, hipStream_t s);
 int launch_hclust_hbm(const HclustArgs &a, int max_n, hipStream_t s);
 

@@ -3,8 +3,7 @@
 // section 4 K9.  The nearest-neighbour chain is sequential and each of its steps is O(n) parallel work, less than a grid
 // barrier costs, so one problem runs in ONE persistent workgroup and a batch fills the CUs with problems:
 //
-//   hclust_gram_kernel  fused entry point: D_ij = sqrt(max(0, |y_i|^2 + |y_j|^2 - 2 y_i.y_j)) of every problem of the batch
-//                       on the matrix cores (gram::tile_product, K7/K8), straight into the workspace
+//   the fused entry point's distances (R's sequential dist, bit for bit) come from distance_kernels.hip
 //   hclust_prep_kernel  every problem's matrix: flags a non-finite distance, squares it for ward.D2 (d * d)
 //   hclust_lds_kernel   n <= 200: one workgroup per problem, the condensed matrix in LDS
 //   hclust_hbm_kernel   larger n: one workgroup per problem, the full square matrix in HBM (rows contiguous, the updated
@@ -14,71 +13,11 @@
 // The raw merges (chain order) go back to api.hip, which sorts and labels them as R does.
 // This file is compiled with -ffp-contract=off (Makefile): the Lance-Williams updates must not become FMAs.
 #include "icnv_internal.h"
-#include "gram_mfma.h"
 #include "hclust_internal.h"
 
 namespace icnv {
 
 namespace {
-
-using gram::dbl4_t;
-
-__device__ __forceinline__ int find_segment(const int64_t *__restrict__ off, int n, int64_t v) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= v) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// ---------------------------------------------------------------- fused distances
-template <int WM>
-__global__ void __launch_bounds__(256, (WM == 4 ? 2 : 4)) hclust_gram_kernel(HclustGram g) {
-    constexpr int DT = 32 * WM;
-    constexpr int RPT = DT / 64;
-    extern __shared__ __attribute__((aligned(16))) double smem_d[];
-    const int p = find_segment(g.tile_off, g.n_prob, blockIdx.x);
-    int64_t rem = blockIdx.x - g.tile_off[p];
-    const int n = g.n[p];
-    const int nt = (n + DT - 1) / DT;
-    int bi = 0;
-    while (rem >= nt - bi) { rem -= nt - bi; ++bi; }
-    const int bj = bi + (int)rem;
-    const int ld = g.ld[p];
-    const double *Yp = g.Y + g.y_off[p];
-
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int wr = w >> 1, wc = w & 1;
-    const int lrow = t >> 2;
-    const double *pa[RPT], *pb[RPT];
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) {
-        const int ra = bi * DT + lrow + 64 * r, rb = bj * DT + lrow + 64 * r;
-        pa[r] = ra < n ? Yp + (int64_t)ra * ld : nullptr;
-        pb[r] = rb < n ? Yp + (int64_t)rb * ld : nullptr;
-    }
-    dbl4_t acc[WM][WM];
-    gram::tile_product<WM, false>(pa, pb, ld, true, nullptr, smem_d, acc);
-
-    const double *nrm = g.norm + g.c_off[p];
-    double *Dp = g.D + g.d_off[p];
-#pragma unroll
-    for (int a = 0; a < WM; ++a)
-#pragma unroll
-        for (int b = 0; b < WM; ++b)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int row = bi * DT + wr * 16 * WM + a * 16 + (lane >> 4) + 4 * reg;
-                const int col = bj * DT + wc * 16 * WM + b * 16 + (lane & 15);
-                // one value per pair, mirrored: the matrix is exactly symmetric, so both chain paths read the same D_ij
-                if (row < n && col < n && row <= col) {
-                    const double v = row == col ? 0.0 : sqrt(fmax(nrm[row] + nrm[col] - 2.0 * acc[a][b][reg], 0.0));
-                    Dp[(int64_t)row * n + col] = v;
-                    Dp[(int64_t)col * n + row] = v;
-                }
-            }
-}
 
 __global__ void hclust_prep_kernel(double *__restrict__ D, int64_t total, int square, uint32_t *__restrict__ bad) {
     uint32_t nonfinite = 0;
@@ -274,20 +213,6 @@ __global__ void __launch_bounds__(HBM_NT) hclust_hbm_kernel(HclustArgs a) {
 }
 
 }  // namespace
-
-int launch_hclust_gram(const HclustGram &g, int64_t n_tiles, int wm, hipStream_t s) {
-    if (n_tiles <= 0) return ICNV_OK;
-    KernelTimer kt("hclust_gram", s);
-    if (wm == 4) {
-        static DeviceOnce once;
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(hclust_gram_kernel<4>), (int)gram::lds_bytes(4), once)) return rc;
-        hipLaunchKernelGGL(hclust_gram_kernel<4>, dim3((unsigned)n_tiles), dim3(256), gram::lds_bytes(4), s, g);
-    } else {
-        hipLaunchKernelGGL(hclust_gram_kernel<2>, dim3((unsigned)n_tiles), dim3(256), gram::lds_bytes(2), s, g);
-    }
-    ICNV_HIP(hipGetLastError());
-    return ICNV_OK;
-}
 
 int launch_hclust_prep(double *D, int64_t total, bool square, uint32_t *bad, hipStream_t s) {
     if (total <= 0) return ICNV_OK;

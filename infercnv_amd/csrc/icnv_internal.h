@@ -271,9 +271,24 @@ int launch_broadcast_states_keep(const uint8_t *grp_states, int32_t G, int64_t C
                                  uint8_t *states, hipStream_t stream);
 int launch_states_to_proxy(const uint8_t *states, double *out, int64_t n, int32_t K, hipStream_t stream);
 
-// ---- cell-cell distances (distance_kernels.hip) ----
-int launch_cell_distances(const double *x, int32_t G, const int32_t *idx_dev, int32_t n, const double *mean_dev,
-                          double *diag_dev, double *out, hipStream_t stream);
+// ---- cell-cell distances (distance_kernels.hip): R's sequential dist, bit for bit (K7, K9, K10) ----
+struct DistArgs {             // one launch over the upper-triangular tiles of a batch of problems; device pointers
+    const double *x;          // cell c's values at x + c * ldx (raw: never centred)
+    int64_t ldx;
+    int32_t G;                // genes of every problem when gene_idx is null (0 .. G-1)
+    const int32_t *gene_idx;  // problem p's genes, in order, at gene_idx[gene_off[p] .. gene_off[p + 1]); or null
+    const int64_t *gene_off;
+    const int32_t *cell_idx;  // problem p's cells at cell_idx[cell_off[p] .. cell_off[p + 1])
+    const int64_t *cell_off;
+    const int32_t *n;         // per problem: cells
+    int32_t n_prob;
+    const int64_t *tile_off;  // [n_prob + 1]: problem p's tiles are blocks tile_off[p] .. tile_off[p + 1] - 1 (exact_dist_plan)
+    const int64_t *d_off;     // problem p's full symmetric n x n matrix at D + d_off[p]
+    double *D;
+};
+// fills tile_off [n_prob + 1] from the host cell counts and returns the tile edge for launch_exact_dist
+int exact_dist_plan(const int32_t *n, int32_t n_prob, std::vector<int64_t> &tile_off);
+int launch_exact_dist(const DistArgs &a, int dt, int64_t n_tiles, hipStream_t stream);
 
 // ---- median filter --------------------------------------------------------
 // The default window (9 x 9) runs on tile descriptors built by the host (api.hip): kernel 1's tiles (56 genes x 32 cells of a

@@ -4,7 +4,7 @@
 //
 //   knn_mean_kernel     per (problem, gene) shift: the mean of the gene over the problem's first <= 256 cells
 //   knn_gather_kernel   Y_p = x[genes_p, cells_p] - shift, compact (one row of ld_p doubles per cell), and ||y_i||^2
-//   knn_screen_kernel   d~2 = ||y_i||^2 + ||y_j||^2 - 2 y_i.y_j on the matrix cores (gram::tile_product, shared with K7),
+//   knn_screen_kernel   d~2 = ||y_i||^2 + ||y_j||^2 - 2 y_i.y_j on the matrix cores (gram::tile_product),
 //                       stored as the upper 32 bits of the order keys of d~2 + e_ij and d~2 - e_ij (e_ij: DESIGN K8)
 //   knn_select_kernel   per query row: b = the k-th smallest upper key (radix select), candidates = {j : lower key <= b}
 //   knn_refine_kernel   per query row: d2 of every candidate exactly as the contract defines it, ranked by (d2, j)
@@ -110,7 +110,7 @@ __global__ void __launch_bounds__(256, (WM == 4 ? 2 : 4)) knn_screen_kernel(KnnA
         pb[r] = rb < np ? Yp + (int64_t)rb * ld : nullptr;
     }
     dbl4_t acc[WM][WM];
-    gram::tile_product<WM, false>(pa, pb, ld, true, nullptr, smem_d, acc);
+    gram::tile_product<WM>(pa, pb, ld, smem_d, acc);
 
     const int Gp = (int)(a.gene_off[p + 1] - a.gene_off[p]);
     const double *nrm = a.norm + a.cell_off[p];

@@ -413,7 +413,7 @@ def hclust(dist, method="ward.D2"):
 
 def hclust_cells(x, problems, method="ward.D2"):
     """hclust(parallelDist(t(expr.data[genes, cells])), method) for a batch of problems in one call (icnv_hclust_cells_dev,
-    DESIGN K9): the distances on the matrix cores, the clustering in LDS or HBM, nothing but the result leaves the device.
+    DESIGN K9): the distances bit-equal to R's sequential dist, the clustering in LDS or HBM, nothing but the result leaves the device.
     problems: list of (genes, cells) 0-based index vectors, at least two cells each.  Returns a list of (merge, height,
     order) CUDA tensors per problem, as `hclust` returns them."""
     L = _lib.load()

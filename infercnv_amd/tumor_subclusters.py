@@ -1,14 +1,15 @@
 """Host-side mirror of the distance step of the reference's subclustering
 (R/inferCNV_tumor_subclusters.R:180-194: `hclust(parallelDist(t(tumor_expr_data)))`): the Euclidean distances
-between the cells of one tumor group, computed on the GPU (icnv_cell_distances_dev, fp64 matrix cores).  The
-clustering itself (hclust / Leiden) stays in R -- SURVEY.md 8f #4 scopes only the dense contraction.
+between the cells of one tumor group, computed on the GPU (icnv_cell_distances_dev) bit-equal to R's sequential dist:
+per pair the fp64 sum over the genes in order of the rounded squares of the rounded differences of the raw values, then
+sqrt.  Identical cells (step 22 makes many) are at distance exactly 0, so tied merges resolve as R's do.
 
 The Leiden route's neighbour search (R/inferCNV_tumor_subclusters.R:646-741, RANN::nn2) is the exact kNN of
 icnv_knn_dev (DESIGN K8): `nn2`, `snn_adjacency`, `knn_per_chr`, with the reference-based gene filter of :45-71.
 
 The hierarchical clustering itself, `hclust(parallelDist(t(x)), method = hclust_method)` (:191, 582, 609 and the other
-call sites of DESIGN K9), runs on the GPU too: `hclust` returns R's hclust object without the distance matrix ever leaving
-the device.
+call sites of DESIGN K9), runs on the GPU too, on the same exact distances: `hclust` returns R's hclust object without the
+distance matrix ever leaving the device.
 
 The random-trees subclustering (R/inferCNV_tumor_subclusters.random_smoothed_trees.R, DESIGN K10) runs its permutation
 statistic on the GPU (icnv_random_trees_dev), one call per recursion level: `define_signif_tumor_subclusters_via_random_smooothed_trees`,

@@ -28,7 +28,7 @@ import torch  # noqa: E402
 
 from infercnv_amd import device  # noqa: E402
 
-KERNELS = ("rt_check", "rt_permute", "rt_smooth", "chain_large_center", "knn_gather", "hclust_gram", "hclust_prep",
+KERNELS = ("rt_check", "rt_permute", "rt_smooth", "chain_large_center", "exact_dist", "hclust_prep",
            "hclust_lds", "hclust_hbm", "rt_max_height")
 G, ITERS, WINDOW = 10000, 100, 101
 
@@ -56,7 +56,7 @@ def call(x, clades, split=False):
         sp = {k: round(device.timing_get(k)[0], 3) for k in KERNELS}
         out["split_ms"] = sp
         out["stage_ms"] = {"permute": sp["rt_check"] + sp["rt_permute"], "smooth": sp["rt_smooth"],
-                           "center": sp["chain_large_center"], "gram": sp["knn_gather"] + sp["hclust_gram"],
+                           "center": sp["chain_large_center"], "dist": sp["exact_dist"],
                            "chain": sp["hclust_prep"] + sp["hclust_lds"] + sp["hclust_hbm"] + sp["rt_max_height"]}
         out["stage_ms"] = {k: round(v, 2) for k, v in out["stage_ms"].items()}
         pre = out["stage_ms"]["permute"] + out["stage_ms"]["smooth"] + out["stage_ms"]["center"]

@@ -89,6 +89,7 @@ def test_tumor_subclusters_hclust_record(dev, golden_dir):
     want = hr.hclust(hr.seq_dist(x[np.ix_(genes, cells)].T), "ward.D2")
     assert np.array_equal(hc.merge, want[0]) and np.array_equal(hc.order, want[2])
     np.testing.assert_allclose(hc.height, want[1], rtol=1e-12)
+    assert np.array_equal(hc.height.view(np.int64), want[1].view(np.int64))
     assert hc.method == "ward.D2" and hc.dist_method == "euclidean"
     assert hc.labels.tolist() == [f"cell_{c + 1}" for c in cells]
 
@@ -159,7 +160,7 @@ def test_hclust_cells_batch_equals_per_problem_calls(dev):
 
 
 def test_hclust_cells_matches_restatement_topology(dev):
-    """The fused distances (matrix-core Gram form) agree with R's sequential dist closely enough that the tree is R's."""
+    """The fused distances are R's sequential dist bit for bit, so the tree is the restatement's bit for bit."""
     rng = np.random.default_rng(4)
     x = rng.standard_normal((300, 500))
     problems = [(np.arange(300), rng.choice(500, size=n, replace=False)) for n in (5, 60, 199, 350)]
@@ -168,6 +169,7 @@ def test_hclust_cells_matches_restatement_topology(dev):
         want = hr.hclust(hr.seq_dist(x[np.ix_(genes, cells)].T), "average")
         assert np.array_equal(m, want[0]) and np.array_equal(o, want[2])
         np.testing.assert_allclose(h, want[1], rtol=1e-12)
+        assert np.array_equal(h.view(np.int64), want[1].view(np.int64))
 
 
 # ------------------------------------------------------------------ 6. SciPy at n = 8 000

@@ -21,6 +21,7 @@ torch = pytest.importorskip("torch")
 import oracle_c as oc  # noqa: E402
 import oracle_np as onp  # noqa: E402
 from parity_util import check_denoise_flips  # noqa: E402
+import hclust_restate as hr  # noqa: E402
 
 RTOL_NORTH_STAR = 1e-5
 
@@ -1369,8 +1370,8 @@ def test_get_spike_dists_block_statistics(dev):
 # ------------------------------------------------------------------ cell-cell distances
 @pytest.mark.parametrize("G,C,n", [(2000, 300, 150), (2001, 90, 70), (512, 64, 64), (777, 200, 129), (64, 5, 1), (33, 40, 2)])
 def test_cell_distances_vs_oracle(dev, G, C, n):
-    """parallelDist(t(expr[, cells])) (R/inferCNV_tumor_subclusters.R:191): the fp64 MFMA Gram formulation against
-    direct sums of squared differences; relative 1e-12 (tile edges, odd G, non-multiples of the 64-cell tile)."""
+    """parallelDist(t(expr[, cells])) (R/inferCNV_tumor_subclusters.R:191): bit-equal to R's sequential sums of squared
+    differences (tile edges, odd G, non-multiples of the 64-cell tile)."""
     rng = np.random.default_rng(G + n)
     x = rng.normal(1.0, 0.3, size=(G, C)) + rng.normal(0.0, 2.0, size=(G, 1))     # large per-gene offsets: centring matters
     cells = rng.permutation(C)[:n].astype(np.int32)
@@ -1382,11 +1383,14 @@ def test_cell_distances_vs_oracle(dev, G, C, n):
     # translation invariance per gene (the kernel centres internally): exact same structure, tiny numeric change
     got2 = dev.cell_distances(to_dev(x + 5.0), cells).cpu().numpy()
     assert np.abs(got2 - want).max() <= 1e-11 * max(want.max(), 1.0)
-    # duplicate cells are at distance (numerically) zero
+    # R's sequential dist bit for bit (tests/hclust_restate.py::seq_dist)
+    assert np.array_equal(got.view(np.int64), hr.seq_dist(x[:, cells].T).view(np.int64))
+    # duplicate cells are at distance exactly zero
     if n >= 2:
         dup = np.concatenate([cells[:2], cells[:1]]).astype(np.int32)
         d3 = dev.cell_distances(to_dev(x), dup).cpu().numpy()
-        assert d3[0, 2] <= 1e-6 * max(want.max(), 1.0) and abs(d3[0, 1] - want[0, 1]) <= 1e-12 * max(want.max(), 1.0)
+        assert d3[0, 2] == 0.0 and d3[2, 0] == 0.0 and abs(d3[0, 1] - want[0, 1]) <= 1e-12 * max(want.max(), 1.0)
+        assert np.array_equal(d3.view(np.int64), hr.seq_dist(x[:, dup].T).view(np.int64))
 
 
 def test_parallelDist_mirror_matches_scipy(dev):

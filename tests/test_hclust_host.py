@@ -81,3 +81,43 @@ def test_restatement_rejects_what_the_library_rejects():
     for m in ("centroid", "median"):
         with pytest.raises(ValueError):
             hr.hclust(np.zeros((3, 3)), m)
+
+
+def assert_valid_r_dendrogram(merge, height, order, n):
+    assert merge.shape == (n - 1, 2) and height.shape == (n - 1,) and order.shape == (n,)
+    assert np.all(np.diff(height) >= 0)
+    assert sorted(order.tolist()) == list(range(1, n + 1))
+    assert sorted((-merge[merge < 0]).tolist()) == list(range(1, n + 1))
+    for i, row in enumerate(merge):
+        assert np.all(row[row > 0] <= i)   # a cluster is used only after the step that made it
+        if row[0] < 0 and row[1] < 0:
+            assert row[0] > row[1]          # two singletons: the smaller index first
+        elif row[0] > 0 and row[1] > 0:
+            assert row[0] < row[1]          # two clusters: the older first
+        else:
+            assert row[0] < 0               # a singleton before a cluster
+
+
+@pytest.mark.parametrize("method", ["ward.D2", "ward.D", "single", "complete", "average", "mcquitty"])
+def test_restatement_on_duplicated_rows(method):
+    """The GPU's distances are held to seq_dist; on duplicated rows seq_dist is exactly 0 and the restatement merges
+    them at height exactly 0, ties by index, as R does."""
+    rng = np.random.default_rng(2)
+    X = rng.normal(1.0, 0.3, size=(30, 500))
+    X[7] = X[2]
+    X[20] = X[11] = X[4]
+    d = hr.seq_dist(X)
+    assert d[2, 7] == 0.0 and d[4, 11] == 0.0 and d[4, 20] == 0.0 and d[11, 20] == 0.0
+    assert np.count_nonzero(d == 0.0) == 30 + 2 * 4
+    merge, height, order = hr.hclust(d, method)
+    assert_valid_r_dendrogram(merge, height, order, 30)
+    assert height[:3].tolist() == [0.0, 0.0, 0.0] and height[3] > 0
+    # the three zero-height merges are R's: singletons by index, then the triple's third member joins its cluster
+    assert merge[:3].tolist() == [[-3, -8], [-5, -12], [-21, 2]]
+    # n copies of one row: every height 0, merged by index
+    n = 9
+    merge, height, order = hr.hclust(hr.seq_dist(np.repeat(X[:1], n, axis=0)), method)
+    assert_valid_r_dendrogram(merge, height, order, n)
+    assert np.all(height == 0.0)
+    assert merge.tolist() == [[-1, -2]] + [[-(i + 2), i] for i in range(1, n - 1)]
+    assert order.tolist() == list(range(n, 2, -1)) + [1, 2]
