@@ -410,6 +410,65 @@ int icnv_random_trees_matrix_dev(const double *expr, int64_t G, int64_t C, const
 int icnv_random_trees_stats(int64_t *out, int32_t n);
 void icnv_random_trees_stats_reset(void);   /* R/inferCNV_tumor_subclusters.random_smoothed_trees.R:255 */
 
+/* ---- Leiden community detection (K11) -------------------------------------------------------------------------------
+ * cluster_leiden(graph_from_adjacency_matrix(sparseMatrix(nn2(t(x), k)$nn.idx), mode = "undirected"), resolution, objective)
+ * of .leiden_simple_snn (R/inferCNV_tumor_subclusters.R:726-741) for a BATCH of problems, on the kNN blocks of icnv_knn_dev.
+ * R's cluster_leiden draws from R's RNG inside igraph's C code: the partition is not claimed equal to igraph's.  The library
+ * defines the algorithm and its random stream exactly (restated in tests/leiden_restate.py);
+ * "as igraph does" below is believed, not verified.
+ *
+ * Graph of problem p (rows node_off[p] .. node_off[p+1] of nn_idx, k positions each, 0-based within the problem):
+ *   edge {i, j}, i != j, weight 1 iff j is in row i or i in row j (igraph's mode = "undirected" acts as "max" on a 0/1
+ *   matrix, :733); loop at i iff i is in row i; strength s_i = #neighbours + 2 loop_i; neighbour lists ascending.
+ * Weights (int64, exact): node weight 1 (CPM) or s_i (modularity); edge weights are edge counts, summed by aggregation.
+ * Resolution: r = gamma (CPM) or gamma / sum(s) (modularity, R's wrapper: resolution_parameter / sum(strength)), a double
+ *   division on the host.  Gain of moving v into C: diff = e_vC - ((w_v * W_C) * r) in doubles in that order, no FMA.
+ * One iteration (Traag et al. 2019 as igraph's leiden.c structures it), from singletons or the previous result; per level l:
+ *   1. move: queue = permutation stream (it, l, 1, 0) of the n_l nodes, all unstable; unused cluster ids on a stack
+ *      (pushed in increasing order).  Pop v, take it out of its cluster c0 (push c0 if it empties); candidates: the top of
+ *      the stack, then the clusters of v's neighbours by first appearance; best starts at c0 (its diff after v left),
+ *      replaced on a strictly greater diff.  v goes to best, stable; if best != c0, each neighbour (list order) that is
+ *      stable and not in best is appended and unstable.  At the end clusters are renumbered by first appearance: K_l.
+ *   2. K_l = n_l ends the iteration.
+ *   3. refine each move cluster c (nodes S_c ascending, visited in the order of permutation stream (it, l, 2, c)); every
+ *      node a singleton; T_c = sum of w over S_c; ext(X) = weight of X's edges to the rest of S_c.  Visit v only if its
+ *      cluster is still a singleton and ext(v) >= ((w_v * (T_c - w_v)) * r); empty it; candidates: that empty cluster,
+ *      then the refined clusters of v's neighbours in S_c by first appearance.  D is admissible iff
+ *      ext(D) >= ((W_D * (T_c - W_D)) * r); every admissible D with diff >= 0 adds exp_lib(diff / beta) to a sequential
+ *      running sum (exp_lib: leiden_internal.h, +inf above 709).  Sum finite: t = u * sum with u the next
+ *      Generator.random() of stream (it, l, 3, c), the first candidate whose running sum is > t (none: the last one that
+ *      added); sum +inf: the strict maximum of the admissible diffs (starting at 0 on the empty cluster).
+ *   4. refined clusters numbered by (c, first appearance in ascending node order); if there are n_l of them, aggregate on
+ *      the move clusters instead (igraph: "refinement didn't aggregate").
+ *   5. aggregate: one node per refined cluster, w summed, edge weights summed, no loops, rows ascending; each aggregate
+ *      starts the next level in its move cluster.
+ *   At the end of the iteration every node takes its aggregate's cluster, renumbered by first appearance.
+ * Streams: NumPy's Generator(Philox(key = [seed, token_p], counter = [0, phase, (it << 32) | l, c])), .permutation(n) and
+ *   .random() (K10's RtPhilox).
+ * Limits: 1 <= k <= min(128, n_p) (k > 128: ICNV_ERR_UNSUPPORTED), monotone node_off, a known objective, resolution finite
+ *   and >= 0, beta finite and > 0, 1 <= n_iterations <= 1000: ICNV_ERR_ARG before any launch.  An nn_idx entry outside
+ *   [0, n_p) is ICNV_ERR_ARG from a device check before anything is clustered.  Outputs stay untouched on any error.  Caps:
+ *   256 n_l + 1024 queue pops per move phase and 512 levels per iteration; more is ICNV_ERR_UNSUPPORTED (never a spin).
+ * Output: membership (1-based, DEVICE, one per node) and n_clusters (HOST, one per problem).  token: HOST, one per problem
+ * (NULL: all 0).  Synchronises the stream. */
+#define ICNV_LEIDEN_CPM 1
+#define ICNV_LEIDEN_MODULARITY 2
+int icnv_leiden_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, int32_t objective,
+                    const double *resolution, double beta, int32_t n_iterations, uint64_t seed, const uint64_t *token,
+                    int32_t *membership, int32_t *n_clusters, void *stream);
+/* The same with HOST nn_idx and membership. */
+int icnv_leiden(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, int32_t objective,
+                const double *resolution, double beta, int32_t n_iterations, uint64_t seed, const uint64_t *token,
+                int32_t *membership, int32_t *n_clusters);
+/* Diagnostic: the graph above as one CSR over the batch (DEVICE): row_off [sum n_p + 1] (problem p's rows follow each other),
+ * col [at least 2 k sum n_p] positions within the problem, strength [sum n_p].  Synchronises the stream. */
+int icnv_snn_graph_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, int64_t *row_off,
+                       int32_t *col, int64_t *strength, void *stream);
+/* Counters since the last reset: out[0] calls, [1] problems, [2] levels, [3] move visits (queue pops), [4] refinement
+ * visits, [5] draws, [6] wall microseconds of the calls. */
+int icnv_leiden_stats(int64_t *out, int32_t n);
+void icnv_leiden_stats_reset(void);   /* R/inferCNV_tumor_subclusters.R:736 */
+
 /* ---- HMM ---------------------------------------------------------------- */
 /* Viterbi.dthmm.adj (R/inferCNV_HMM.R:1101-1176) for every (cell, chromosome):
  * predict_CNV_via_HMM_on_indiv_cells (R/inferCNV_HMM.R:284-324) with K = 6 and

@@ -27,6 +27,7 @@ RT_PERMUTE, RT_SMOOTH, RT_CENTER = 0x1, 0x2, 0x4   # ICNV_RT_* stages of icnv_ra
 ST_NA_AWARE = 0x100     # the matrix may hold NaN: cells that do are recomputed with the reference's NA semantics
 
 OK, ERR_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_UNDERFLOW, ERR_NOMEM = 0, 1, 2, 3, 4, 5
+LEIDEN_CPM, LEIDEN_MODULARITY = 1, 2   # ICNV_LEIDEN_* objectives of icnv_leiden_dev
 
 
 class IcnvError(RuntimeError):
@@ -127,6 +128,11 @@ PROTOTYPES = {
     "icnv_random_trees_matrix_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _i32, _i32, _u64, _u64, _i32, _u32, _vp, _vp]),
     "icnv_random_trees_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_random_trees_stats_reset": (None, []),
+    "icnv_leiden_dev": (ct.c_int, [_vp, _i32, _ip, _i32, _i32, _dp, _dbl, _i32, _u64, _u64p, _vp, _ip, _vp]),
+    "icnv_leiden": (ct.c_int, [_vp, _i32, _ip, _i32, _i32, _dp, _dbl, _i32, _u64, _u64p, _vp, _ip]),
+    "icnv_snn_graph_dev": (ct.c_int, [_vp, _i32, _ip, _i32, _vp, _vp, _vp, _vp]),
+    "icnv_leiden_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_leiden_stats_reset": (None, []),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

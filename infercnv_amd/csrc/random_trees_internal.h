@@ -28,8 +28,9 @@ struct RtPhilox {
     uint64_t b0, b1, b2, b3;   // the current block; b0 holds the next 64-bit word
     int pos;                   // 32-bit draws taken from the current block (8 = empty)
 
-    RT_HD RtPhilox(uint64_t seed, uint64_t token, uint64_t g, uint64_t r)
-        : c0(0), c1(g), c2(r), c3(0), k0(seed), k1(token), b0(0), b1(0), b2(0), b3(0), pos(8) {}
+    // counter = [0, g, r, w3]: K10 uses w3 = 0, K11 (Leiden) puts its move cluster there
+    RT_HD RtPhilox(uint64_t seed, uint64_t token, uint64_t g, uint64_t r, uint64_t w3 = 0)
+        : c0(0), c1(g), c2(r), c3(w3), k0(seed), k1(token), b0(0), b1(0), b2(0), b3(0), pos(8) {}
 
     RT_HD void block() {
         if (++c0 == 0 && ++c1 == 0 && ++c2 == 0) ++c3;   // NumPy's carry
@@ -54,6 +55,19 @@ struct RtPhilox {
         ++pos;
         return v;
     }
+
+    // philox_next: the next 64-bit word.  A stream takes either 32-bit or 64-bit draws, never both (NumPy caches the high
+    // half of a 32-bit draw apart from the word buffer)
+    RT_HD uint64_t next64() {
+        if (pos >= 8) block();
+        const uint64_t v = b0;
+        b0 = b1; b1 = b2; b2 = b3;
+        pos += 2;
+        return v;
+    }
+
+    // Generator.random(): (next64 >> 11) * 2^-53
+    RT_HD double random() { return (double)(next64() >> 11) * (1.0 / 9007199254740992.0); }
 
     // random_interval(max) for max < 2^32: masked rejection
     RT_HD uint32_t interval(uint32_t max) {

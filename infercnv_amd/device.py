@@ -514,6 +514,70 @@ def random_trees_stats(reset=False):
     return dict(zip(RANDOM_TREES_STATS, (int(v) for v in out)))
 
 
+LEIDEN_OBJECTIVES = {"CPM": _lib.LEIDEN_CPM, "modularity": _lib.LEIDEN_MODULARITY}   # ICNV_LEIDEN_* of include/icnv.h
+
+
+def _leiden_objective(objective):
+    """An R objective_function name -> its ICNV_LEIDEN_* code; an unknown name -> -1, which the library refuses."""
+    return LEIDEN_OBJECTIVES.get(objective, -1) if isinstance(objective, str) else int(objective)
+
+
+def _leiden_offsets(nn_idx, sizes):
+    if not (nn_idx.is_cuda and nn_idx.dtype == torch.int32 and nn_idx.dim() == 2 and nn_idx.is_contiguous()):
+        raise ValueError("nn_idx must be a contiguous (sum n_p, k) int32 CUDA tensor")
+    off = np.zeros(len(sizes) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(np.asarray(sizes, dtype=np.int64))
+    if off[-1] != nn_idx.shape[0]:
+        raise ValueError("the problem sizes must add up to the rows of nn_idx")
+    return i32(off)
+
+
+def leiden(nn_idx, sizes, objective, resolution, beta=0.01, n_iterations=2, seed=0, tokens=None):
+    """cluster_leiden on the kNN graph of .leiden_simple_snn (R/inferCNV_tumor_subclusters.R:726-741) for a batch of problems
+    in one call (icnv_leiden_dev, DESIGN K11).  nn_idx: the (sum n_p, k) int32 CUDA tensor of `knn` (positions within each
+    problem); sizes: n_p per problem; objective "CPM" or "modularity"; resolution one gamma or one per problem; tokens one
+    uint64 per problem (the stream's second key word, default 0).  Returns (membership, n_clusters): a 1-based int32 CUDA
+    tensor (sum n_p,) and a numpy int32 array per problem.  Synchronises the device."""
+    L = _lib.load()
+    off, op = _leiden_offsets(nn_idx, sizes)
+    P = len(sizes)
+    res, rp = f64(np.broadcast_to(np.asarray(resolution, dtype=np.float64), (P,)))
+    tok, tp = _u64([0] * P if tokens is None else tokens)
+    if tok.size != P:
+        raise ValueError("one token per problem")
+    memb = torch.empty(max(int(off[-1]), 1), dtype=torch.int32, device=nn_idx.device)
+    ncl = np.zeros(max(P, 1), dtype=np.int32)
+    check(L.icnv_leiden_dev(_ptr(nn_idx), int(nn_idx.shape[1]), op, P, _leiden_objective(objective), rp, float(beta),
+                            int(n_iterations), int(seed) & (2**64 - 1), tp, _ptr(memb), ncl.ctypes.data_as(_lib._ip), _stream()))
+    return memb[:int(off[-1])], ncl[:P]
+
+
+def snn_graph(nn_idx, sizes):
+    """The graph of `leiden` as one CSR over the batch (icnv_snn_graph_dev): (row_off int64, col int32, strength int64) CUDA
+    tensors; problem p's rows follow each other, columns are positions within the problem, rows ascending."""
+    L = _lib.load()
+    off, op = _leiden_offsets(nn_idx, sizes)
+    n, k = int(off[-1]), int(nn_idx.shape[1])
+    row_off = torch.empty(n + 1, dtype=torch.int64, device=nn_idx.device)
+    col = torch.empty(max(2 * k * n, 1), dtype=torch.int32, device=nn_idx.device)
+    strength = torch.empty(max(n, 1), dtype=torch.int64, device=nn_idx.device)
+    check(L.icnv_snn_graph_dev(_ptr(nn_idx), k, op, len(sizes), _ptr(row_off), _ptr(col), _ptr(strength), _stream()))
+    return row_off, col[:int(row_off[-1].item())], strength[:n]
+
+
+LEIDEN_STATS = ("calls", "problems", "levels", "move_visits", "refine_visits", "draws", "us")
+
+
+def leiden_stats(reset=False):
+    """icnv_leiden_stats as a dict (`us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(LEIDEN_STATS))()
+    check(L.icnv_leiden_stats(out, len(LEIDEN_STATS)))
+    if reset:
+        L.icnv_leiden_stats_reset()
+    return dict(zip(LEIDEN_STATS, (int(v) for v in out)))
+
+
 def state_consensus(states, groups, overwrite=False):
     """.get_state_consensus (R/inferCNV_HMM.R:977-987) per group -> (n_groups, G) uint8; with
     overwrite=True also returns the state matrix with every member cell set to its group's consensus."""

@@ -331,3 +331,205 @@ def define_signif_tumor_subclusters_via_random_smooothed_trees(infercnv_obj: Inf
             infercnv_obj.hspike, p_val, hclust_method, window_size, max_recursion_depth, min_cluster_size_recurse,
             seed=seed + 1)
     return out
+
+
+# ------------------------------------------------------------------ Leiden subclustering (DESIGN K11)
+LEIDEN_BETA = 0.01          # cluster_leiden's beta (R igraph default)
+LEIDEN_ITERATIONS = 2       # cluster_leiden's n_iterations (R igraph default)
+
+
+def auto_leiden_resolution(n: int) -> float:
+    """leiden_resolution = "auto": (11.98 / ncol)^(1 / 1.165) (R/inferCNV_tumor_subclusters.R:583-586, 673-676)."""
+    return (11.98 / n) ** (1 / 1.165)
+
+
+def _device_leiden(seed):
+    def fn(nn_idx, sizes, objective, gammas, tokens):
+        memb, _ = device.leiden(nn_idx, sizes, objective, gammas, LEIDEN_BETA, LEIDEN_ITERATIONS, seed, tokens)
+        return memb.cpu().numpy()
+    return fn
+
+
+def cluster_leiden(nn_idx, resolution_parameter, objective_function="CPM", beta=LEIDEN_BETA, n_iterations=LEIDEN_ITERATIONS,
+                   seed=0, token=0):
+    """cluster_leiden(graph, resolution_parameter, objective_function)$membership on the graph of one (n, k) nn_idx block
+    (.leiden_simple_snn, R/inferCNV_tumor_subclusters.R:733-739) by icnv_leiden_dev: a 1-based numpy int32 vector.  The
+    partition follows the library's contract (include/icnv.h, K11), not igraph's RNG."""
+    import torch
+    nn = nn_idx if isinstance(nn_idx, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(nn_idx, dtype=np.int32))
+    nn = nn.to(device="cuda", dtype=torch.int32).contiguous()
+    memb, _ = device.leiden(nn, [nn.shape[0]], objective_function, resolution_parameter, beta, n_iterations, seed, [token])
+    return memb.cpu().numpy()
+
+
+def leiden_simple_snn(infercnv_obj: InfercnvObject, cells, k_nn, resolution_parameter, objective_function="CPM", genes=None,
+                      seed=0, token=0):
+    """.leiden_simple_snn(expr.data[genes, cells], k_nn, resolution_parameter, objective_function)
+    (R/inferCNV_tumor_subclusters.R:725-741): the exact kNN (K8) and the Leiden partition (K11), both on the GPU."""
+    cells = np.asarray(cells, dtype=np.int32)
+    G = np.asarray(infercnv_obj.expr_data).shape[0]
+    genes = np.arange(G, dtype=np.int32) if genes is None else np.asarray(genes, dtype=np.int32)
+    idx, _ = device.knn(_to_device(infercnv_obj), [(genes, cells)], k_nn)
+    return cluster_leiden(idx, resolution_parameter, objective_function, seed=seed, token=token)
+
+
+def _check_leiden_args(leiden_method, leiden_function, partition_method, restrict_to_DE_genes):
+    if restrict_to_DE_genes:
+        raise NotImplementedError("restrict_to_DE_genes = TRUE (.find_DE_stat_significance) is not implemented")
+    if partition_method in ("qnorm", "pheight", "qgamma"):
+        raise NotImplementedError(f'partition_method = "{partition_method}" is not implemented')
+    if partition_method not in ("leiden", "none"):
+        raise ValueError(f"unknown partition_method {partition_method!r}")
+    if leiden_method not in ("PCA", "simple"):
+        raise ValueError(f"unknown leiden_method {leiden_method!r}")
+    if leiden_function not in ("CPM", "modularity"):
+        raise ValueError(f"unknown leiden_function {leiden_function!r}")
+
+
+def _resolution(leiden_resolution, n):
+    return auto_leiden_resolution(n) if isinstance(leiden_resolution, str) and leiden_resolution == "auto" else float(leiden_resolution)
+
+
+def _leiden_problems(x, genes, problems, k_nn, leiden_method, objective, leiden_resolution, leiden_fn):
+    """One K8 call and one Leiden call for every (cells, token) problem: a list of 1-based partitions."""
+    if not problems:
+        return []
+    if leiden_method == "PCA":
+        raise NotImplementedError('leiden_method = "PCA" (Seurat vst / irlba / annoy) is not implemented; use "simple"')
+    idx, _ = device.knn(x, [(g, c) for g, (c, _) in zip(genes, problems)], k_nn)
+    sizes = [c.size for c, _ in problems]
+    memb = leiden_fn(idx, sizes, objective, [_resolution(leiden_resolution, n) for n in sizes], [t for _, t in problems])
+    out, r0 = [], 0
+    for n in sizes:
+        out.append(np.asarray(memb[r0:r0 + n]))
+        r0 += n
+    return out
+
+
+def define_signif_tumor_subclusters(infercnv_obj: InfercnvObject, p_val=0.1, k_nn=20, leiden_method="PCA", leiden_function="CPM",
+                                    leiden_resolution="auto", leiden_method_per_chr="simple",
+                                    leiden_function_per_chr="modularity", leiden_resolution_per_chr=1, hclust_method="ward.D2",
+                                    cluster_by_groups=True, partition_method="leiden", per_chr_hmm_subclusters=False,
+                                    per_chr_hmm_subclusters_references=False, z_score_filter=0.8, restrict_to_DE_genes=False,
+                                    seed=0, leiden_fn=None):
+    """define_signif_tumor_subclusters (R/inferCNV_tumor_subclusters.R:2-177) with leiden_method(_per_chr) = "simple" or
+    partition_method = "none", on the GPU: per route one K8 call, one Leiden call (K11) and one K9 call over every group and
+    partition.  Returns (copy of the object with tumor_subclusters = {"hc": {group: ...}, "subclusters": {group: {name:
+    0-based cells}}}, subclusters_per_chr or None).
+
+    hc[group]: None (< 3 cells), one HClust (k_nn >= n, or "none"), or the list of the partitions' HClust of >= 2 cells in
+    subcluster order (the Leiden branch; ape's binding of them into one tree, :602-640, is not mirrored).  Partitions are
+    named "<group>_s<label>", by decreasing size then label (:604) -- ascending label on the per-chromosome route (:687).
+    The streams are keyed by seed and FNV-1a-64 of the group name (of chr + "\\0" + group per chromosome); R's are
+    igraph's.  leiden_fn(nn_idx, sizes, objective, gammas, tokens) -> 1-based memberships replaces the device Leiden
+    (tests hold the driver to the restatement with it)."""
+    leiden_method_per_chr = leiden_method_per_chr if per_chr_hmm_subclusters else "simple"
+    _check_leiden_args(leiden_method, leiden_function, partition_method, restrict_to_DE_genes)
+    _check_leiden_args(leiden_method_per_chr, leiden_function_per_chr, partition_method, False)
+    leiden_fn = _device_leiden(seed) if leiden_fn is None else leiden_fn
+    kept = zscore_kept_genes(infercnv_obj, z_score_filter)
+    if kept.size == 0:
+        raise ValueError("the z-score filter keeps no gene (R: expr.data[-integer(0), ] has no row)")
+    kept32 = kept.astype(np.int32)
+    groups = random_trees_groups(infercnv_obj, cluster_by_groups)
+    cell_names = np.asarray(infercnv_obj.cells())
+    x = _to_device(infercnv_obj)
+
+    hc, subclusters, trees = {}, {}, []          # trees: (group, cells) of the K9 batch, in order
+    if partition_method == "none":               # .single_tumor_subclustering (:181-268): one tree, one subcluster
+        for g, c in groups.items():
+            if c.size > 2:
+                trees.append((g, c))
+            else:
+                hc[g], subclusters[g] = None, {f"{g}_s1": c}
+    else:                                        # .single_tumor_leiden_subclustering (:569-642)
+        problems, keys = [], []
+        for g, c in groups.items():
+            if c.size < 3:
+                hc[g], subclusters[g] = None, {f"{g}_s1": c}
+            elif k_nn >= c.size:
+                subclusters[g] = {g: c}
+                trees.append((g, c))
+            else:
+                problems.append((c.astype(np.int32), fnv1a64(g)))
+                keys.append(g)
+        parts = _leiden_problems(x, [kept32] * len(problems), problems, k_nn, leiden_method, leiden_function,
+                                 leiden_resolution, leiden_fn)
+        for g, (c, _), part in zip(keys, problems, parts):
+            labels, sizes = np.unique(part, return_counts=True)
+            subclusters[g] = {}
+            hc[g] = []
+            for i in labels[np.lexsort((labels, -sizes))]:   # sort(table(partition), decreasing = TRUE): ties by label
+                sub = c[part == i].astype(np.int64)
+                subclusters[g][f"{g}_s{i}"] = sub
+                if sub.size >= 2:
+                    trees.append((g, sub))
+    if trees:
+        res = device.hclust_cells(x, [(kept32, c.astype(np.int32)) for _, c in trees], hclust_method)
+        for (g, c), (merge, height, order) in zip(trees, res):
+            tree = HClust(merge.cpu().numpy(), height.cpu().numpy(), order.cpu().numpy(), cell_names[c], hclust_method)
+            if partition_method == "none":
+                hc[g] = tree
+                subclusters[g] = {f"{g}_s1": c[tree.order - 1]}    # cutree(hc, k = 1), cells in hc$order
+            elif isinstance(hc.get(g), list):
+                hc[g].append(tree)
+            else:
+                hc[g] = tree
+    out = infercnv_obj.copy()
+    out.tumor_subclusters = {"hc": {g: hc[g] for g in groups}, "subclusters": {g: subclusters[g] for g in groups}}
+
+    per_chr = None
+    if per_chr_hmm_subclusters and partition_method == "leiden":
+        if per_chr_hmm_subclusters_references:
+            chr_groups = groups
+        else:
+            obs = {k: np.asarray(v, dtype=np.int64) for k, v in infercnv_obj.observation_grouped_cell_indices.items()}
+            chr_groups = obs if cluster_by_groups else {
+                "all_observations": np.concatenate(list(obs.values())) if obs else np.zeros(0, dtype=np.int64)}
+        per_chr = _leiden_per_chr(infercnv_obj, x, kept, chr_groups, k_nn, leiden_method_per_chr, leiden_function_per_chr,
+                                  leiden_resolution_per_chr, leiden_fn)
+        if not per_chr_hmm_subclusters_references:
+            refs = {k: np.asarray(v, dtype=np.int64) for k, v in infercnv_obj.reference_grouped_cell_indices.items()}
+            for c in per_chr:
+                per_chr[c].update(refs)
+    if infercnv_obj.hspike is not None:
+        # "-mirroring for hspike" (:151-160): cluster_by_groups = TRUE, partition_method = "none", the rest at R's defaults
+        out.hspike = define_signif_tumor_subclusters(infercnv_obj.hspike, cluster_by_groups=True, partition_method="none")[0]
+    return out, per_chr
+
+
+def _leiden_per_chr(infercnv_obj, x, kept, groups, k_nn, leiden_method, objective, leiden_resolution, leiden_fn):
+    """.whole_dataset_leiden_subclustering_per_chr (R/inferCNV_tumor_subclusters.R:646-697) on the filtered genes."""
+    chr_all = np.asarray(infercnv_obj.gene_order.chr).astype(str)
+    chrs = chr_all[kept]
+    _, first = np.unique(chr_all, return_index=True)
+    levels = chr_all[np.sort(first)]
+    present = set(chrs.tolist())
+    C = np.asarray(infercnv_obj.expr_data).shape[1]
+    out = {c: {} for c in levels}
+    problems, genes, keys = [], [], []
+    for c in levels:
+        genes_c = kept[chrs == c].astype(np.int32)
+        for g, cells in groups.items():
+            if c not in present:
+                out[c][g] = np.arange(C, dtype=np.int64)                     # every cell (:654-656)
+            elif cells.size < 3 or k_nn >= cells.size:
+                out[c][g] = cells                                            # kept as is (:661-668)
+            else:
+                out[c][g] = None                                             # placeholder: keeps R's order of the names
+                problems.append((cells.astype(np.int32), fnv1a64(f"{c}\0{g}")))
+                genes.append(genes_c)
+                keys.append((c, g))
+    parts = _leiden_problems(x, genes, problems, k_nn, leiden_method, objective, leiden_resolution, leiden_fn)
+    for (c, g), (cells, _), part in zip(keys, problems, parts):
+        entries = {}
+        for i in np.unique(part):                                            # unique(partition[grouping(partition)])
+            entries[f"{g}_s{i}"] = cells[part == i].astype(np.int64)
+        d = out[c]
+        out[c] = {}
+        for name, v in d.items():
+            if name == g and v is None:
+                out[c].update(entries)
+            else:
+                out[c][name] = v
+    return out
