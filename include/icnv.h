@@ -635,6 +635,67 @@ void icnv_group_hmm_end(icnv_group_hmm_t *plan);
 int icnv_gather_values_dev(const double *expr, int64_t n_elements, const int64_t *offsets_host, int64_t n, double *out_host, void *stream);
 int icnv_gather_values(const double *expr, int64_t G, int64_t C, const int64_t *offsets, int64_t n, double *out);
 
+/* ---- non-DE gene masking (K12) --------------------------------------------------------------------------------------
+ * get_DE_genes_basic / .mask_DE_genes (R/inferCNV_mask_non_DE.R:28-258, step 21 of run()): per gene and per comparison
+ * (x group, y group) = (normal type, tumour subcluster), wilcox.test(x, y) or t.test(x, y), then p.adjust(, "BH") over the
+ * genes of each comparison.  DESIGN.md section 4 K12, restated in tests/de_restate.py; R's arithmetic is read, not run.
+ * Groups: cell_idx / cell_off (HOST, int32, 0-based columns of the matrix, cell_off[0] = 0); cmp: HOST, n_cmp pairs of
+ * group numbers (x first).  Element (gene g, cell c) at expr[c * ld + g].  Outputs [n_cmp x G] (row k = comparison k):
+ * stat (W, or t), p and padj.
+ * ICNV_DE_WILCOXON: per (gene, cell) jitter j = 1e-4 + 1e-4 z (jitter != 0), z from NumPy's
+ *   Generator(Philox(key = [seed, ICNV_DE_JITTER_TOKEN], counter = [0, g, c, 0])): u1, u2 = two .random() draws,
+ *   z = qnorm((floor(2^27 u1) + u2) / 2^27) (R's INVERSION; AS 241 with the library's table log).  The same cell has the same
+ *   jitter in every comparison of a call.  Values x + j; non-finite values dropped; an empty sample is ICNV_ERR_ARG naming the
+ *   comparison and the gene.  Midranks of the pooled sample (-0 == +0); 2W = 2 sum(ranks of x) - n.x (n.x + 1), exact;
+ *   T = sum(t^3 - t) over the pooled tie groups, exact.  n.x < 50, n.y < 50 and T = 0: p = min(2 P, 1), P the exact
+ *   Mann-Whitney tail on W's side (upper P(W' >= W) if 2W > n.x n.y, else lower P(W' <= W)) CORRECTLY ROUNDED from 128-bit
+ *   integer counts (R sums rounded cwilcox terms over a choose() from lgamma: it may differ in the last bits).  Otherwise
+ *   z = W - n.x n.y / 2; SIGMA = sqrt((n.x n.y / 12) ((n.x + n.y + 1) - T / ((n.x + n.y) (n.x + n.y - 1))));
+ *   z = (z - sign(z) 0.5) / SIGMA; p = 2 min(pnorm(z), pnorm(z, lower = FALSE)), pnorm_both's non-log branches with exp_lib
+ *   (leiden_internal.h, 0 below -708).
+ * ICNV_DE_T: Welch, NaN dropped, +-Inf kept.  mean = correctly rounded sum / n; var = (correctly rounded sum of
+ *   round(round(x - mean)^2)) / (n - 1); sx = sqrt(vx / nx); se = sqrt(sx sx + sy sy); df = (se^2)^2 / ((sx^2)^2 / (nx - 1) +
+ *   (sy^2)^2 / (ny - 1)) (R: powl(se, 4)); t = (mx - my) / se; p = I_{df / (df + t^2)}(df / 2, 1 / 2) = 2 pt(-|t|, df) by the
+ *   continued fraction of the regularized incomplete beta (modified Lentz, at most ICNV_DE_CF_MAX_ITER steps, symmetric form
+ *   above (a + 1) / (a + b + 2)), its prefactor exp_lib(a log x + b log(1 - x) - lbeta) from the table log, a series log1p and
+ *   Stirling's series for lgamma(a) - lgamma(a + 1/2).  p is NaN (R: NA) when nx < 2, ny < 2, either sample holds +-Inf, or
+ *   se < 10 eps max(|mx|, |my|).
+ * BH per row: n = # non-NaN p; padj = min(1, min over q >= p of fl(n / #(p' <= q)) q); NaN stays NaN.
+ * Genes run in waves within ICNV_DE_SCRATCH_MB (default 8192) of sort scratch; no wave split changes a bit.
+ * Limits: 1 <= G, C < 2^31, groups non-empty, indices in range, known test: ICNV_ERR_ARG before any launch.  Synchronises. */
+#define ICNV_DE_WILCOXON 1
+#define ICNV_DE_T 2
+#define ICNV_DE_JITTER_TOKEN 0x6E6F6E44456A6974ull   /* "nonDEjit" */
+#define ICNV_DE_CF_MAX_ITER 20000
+int icnv_de_tests_dev(const double *expr, int64_t G, int64_t C, int64_t ld, const int32_t *cell_idx, const int32_t *cell_off,
+                      int32_t n_groups, const int32_t *cmp, int32_t n_cmp, int32_t test, int32_t jitter, uint64_t seed,
+                      double *stat, double *p, double *padj, void *stream);
+/* The same with a HOST matrix (ld = G) and HOST outputs. */
+int icnv_de_tests(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, const int32_t *cell_off, int32_t n_groups,
+                  const int32_t *cmp, int32_t n_cmp, int32_t test, int32_t jitter, uint64_t seed, double *stat, double *p,
+                  double *padj);
+/* .mask_DE_genes (R/inferCNV_mask_non_DE.R:77-134): count(g, c) = base[c] + #{k in the comparisons of cell c
+ * (cc_idx[cc_off[c] .. cc_off[c+1]]): padj[k, g] < p_val_thresh} (the caller sets base = N for reference cells and the cells
+ * of subclusters under 5 cells, and lists only the comparisons of the other subclusters); out = mask value where
+ * count == 0 (ANY), count < N / 2 (MOST) or count != N (ALL), expr elsewhere.  use_mean: the mask value is the correctly
+ * rounded mean of the whole G x C matrix, else mask_val; *mean_out (HOST, optional) receives the value used.  out may be
+ * expr (same ld).  padj, expr, out: DEVICE; base, cc_off, cc_idx: HOST.  Synchronises. */
+#define ICNV_DE_MASK_ANY 0
+#define ICNV_DE_MASK_MOST 1
+#define ICNV_DE_MASK_ALL 2
+int icnv_mask_non_de_dev(const double *expr, int64_t G, int64_t C, int64_t ld, const double *padj, int32_t n_cmp,
+                         double p_val_thresh, const int32_t *base, const int32_t *cc_off, const int32_t *cc_idx, int32_t n_normal,
+                         int32_t rule, int32_t use_mean, double mask_val, double *out, int64_t ld_out, double *mean_out,
+                         void *stream);
+/* The same with HOST expr / padj / out (ld = ld_out = G). */
+int icnv_mask_non_de(const double *expr, int64_t G, int64_t C, const double *padj, int32_t n_cmp, double p_val_thresh,
+                     const int32_t *base, const int32_t *cc_off, const int32_t *cc_idx, int32_t n_normal, int32_t rule,
+                     int32_t use_mean, double mask_val, double *out, double *mean_out);
+/* Counters since the last reset: out[0] calls, [1] comparisons, [2] genes, [3] segments sorted in LDS (<= 4096 values),
+ * [4] segments merged through HBM, [5] waves, [6] wall microseconds of the test calls. */
+int icnv_de_stats(int64_t *out, int32_t n);
+void icnv_de_stats_reset(void);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

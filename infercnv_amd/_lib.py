@@ -28,6 +28,9 @@ ST_NA_AWARE = 0x100     # the matrix may hold NaN: cells that do are recomputed 
 
 OK, ERR_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_UNDERFLOW, ERR_NOMEM = 0, 1, 2, 3, 4, 5
 LEIDEN_CPM, LEIDEN_MODULARITY = 1, 2   # ICNV_LEIDEN_* objectives of icnv_leiden_dev
+DE_WILCOXON, DE_T = 1, 2               # ICNV_DE_* tests of icnv_de_tests_dev
+DE_MASK_ANY, DE_MASK_MOST, DE_MASK_ALL = 0, 1, 2   # ICNV_DE_MASK_* rules of icnv_mask_non_de_dev
+DE_JITTER_TOKEN = 0x6E6F6E44456A6974   # ICNV_DE_JITTER_TOKEN: the jitter stream's second key word
 
 
 class IcnvError(RuntimeError):
@@ -133,6 +136,13 @@ PROTOTYPES = {
     "icnv_snn_graph_dev": (ct.c_int, [_vp, _i32, _ip, _i32, _vp, _vp, _vp, _vp]),
     "icnv_leiden_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_leiden_stats_reset": (None, []),
+    "icnv_de_tests_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _ip, _i32, _ip, _i32, _i32, _i32, _u64, _vp, _vp, _vp, _vp]),
+    "icnv_de_tests": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _ip, _i32, _i32, _i32, _u64, _vp, _vp, _vp]),
+    "icnv_mask_non_de_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _vp, _i32, _dbl, _ip, _ip, _ip, _i32, _i32, _i32, _dbl, _vp, _i64,
+                                        _dp, _vp]),
+    "icnv_mask_non_de": (ct.c_int, [_vp, _i64, _i64, _vp, _i32, _dbl, _ip, _ip, _ip, _i32, _i32, _i32, _dbl, _vp, _dp]),
+    "icnv_de_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_de_stats_reset": (None, []),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

@@ -578,6 +578,73 @@ def leiden_stats(reset=False):
     return dict(zip(LEIDEN_STATS, (int(v) for v in out)))
 
 
+DE_TESTS = {"wilcoxon": _lib.DE_WILCOXON, "t": _lib.DE_T}   # ICNV_DE_* of include/icnv.h
+DE_RULES = {"any": _lib.DE_MASK_ANY, "most": _lib.DE_MASK_MOST, "all": _lib.DE_MASK_ALL}
+
+
+def de_tests(x, groups, comparisons, test="wilcoxon", jitter=True, seed=0):
+    """The per-gene tests of get_DE_genes_basic (R/inferCNV_mask_non_DE.R:157-258) for a batch of comparisons in one call
+    (icnv_de_tests_dev, DESIGN K12).  x: (C, G) CUDA float64 matrix with contiguous rows; groups: list of 0-based cell index
+    vectors; comparisons: (x group, y group) pairs = (normal type, subcluster); test "wilcoxon" or "t".  Returns (stat, p,
+    padj) CUDA float64 tensors (n_cmp, G): W or t, the p-values and their BH adjustment per row.  Synchronises the device."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    code = DE_TESTS.get(test, -1) if isinstance(test, str) else int(test)
+    cidx, coff = pack_groups(groups)
+    cidx, cp = i32(cidx)
+    coff, cop = i32(coff)
+    cmp = np.asarray(comparisons, dtype=np.int32).reshape(-1, 2)
+    cmp, mp = i32(cmp)
+    n = max(cmp.shape[0], 1)
+    stat = torch.empty((n, G), dtype=torch.float64, device=x.device)
+    p = torch.empty_like(stat)
+    padj = torch.empty_like(stat)
+    check(L.icnv_de_tests_dev(_ptr(x), G, C, ld, cp, cop, len(groups), mp, cmp.shape[0], code, int(bool(jitter)),
+                              int(seed) & (2**64 - 1), _ptr(stat), _ptr(p), _ptr(padj), _stream()))
+    return stat, p, padj
+
+
+def mask_non_de(x, padj, p_val_thresh, base, cell_cmps, n_normal, rule="any", mask_val=None, out=None):
+    """.mask_DE_genes (R/inferCNV_mask_non_DE.R:77-134) on the device (icnv_mask_non_de_dev): count(g, c) = base[c] + the
+    comparisons k in cell_cmps[c] with padj[k, g] < p_val_thresh; the mask value where the rule holds.  mask_val None: the
+    correctly rounded mean of x.  out: a (C, G) tensor (may be x), default a new one.  Returns (out, mask value used)."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    code = DE_RULES.get(rule, -1) if isinstance(rule, str) else int(rule)
+    if out is None:
+        out = torch.empty((C, G), dtype=torch.float64, device=x.device)
+    Co, Go, ld_out = _check_matrix_ld(out)
+    if (Co, Go) != (C, G):
+        raise ValueError("out must have the shape of x")
+    b, bp = i32(base)
+    off = np.zeros(C + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(v) for v in cell_cmps])
+    off, op = i32(off)
+    idx = np.concatenate([np.asarray(v, dtype=np.int32) for v in cell_cmps]) if off[-1] else np.zeros(1, dtype=np.int32)
+    idx, ip = i32(idx)
+    n_cmp = padj.shape[0] if padj is not None else 0
+    if padj is not None and not (padj.is_cuda and padj.dtype == torch.float64 and padj.is_contiguous() and padj.shape[-1] == G):
+        raise TypeError("padj must be a contiguous (n_cmp, G) CUDA float64 tensor")
+    used = ct.c_double(0.0)
+    check(L.icnv_mask_non_de_dev(_ptr(x), G, C, ld, _ptr(padj), n_cmp, float(p_val_thresh), bp, op, ip, int(n_normal), code,
+                                 int(mask_val is None), float("nan") if mask_val is None else float(mask_val), _ptr(out), ld_out,
+                                 ct.byref(used), _stream()))
+    return out, used.value
+
+
+DE_STATS = ("calls", "comparisons", "genes", "segments_lds", "segments_hbm", "waves", "us")
+
+
+def de_stats(reset=False):
+    """icnv_de_stats as a dict (`us`: wall time of the test calls in microseconds); reset=True zeroes the counters."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(DE_STATS))()
+    check(L.icnv_de_stats(out, len(DE_STATS)))
+    if reset:
+        L.icnv_de_stats_reset()
+    return dict(zip(DE_STATS, (int(v) for v in out)))
+
+
 def state_consensus(states, groups, overwrite=False):
     """.get_state_consensus (R/inferCNV_HMM.R:977-987) per group -> (n_groups, G) uint8; with
     overwrite=True also returns the state matrix with every member cell set to its group's consensus."""
