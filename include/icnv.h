@@ -652,7 +652,7 @@ int icnv_gather_values(const double *expr, int64_t G, int64_t C, const int64_t *
  *   integer counts (R sums rounded cwilcox terms over a choose() from lgamma: it may differ in the last bits).  Otherwise
  *   z = W - n.x n.y / 2; SIGMA = sqrt((n.x n.y / 12) ((n.x + n.y + 1) - T / ((n.x + n.y) (n.x + n.y - 1))));
  *   z = (z - sign(z) 0.5) / SIGMA; p = 2 min(pnorm(z), pnorm(z, lower = FALSE)), pnorm_both's non-log branches with exp_lib
- *   (leiden_internal.h, 0 below -708).
+ *   (lib_math.h, 0 below -708).
  * ICNV_DE_T: Welch, NaN dropped, +-Inf kept.  mean = correctly rounded sum / n; var = (correctly rounded sum of
  *   round(round(x - mean)^2)) / (n - 1); sx = sqrt(vx / nx); se = sqrt(sx sx + sy sy); df = (se^2)^2 / ((sx^2)^2 / (nx - 1) +
  *   (sy^2)^2 / (ny - 1)) (R: powl(se, 4)); t = (mx - my) / se; p = I_{df / (df + t^2)}(df / 2, 1 / 2) = 2 pt(-|t|, df) by the
@@ -695,6 +695,59 @@ int icnv_mask_non_de(const double *expr, int64_t G, int64_t C, const double *pad
  * [4] segments merged through HBM, [5] waves, [6] wall microseconds of the test calls. */
 int icnv_de_stats(int64_t *out, int32_t n);
 void icnv_de_stats_reset(void);
+
+/* ---- Bayesian filter of the predicted CNV regions (K13) -----------------------------------------------------------------
+ * inferCNVBayesNet (R/inferCNV_BayesNet.R:1054-1107 with the model file inst/BUGS_Mixture_Model, steps 18-19 of run()): per
+ * predicted region -- one contiguous gene run x the cells of one cell group -- a K-state mixture with FIXED state means
+ * mu[k] and precisions tau[k]: every cell has one state eps[c], the values of its genes are Normal(mu[eps[c]], 1 / tau[eps[c]]),
+ * eps[c] ~ Categorical(theta), theta ~ Dirichlet(1, .., 1).  The reference samples it with JAGS; this library owns a Gibbs
+ * sampler of the same posterior with its own documented random stream, so results are reproducible here and statistically,
+ * not bit-wise, those of JAGS.  DESIGN.md section 4 K13, restated in tests/bayes_restate.py.
+ * Regions: gene_start / gene_count (HOST, rows gene_start[r] .. + gene_count[r] - 1), cell_idx / cell_off (HOST, int32 columns
+ * and int64 offsets, cell_off[0] = 0); region r's cells are the rows cell_off[r] .. cell_off[r + 1] - 1 of every per-cell
+ * output, in the order given.  Element (gene g, cell c) at expr[c * ld + g]; the values of a region must be finite.
+ * icnv_bayes_loglik: per (row, state k), every operation rounded by itself:
+ *   ssq = 0; for g in gene order: d = x - mu[k]; ssq = ssq + d * d
+ *   ll[row, k] = (gene_count * 0.5) * log_lib(tau[k]) - (tau[k] * 0.5) * ssq          (log_lib: the library's table log)
+ *   m = max_k ll[row, .];  L[row, k] = exp_lib(ll[row, k] - m)     (exp_lib of lib_math.h: 0 below -708, so L is 1 at the
+ *   maximum and exactly 0 for every state more than 708 below it).  ll, L: DEVICE [rows x K] doubles, row-major.
+ * icnv_bayes_sample: K chains per region; chain ch starts from eps == ch (n[ch] = the region's cell count, 0 elsewhere) and
+ *   runs n_adapt + n_burn discarded and then n_keep kept iterations t = 0, 1, ..  Every draw is the start of its own stream
+ *   of NumPy's Generator(Philox(key = [seed, token[r]], counter = [0, w1, t, w3])).random(); token[r] identifies the region
+ *   (the callers here pass fnv1a64 of its name), so a region's output does not depend on the other regions of the call.
+ *   theta: for k = 0 .. K-1, g[k] ~ Gamma(1 + n[k], 1) by Marsaglia-Tsang: d = shape - 1/3, c = 1 / sqrt(9 d); attempt
+ *     j = 0, 1, .. takes u1, u2 from the stream w1 = k, w3 = ch 2^40 + 2^32 + j: u1 = 0 rejects; x = qnorm(u1) (AS 241 with
+ *     log_lib); v = 1 + c x; v <= 0 rejects; v = (v v) v; accept d v if u2 < 1 - 0.0331 ((x x) (x x)), else if
+ *     log_lib(u2) < 0.5 (x x) + d ((1 - v) + log_lib(v)) (u2 = 0: log_lib gives -inf, which accepts).  After
+ *     ICNV_BAYES_GAMMA_ATTEMPTS rejections g[k] = d.  S = ((g[0] + g[1]) + ..) + g[K-1]; theta[k] = g[k] / S.
+ *   cells: for row i of the region (0-based), u from the stream w1 = i, w3 = ch 2^40; w[k] = theta[k] L[i, k];
+ *     cum[k] = cum[k-1] + w[k] (cum[-1] = 0); eps = the first k with cum[k] > u cum[K-1]; if there is none the last k with
+ *     w[k] > 0, else the last k with L[i, k] > 0, else 0.  Then n[k] = #{i: eps[i] = k}.
+ *   kept iterations: theta goes to theta_samples[r, ch, t - n_adapt - n_burn, .] (DEVICE, optional), is added to
+ *   theta_sum[r, ch, .] (sequentially in t, from 0), and freq[row, eps] += 1 (DEVICE int32 [rows x K], all chains together).
+ *   A region without cells: NaN theta_sum and theta_samples, nothing else.
+ *   A cell with exactly one L > 0 has the same eps whatever theta and u are; it is counted once and never visited.
+ *   ICNV_BAYES_DECIDED=0 (environment) visits every cell instead: the output is identical.
+ * Limits: 2 <= K <= 8 (more: ICNV_ERR_UNSUPPORTED), tau > 0, indices in range: ICNV_ERR_ARG before any launch.  Synchronises. */
+#define ICNV_BAYES_GAMMA_ATTEMPTS 64
+int icnv_bayes_loglik_dev(const double *expr, int64_t G, int64_t C, int64_t ld, const int32_t *gene_start, const int32_t *gene_count,
+                          const int32_t *cell_idx, const int64_t *cell_off, int32_t n_regions, int32_t K, const double *mu,
+                          const double *tau, double *ll, double *L, void *stream);
+/* The same with a HOST matrix (ld = G) and HOST outputs. */
+int icnv_bayes_loglik(const double *expr, int64_t G, int64_t C, const int32_t *gene_start, const int32_t *gene_count,
+                      const int32_t *cell_idx, const int64_t *cell_off, int32_t n_regions, int32_t K, const double *mu, const double *tau,
+                      double *ll, double *L);
+int icnv_bayes_sample_dev(const double *L, const int64_t *cell_off, const uint64_t *token, int32_t n_regions, int32_t K, int32_t n_adapt,
+                          int32_t n_burn, int32_t n_keep, uint64_t seed, double *theta_sum, double *theta_samples, int32_t *freq,
+                          void *stream);
+/* The same with HOST L and HOST outputs. */
+int icnv_bayes_sample(const double *L, const int64_t *cell_off, const uint64_t *token, int32_t n_regions, int32_t K, int32_t n_adapt,
+                      int32_t n_burn, int32_t n_keep, uint64_t seed, double *theta_sum, double *theta_samples, int32_t *freq);
+/* Counters since the last reset: out[0] sample calls, [1] regions, [2] (region, cell) rows, [3] undecided rows, [4] regions
+ * sampled from LDS (<= 512 undecided cells), [5] regions streamed, [6] wall microseconds of the sample calls, [7] of the
+ * likelihood calls. */
+int icnv_bayes_stats(int64_t *out, int32_t n);
+void icnv_bayes_stats_reset(void);
 
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for

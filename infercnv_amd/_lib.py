@@ -67,6 +67,7 @@ _ip = ct.POINTER(ct.c_int32)
 _dp = ct.POINTER(ct.c_double)
 _u32, _u64 = ct.c_uint32, ct.c_uint64
 _u64p = ct.POINTER(ct.c_uint64)
+_i64p = ct.POINTER(ct.c_int64)
 
 # name -> (restype, argtypes); every symbol include/icnv.h declares
 PROTOTYPES = {
@@ -143,6 +144,12 @@ PROTOTYPES = {
     "icnv_mask_non_de": (ct.c_int, [_vp, _i64, _i64, _vp, _i32, _dbl, _ip, _ip, _ip, _i32, _i32, _i32, _dbl, _vp, _dp]),
     "icnv_de_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_de_stats_reset": (None, []),
+    "icnv_bayes_loglik_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _ip, _ip, _i64p, _i32, _i32, _dp, _dp, _vp, _vp, _vp]),
+    "icnv_bayes_loglik": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _ip, _i64p, _i32, _i32, _dp, _dp, _vp, _vp]),
+    "icnv_bayes_sample_dev": (ct.c_int, [_vp, _i64p, _u64p, _i32, _i32, _i32, _i32, _i32, _u64, _vp, _vp, _vp, _vp]),
+    "icnv_bayes_sample": (ct.c_int, [_vp, _i64p, _u64p, _i32, _i32, _i32, _i32, _i32, _u64, _vp, _vp, _vp]),
+    "icnv_bayes_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_bayes_stats_reset": (None, []),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

@@ -158,3 +158,26 @@ def generate_cnv_region_reports(infercnv_obj: InfercnvObject, output_filename_pr
         for i in range(n):
             fh.write(f"{genes[i]}\t{np.asarray(go.chr)[i]}\t{_fmt(st[i])}\t{_fmt(sp[i])}\n")
     return cnv_regions
+
+
+def adjust_genes_regions_report(mcmc_obj, input_filename_prefix, output_filename_prefix, out_dir):
+    """adjust_genes_regions_report (R/inferCNV_HMM.R:891-963): the step-17 reports <input prefix>.pred_cnv_genes.dat and
+    .pred_cnv_regions.dat restricted to the regions the Bayesian filter kept (mcmc_obj.cell_gene), their state column
+    replaced by the region's state after the filter, written under the output prefix.  Every other field passes through
+    as text."""
+    new_state = {str(cg["cnv_regions"]): cg["State"] for cg in mcmc_obj.cell_gene}
+    for suffix, name_col in ((".pred_cnv_genes.dat", "gene_region_name"), (".pred_cnv_regions.dat", "cnv_name")):
+        src = os.path.join(out_dir, input_filename_prefix + suffix)
+        if not os.path.exists(src):
+            raise FileNotFoundError(f"Cannot find and adjust the following file. {src}")
+        with open(src) as fh:
+            lines = fh.read().splitlines()
+        header = lines[0].split("\t")
+        i_name, i_state = header.index(name_col), header.index("state")
+        with open(os.path.join(out_dir, output_filename_prefix + suffix), "w") as fh:
+            fh.write(lines[0] + "\n")
+            for ln in lines[1:]:
+                f = ln.split("\t")
+                if f[i_name] in new_state:
+                    f[i_state] = _fmt(new_state[f[i_name]])
+                    fh.write("\t".join(f) + "\n")

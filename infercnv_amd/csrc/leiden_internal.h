@@ -5,6 +5,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "lib_math.h"
+
 namespace icnv {
 
 constexpr int LEIDEN_MAX_K = 128;          // larger k: ICNV_ERR_UNSUPPORTED (K8's own limit)
@@ -17,25 +19,6 @@ __host__ __device__ constexpr int64_t leiden_move_cap(int64_t n) { return 256 * 
 enum { LEIDEN_OK = 0, LEIDEN_MOVE_CAP = 1, LEIDEN_LEVEL_CAP = 2, LEIDEN_INTERNAL = 3 };
 // per-problem counters (int64) written by leiden_kernel
 enum { LEIDEN_CNT_LEVELS = 0, LEIDEN_CNT_MOVE = 1, LEIDEN_CNT_REFINE = 2, LEIDEN_CNT_DRAWS = 3, LEIDEN_CNT_N = 4 };
-
-// exp_lib(x), the library's own exp: separately rounded operations in a fixed order (the files that use it are built with
-// -ffp-contract=off), restated operation by operation in tests/leiden_restate.py (x >= 0) and tests/de_restate.py.
-//   k = floor(x * (1/ln2) + 0.5);  t = (x - k * ln2_hi) - k * ln2_lo;  p = Horner of sum_{j<=11} t^j / j!;  ldexp(p, k)
-// x > 709 (and NaN) gives +inf: the threshold keeps p * 2^k finite (k <= 1023, p < 1).  x < -708 gives 0 (K12's pnorm and pt;
-// K11 only passes x >= 0): from -708 on, k >= -1021 and p * 2^k stays a normal number.
-constexpr double LEIDEN_EXP_MAX = 709.0;
-constexpr double LEIDEN_EXP_MIN = -708.0;
-__host__ __device__ inline double leiden_exp_lib(double x) {
-    if (!(x <= LEIDEN_EXP_MAX)) return INFINITY;
-    if (x < LEIDEN_EXP_MIN) return 0.0;
-    const double kd = floor(x * 1.4426950408889634 + 0.5);
-    const double t = (x - kd * 6.93147180369123816490e-01) - kd * 1.90821492927058770002e-10;
-    const double c[12] = {1.0, 1.0, 1.0 / 2, 1.0 / 6, 1.0 / 24, 1.0 / 120, 1.0 / 720, 1.0 / 5040, 1.0 / 40320, 1.0 / 362880,
-                          1.0 / 3628800, 1.0 / 39916800};
-    double p = c[11];
-    for (int j = 10; j >= 0; --j) p = p * t + c[j];
-    return ldexp(p, (int)kd);
-}
 
 struct LeidenGraph {              // the graphs of a batch: problem p's nodes at node_off[p], its CSR offsets at node_off[p] + p
     const int32_t *nn;            // (sum n_p) x k, positions within the problem

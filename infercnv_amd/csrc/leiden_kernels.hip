@@ -360,7 +360,7 @@ __device__ int64_t refine(const Level &L, int64_t N, int64_t K, double r, double
             double bd = 0.0;
             int32_t bord = -1, best = v;
             int64_t nc = 1;
-            if (lane_id() == 0) { P.cands[0] = v; P.cum[0] = leiden_exp_lib(0.0 / beta); }
+            if (lane_id() == 0) { P.cands[0] = v; P.cum[0] = lib_exp(0.0 / beta); }
             for (int64_t b = 0; b < d; b += LD_WAVE) {
                 const int64_t t = b + lane_id();
                 bool f = false;
@@ -377,7 +377,7 @@ __device__ int64_t refine(const Level &L, int64_t N, int64_t K, double r, double
                     if ((double)P.ext[D] >= ((WD * (double)(T - P.Wr[D])) * r)) {
                         const double dd = (double)P.acc[D] - ((dwv * WD) * r);
                         if (dd > bd) { bd = dd; bord = (int32_t)j; best = D; }
-                        if (dd >= 0) term = leiden_exp_lib(dd / beta);
+                        if (dd >= 0) term = lib_exp(dd / beta);
                     }
                     P.cands[j] = D;
                     P.cum[j] = term;

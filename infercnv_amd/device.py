@@ -645,6 +645,73 @@ def de_stats(reset=False):
     return dict(zip(DE_STATS, (int(v) for v in out)))
 
 
+def _bayes_offsets(regions_cells):
+    off = np.zeros(len(regions_cells) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(c) for c in regions_cells])
+    return off, off.ctypes.data_as(ct.POINTER(ct.c_int64))
+
+
+def bayes_loglik(x, regions, mu, tau):
+    """The likelihood pass of the mixture model of the predicted CNV regions (icnv_bayes_loglik_dev, DESIGN K13).  x: (C, G)
+    CUDA float64 matrix with contiguous rows; regions: list of (first gene, gene count, 0-based cell index vector); mu, tau:
+    the K state means and precisions.  Returns (ll, L, cell_off): CUDA float64 (rows, K) tensors -- region r's cells are the
+    rows cell_off[r] .. cell_off[r + 1] - 1 -- with L = exp_lib(ll - its row maximum).  Synchronises the device."""
+    L_ = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    K = len(mu)
+    g0, g0p = i32([r[0] for r in regions])
+    ng, ngp = i32([r[1] for r in regions])
+    off, offp = _bayes_offsets([r[2] for r in regions])
+    cidx = (np.concatenate([np.asarray(r[2], dtype=np.int32).ravel() for r in regions]) if len(regions) else np.zeros(0, dtype=np.int32))
+    cidx, cp = i32(cidx if cidx.size else np.zeros(1, dtype=np.int32))
+    m, mp = f64(mu)
+    t, tp = f64(tau)
+    rows = int(off[-1])
+    ll = torch.empty((rows, K), dtype=torch.float64, device=x.device)
+    Lk = torch.empty_like(ll)
+    check(L_.icnv_bayes_loglik_dev(_ptr(x), G, C, ld, g0p, ngp, cp, offp, len(regions), K, mp, tp, _ptr(ll), _ptr(Lk), _stream()))
+    return ll, Lk, off
+
+
+def bayes_sample(L, cell_off, tokens, n_adapt=500, n_burn=200, n_keep=1000, seed=0, want_samples=False):
+    """The Gibbs sampler of every region's mixture model in one call (icnv_bayes_sample_dev, DESIGN K13): K chains per region,
+    n_adapt + n_burn discarded and n_keep kept iterations.  L, cell_off: as bayes_loglik returns them; tokens: one uint64
+    per region (fnv1a64 of its name).  Returns (theta_sum (R, K, K) float64: per chain the sum of its kept theta,
+    theta_samples (R, K, n_keep, K) or None, freq (rows, K) int32: how often each cell was in each state over all chains).
+    Synchronises the device."""
+    L_ = _lib.load()
+    if not (isinstance(L, torch.Tensor) and L.is_cuda and L.dtype == torch.float64 and L.dim() == 2 and L.is_contiguous()):
+        raise TypeError("L must be a contiguous (rows, K) CUDA float64 tensor")
+    K = L.shape[1]
+    off = np.ascontiguousarray(cell_off, dtype=np.int64)
+    R = off.size - 1
+    if int(off[-1]) != L.shape[0]:
+        raise ValueError("cell_off does not match the rows of L")
+    tok, tokp = _u64(tokens)
+    if tok.size != R:
+        raise ValueError("one token per region")
+    theta_sum = torch.empty((R, K, K), dtype=torch.float64, device=L.device)
+    samples = torch.empty((R, K, int(n_keep), K), dtype=torch.float64, device=L.device) if want_samples else None
+    freq = torch.empty((L.shape[0], K), dtype=torch.int32, device=L.device)
+    check(L_.icnv_bayes_sample_dev(_ptr(L), off.ctypes.data_as(ct.POINTER(ct.c_int64)), tokp, R,
+                                   K, int(n_adapt), int(n_burn), int(n_keep), int(seed) & (2**64 - 1), _ptr(theta_sum), _ptr(samples),
+                                   _ptr(freq), _stream()))
+    return theta_sum, samples, freq
+
+
+BAYES_STATS = ("calls", "regions", "rows", "undecided_rows", "regions_lds", "regions_streamed", "us", "loglik_us")
+
+
+def bayes_stats(reset=False):
+    """icnv_bayes_stats as a dict (`us` / `loglik_us`: wall microseconds of the sample / likelihood calls); reset=True zeroes it."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(BAYES_STATS))()
+    check(L.icnv_bayes_stats(out, len(BAYES_STATS)))
+    if reset:
+        L.icnv_bayes_stats_reset()
+    return dict(zip(BAYES_STATS, (int(v) for v in out)))
+
+
 def state_consensus(states, groups, overwrite=False):
     """.get_state_consensus (R/inferCNV_HMM.R:977-987) per group -> (n_groups, G) uint8; with
     overwrite=True also returns the state matrix with every member cell set to its group's consensus."""
