@@ -749,6 +749,52 @@ int icnv_bayes_sample(const double *L, const int64_t *cell_off, const uint64_t *
 int icnv_bayes_stats(int64_t *out, int32_t n);
 void icnv_bayes_stats_reset(void);
 
+/* ---- per-cell CNV features and run-length segmentation (K14) -------------------------------------------------------------
+ * The numbers behind add_to_seurat's map_metadata_from_infercnv.txt (.get_features, R/seurat_interaction.R:244-353) and the
+ * segmentation of state columns into CNV regions (.define_cnv_gene_regions, R/inferCNV_HMM.R:1005-1057, called per cell
+ * group by get_predicted_CNV_regions, :706-764).  DESIGN.md section 4 K14, restated in tests/cnv_summary_restate.py.
+ * states: uint8, element (gene g, column c) at states[c * ld + g], ld >= G (a leading dimension that is a multiple of 16 on a
+ * 16-byte aligned base is read with 16-byte loads); chr_start: HOST, n_chr + 1 entries from 0 to G, non-decreasing (the
+ * kernels see contiguous chromosomes only).  A chromosome of fewer than two genes never appears in a report
+ * (R/inferCNV_HMM.R:1013): it counts nothing, produces no run and does not advance the region counter.
+ * icnv_cnv_features: per (chromosome k, column c) four int32 at counts[(k * C + c) * 4 ..] (DEVICE and 16-byte aligned in the
+ *   _dev flavour, else ICNV_ERR_ARG: a group of four is stored at once):
+ *   n_loss = #{genes of k with state < s0}, n_gain = #{state > s0}, d_loss = sum of s0 - state over the former, d_gain = sum
+ *   of state - s0 over the latter.  s0 is the centre state (3 for i6, 2 for i3).  The nine features of the reference are
+ *   has_loss = n_loss > 0, has_dupli = n_gain > 0, has_cnv = n_loss + n_gain > 0, proportion_loss = n_loss / n_k,
+ *   proportion_dupli = n_gain / n_k, proportion_cnv = (n_loss + n_gain) / n_k and, for i6, proportion_scaled_loss =
+ *   d_loss / (2 n_k), _dupli = d_gain / (2 n_k), _cnv = (d_loss + d_gain) / (2 n_k): one correctly rounded division each.
+ *   The reference's reports hold a cell group's CONSENSUS state, so in group mode the columns passed here are the consensus
+ *   columns of icnv_state_consensus and the caller broadcasts the result to the member cells; groups must not overlap.
+ *   run_counts (nullable; DEVICE in the _dev flavour): per column c, run_counts[2 c] = runs of equal states within the
+ *   chromosomes of two or more genes (a run ends at a chromosome border whatever the states are), run_counts[2 c + 1] =
+ *   those whose state is not s0.  Every byte of the matrix must be a state 1 .. K (2 <= K <= 7): any other byte, the
+ *   library's 0xFF "invalid" included, gives ICNV_ERR_ARG and no number.
+ * icnv_cnv_runs: the runs themselves.  col_idx (HOST, nullable = every column in order): the columns to visit, in report order
+ *   (by cell that is reference groups first, then observation groups, R/inferCNV_HMM.R:713-733).  One record per run whose
+ *   state is not `neutral` (neutral = 0: every run), ordered by (list position, gene), as six int32 arrays of `capacity`
+ *   entries each, records[f * capacity + r]: f = 0 list position, 1 chromosome index, 2 first gene, 3 last gene (0-based,
+ *   inclusive), 4 state, 5 ordinal = the 1-based counter of "<chr>-region_<k>": it counts neutral runs too and runs on across
+ *   the list.  *n_records receives the number of records, *n_runs (nullable) the number of runs of every state.
+ *   records = NULL is the count-only call.  capacity < *n_records: ICNV_ERR_ARG, nothing written.  run_counts (_dev, DEVICE
+ *   [2 C], nullable): receives the per-column counts; with counts_valid != 0 it holds them already (from icnv_cnv_features_dev
+ *   with s0 = neutral, or from the count-only call) and the counting pass is skipped.  K = 0: bytes are compared as they
+ *   are (0xFF is a state like any other); K >= 1: as above, ICNV_ERR_ARG for a byte outside 1 .. K.
+ *   Ties between regions of equal gene count are not decided here: infercnv_amd/seurat_interaction.py orders them by the
+ *   bytes of the region name ("chr1-region_9" before "chr10-region_2"), where the reference's order depends on R's locale.
+ * Both synchronise. */
+int icnv_cnv_features_dev(const uint8_t *states, int64_t G, int64_t C, int64_t ld, const int32_t *chr_start, int32_t n_chr, int32_t K,
+                          int32_t s0, int32_t *counts, int32_t *run_counts, void *stream);
+/* The same with a HOST matrix (ld = G) and HOST outputs. */
+int icnv_cnv_features(const uint8_t *states, int64_t G, int64_t C, const int32_t *chr_start, int32_t n_chr, int32_t K, int32_t s0,
+                      int32_t *counts, int32_t *run_counts);
+int icnv_cnv_runs_dev(const uint8_t *states, int64_t G, int64_t C, int64_t ld, const int32_t *chr_start, int32_t n_chr,
+                      const int32_t *col_idx, int64_t n_cols, int32_t K, int32_t neutral, int32_t *run_counts, int32_t counts_valid,
+                      int64_t capacity, int32_t *records, int64_t *n_records, int64_t *n_runs, void *stream);
+/* The same with a HOST matrix (ld = G) and HOST records. */
+int icnv_cnv_runs(const uint8_t *states, int64_t G, int64_t C, const int32_t *chr_start, int32_t n_chr, const int32_t *col_idx,
+                  int64_t n_cols, int32_t K, int32_t neutral, int64_t capacity, int32_t *records, int64_t *n_records, int64_t *n_runs);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

@@ -1,8 +1,8 @@
 """CNV region / consensus reporting (second "next" row): host-side mirror of
 get_predicted_CNV_regions, .define_cnv_gene_regions, .get_cnv_gene_region_bounds and
 generate_cnv_region_reports (R/inferCNV_HMM.R:706-869, 1005-1087).  The per-gene consensus over a
-group's cells (.get_state_consensus, :977-987) runs on the GPU (icnv_state_consensus); the run-length
-segmentation and the four report files are tiny and stay on the host, in the reference's formats.
+group's cells (.get_state_consensus, :977-987) and the run-length segmentation run on the GPU (icnv_state_consensus,
+icnv_cnv_runs); the four report files are written on the host, in the reference's formats.
 """
 from __future__ import annotations
 
@@ -21,17 +21,21 @@ def _states_u8(obj):
     return np.asfortranarray(np.where(st < 0, 255, st).astype(np.uint8))
 
 
-def state_consensus(infercnv_obj: InfercnvObject, groups):
-    """(G, n_groups) consensus states (float, -1 where the consensus is the invalid state)."""
+def _consensus_u8(st, groups):
+    """(G, n_groups) uint8 consensus of the (G, C) uint8 state matrix (icnv_state_consensus)."""
     L = _lib.load()
-    st = _states_u8(infercnv_obj)
     G, C = st.shape
     idx, off = pack_groups(groups)
     idx, ip = i32(idx)
     off, op = i32(off)
     cons = np.empty((G, len(groups)), dtype=np.uint8, order="F")
-    check(L.icnv_state_consensus(st.ctypes.data_as(ct.c_void_p), G, C, ip, op, len(groups),
-                                 cons.ctypes.data_as(ct.c_void_p), None))
+    check(L.icnv_state_consensus(st.ctypes.data_as(ct.c_void_p), G, C, ip, op, len(groups), cons.ctypes.data_as(ct.c_void_p), None))
+    return cons
+
+
+def state_consensus(infercnv_obj: InfercnvObject, groups):
+    """(G, n_groups) consensus states (float, -1 where the consensus is the invalid state)."""
+    cons = _consensus_u8(_states_u8(infercnv_obj), groups)
     out = cons.astype(np.float64)
     out[cons == 255] = -1.0
     return out
@@ -83,32 +87,90 @@ def _cell_groups(obj, by):
     raise ValueError("by must be one of consensus, subcluster, cell")
 
 
+def _range_reduce(ufunc, a, first, last):
+    """ufunc.reduce(a[first[i] : last[i] + 1]) for every i, without a loop."""
+    if first.size == 0:
+        return a[:0]
+    idx = np.empty(2 * first.size, dtype=np.int64)
+    idx[0::2], idx[1::2] = first, last + 1
+    return ufunc.reduceat(np.concatenate([a, a[-1:]]), idx)[0::2]
+
+
+def predicted_cnv_runs(infercnv_obj: InfercnvObject, by="consensus", neutral=0, K=0):
+    """The run-length segmentation of get_predicted_CNV_regions (R/inferCNV_HMM.R:706-764 with .define_cnv_gene_regions,
+    :1005-1057) as arrays, from the device (icnv_cnv_runs): one record per run of equal states within a chromosome whose state
+    is not `neutral` (0: every run), ordered by (cell group in report order, gene).  Group modes segment the groups' consensus
+    states (icnv_state_consensus); by = "cell" segments the cells' own columns in report order -- reference groups, then
+    observation groups -- without a consensus.  Returns a dict: groups [(name, 0-based cell indices)], chr_names (order of
+    first appearance), chr_start, perm (the gene gather of chr_layout(), or None), n_runs (runs of every state: the last
+    region counter), and per record the arrays col (index into groups), chr (index into chr_names), gene_first / gene_last
+    (positions in the gathered gene order, inclusive), state (-1: the invalid state), ordinal, name ("<chr>-region_<ordinal>"),
+    start / end (min start / max stop over the run's genes).  K > 0 refuses states outside 1 .. K with ValueError."""
+    L = _lib.load()
+    groups = _cell_groups(infercnv_obj, by)
+    by_cell = by == "cell" and infercnv_obj.tumor_subclusters is not None
+    perm, chr_start = infercnv_obj.chr_layout()
+    chrs = np.asarray(infercnv_obj.gene_order.chr)
+    n = chrs.size
+    start = np.asarray(infercnv_obj.gene_order.start) if infercnv_obj.gene_order.start is not None else np.arange(n)
+    stop = np.asarray(infercnv_obj.gene_order.stop) if infercnv_obj.gene_order.stop is not None else np.arange(n)
+    st = _states_u8(infercnv_obj)
+    if perm is not None:                                   # the kernels see contiguous chromosomes only
+        st, chrs, start, stop = np.asfortranarray(st[perm]), chrs[perm], start[perm], stop[perm]
+    chr_names = chrs[chr_start[:-1]]                       # chr_layout() yields no empty chromosome
+    if by_cell:
+        # what the consensus over one cell gave before: a byte outside 1 .. 6 is the invalid state (reported as -1)
+        mat = np.asfortranarray(np.where((st >= 1) & (st <= 6), st, 255).astype(np.uint8))
+        col_idx, cp = i32(np.concatenate([g for _, g in groups]) if groups else np.zeros(0, dtype=np.int32))
+        n_cols = col_idx.size
+    else:
+        mat = _consensus_u8(st, [g for _, g in groups])
+        col_idx, cp, n_cols = None, None, len(groups)
+    G, C = mat.shape
+    cs, csp = i32(chr_start)
+    n_rec, n_runs = ct.c_int64(), ct.c_int64()
+
+    def call(cap, rec):
+        rc = L.icnv_cnv_runs(mat.ctypes.data_as(ct.c_void_p), G, C, csp, cs.size - 1, cp, n_cols, int(K), int(neutral), cap,
+                             rec.ctypes.data_as(ct.c_void_p) if rec is not None else None, ct.byref(n_rec), ct.byref(n_runs))
+        if rc == _lib.ERR_ARG:
+            raise ValueError(L.icnv_last_error().decode("utf-8", "replace"))
+        check(rc)
+
+    rec = np.zeros((6, 0), dtype=np.int32)
+    if C and n_cols:
+        call(0, None)
+        rec = np.empty((6, max(n_rec.value, 1)), dtype=np.int32)
+        call(rec.shape[1], rec)
+        rec = rec[:, :n_rec.value]
+    col, chr_i, first, last, state, ordinal = (rec[k].astype(np.int64) for k in range(6))
+    state = np.where(state == 255, -1, state)
+    names = [f"{chr_names[c]}-region_{o}" for c, o in zip(chr_i, ordinal)]
+    return {"groups": groups, "chr_names": chr_names, "chr_start": chr_start, "perm": perm, "n_runs": n_runs.value,
+            "col": col, "chr": chr_i, "gene_first": first, "gene_last": last, "state": state, "ordinal": ordinal, "name": names,
+            "start": _range_reduce(np.minimum, start, first, last), "end": _range_reduce(np.maximum, stop, first, last)}
+
+
 def get_predicted_CNV_regions(infercnv_obj: InfercnvObject, by="consensus"):
     """R/inferCNV_HMM.R:706-764.  Returns a list of dicts {cell_group_name, cells, gene_regions, cnv_ranges};
-    gene_regions = ordered list of (region name, dict(state, gene idx array, chr, start, end arrays))."""
-    groups = _cell_groups(infercnv_obj, by)
-    cons = state_consensus(infercnv_obj, [g for _, g in groups])
-    chrs = np.asarray(infercnv_obj.gene_order.chr)
-    start = np.asarray(infercnv_obj.gene_order.start) if infercnv_obj.gene_order.start is not None else np.arange(chrs.size)
-    stop = np.asarray(infercnv_obj.gene_order.stop) if infercnv_obj.gene_order.stop is not None else np.arange(chrs.size)
-    _, first = np.unique(chrs, return_index=True)
-    chr_order = chrs[np.sort(first)]
+    gene_regions = ordered list of (region name, dict(state, gene idx array, chr, start, end arrays)).  Built from the run
+    records of predicted_cnv_runs (every run, the neutral ones included)."""
+    runs = predicted_cnv_runs(infercnv_obj, by)
+    perm = runs["perm"]
+    n = np.asarray(infercnv_obj.gene_order.chr).size
+    start = np.asarray(infercnv_obj.gene_order.start) if infercnv_obj.gene_order.start is not None else np.arange(n)
+    stop = np.asarray(infercnv_obj.gene_order.stop) if infercnv_obj.gene_order.stop is not None else np.arange(n)
     cells = infercnv_obj.cells()
+    bounds = np.searchsorted(runs["col"], np.arange(len(runs["groups"]) + 1))
     out = []
-    counter = 0
-    for gi, (name, idx) in enumerate(groups):
+    for gi, (name, idx) in enumerate(runs["groups"]):
         regions = []
-        for c in chr_order:                                   # .define_cnv_gene_regions (:1005-1057)
-            gene_idx = np.nonzero(chrs == c)[0]
-            if gene_idx.size < 2:
-                continue
-            states = cons[gene_idx, gi]
-            cuts = np.concatenate([[0], np.nonzero(states[1:] != states[:-1])[0] + 1, [gene_idx.size]])
-            for a, b in zip(cuts[:-1], cuts[1:]):
-                counter += 1
-                rows = gene_idx[a:b]
-                regions.append((f"{c}-region_{counter}",
-                                {"state": float(states[a]), "gene": rows, "chr": c, "start": start[rows], "end": stop[rows]}))
+        for r in range(bounds[gi], bounds[gi + 1]):
+            rows = np.arange(runs["gene_first"][r], runs["gene_last"][r] + 1)
+            if perm is not None:
+                rows = perm[rows]
+            regions.append((runs["name"][r], {"state": float(runs["state"][r]), "gene": rows, "chr": runs["chr_names"][runs["chr"][r]],
+                                              "start": start[rows], "end": stop[rows]}))
         ranges = [(rn, r["state"], r["chr"], r["start"].min(), r["end"].max()) for rn, r in regions]   # :1071-1087
         out.append({"cell_group_name": name, "cells": cells[idx], "gene_regions": regions, "cnv_ranges": ranges})
     return out

@@ -726,6 +726,71 @@ def state_consensus(states, groups, overwrite=False):
     return (cons, out) if overwrite else cons
 
 
+def _chr_start(chr_start, G):
+    cs, cp = i32(chr_start)
+    if cs.ndim != 1 or cs.size < 2 or cs[0] != 0 or cs[-1] != G:
+        raise ValueError("chr_start must run from 0 to the gene count")
+    return cs, cp
+
+
+def cnv_features(states, chr_start, K, s0, want_run_counts=False):
+    """The four integers behind add_to_seurat's per-chromosome features (icnv_cnv_features_dev; .get_features,
+    R/seurat_interaction.R:244-353): states (columns, G) uint8, rows `ld` apart -> int32 (n_chr, columns, 4) tensor of n_loss,
+    n_gain, d_loss, d_gain; with want_run_counts also the (columns, 2) int32 tensor of runs / non-neutral runs per column.
+    ValueError when a byte is outside 1 .. K."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(states, torch.uint8)
+    cs, cp = _chr_start(chr_start, G)
+    counts = torch.empty((cs.size - 1, C, 4), dtype=torch.int32, device=states.device)
+    runs = torch.empty((C, 2), dtype=torch.int32, device=states.device)
+    rc = L.icnv_cnv_features_dev(_ptr(states), G, C, ld, cp, cs.size - 1, int(K), int(s0), _ptr(counts), _ptr(runs), _stream())
+    if rc == _lib.ERR_ARG:
+        raise ValueError(L.icnv_last_error().decode("utf-8", "replace"))
+    check(rc)
+    return (counts, runs) if want_run_counts else counts
+
+
+CNV_RUN_FIELDS = ("col", "chr", "gene_first", "gene_last", "state", "ordinal")
+
+
+def cnv_runs(states, chr_start, neutral=0, K=0, col_idx=None, run_counts=None):
+    """Run-length segmentation of state columns into CNV regions (icnv_cnv_runs_dev; .define_cnv_gene_regions,
+    R/inferCNV_HMM.R:1005-1057): one record per run whose state is not `neutral` (0: every run), ordered by (position in
+    col_idx, gene) -> (records, n_runs): records an int32 (6, n) tensor in the order of CNV_RUN_FIELDS (`col` is the position
+    in col_idx, `ordinal` the 1-based counter of the region name), n_runs the number of runs of every state.  run_counts:
+    the (columns, 2) tensor cnv_features returned for s0 == neutral, which saves the counting pass.  K > 0 refuses bytes
+    outside 1 .. K with ValueError."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(states, torch.uint8)
+    cs, cp = _chr_start(chr_start, G)
+    if col_idx is None:
+        idx, ip, n_cols = None, None, C
+    else:
+        idx, ip = i32(col_idx)
+        n_cols = idx.size
+    have = run_counts is not None
+    if not have:
+        run_counts = torch.empty((C, 2), dtype=torch.int32, device=states.device)
+    n_rec, n_runs = ct.c_int64(), ct.c_int64()
+
+    def call(valid, cap, rec):
+        rc = L.icnv_cnv_runs_dev(_ptr(states), G, C, ld, cp, cs.size - 1, ip, n_cols, int(K), int(neutral), _ptr(run_counts), valid,
+                                 cap, _ptr(rec), ct.byref(n_rec), ct.byref(n_runs), _stream())
+        if rc == _lib.ERR_ARG:
+            raise ValueError(L.icnv_last_error().decode("utf-8", "replace"))
+        check(rc)
+
+    if not have:
+        call(0, 0, None)                                    # the count-only call fills run_counts
+    else:
+        n_rec.value = int(run_counts[:, 1].sum().item()) if idx is None else int(
+            run_counts[torch.as_tensor(idx.astype(np.int64), device=states.device), 1].sum().item())
+    cap = n_rec.value
+    rec = torch.empty((6, max(cap, 1)), dtype=torch.int32, device=states.device)
+    call(1, max(cap, 1), rec)
+    return rec[:, :n_rec.value], n_runs.value
+
+
 def states_to_proxy(states, K):
     """assign_HMM_states_to_proxy_expr_vals (R/inferCNV_HMM.R:1191-1206) / i3 (R/inferCNV_i3HMM.R:405-417)."""
     L = _lib.load()

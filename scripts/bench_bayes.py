@@ -43,24 +43,15 @@ def timed(fn, reps):
 
 def predicted_regions(states, groups, chr_start, neutral):
     """Run-length segmentation per (group, chromosome) of the group's state row (the group HMM gives every cell of a group the
-    same states): (first gene, gene count, cells) and a name per non-neutral run."""
+    same states) on the device (icnv_cnv_runs_dev): (first gene, gene count, cells) and a name per non-neutral run -- this
+    script's own names, which number the non-neutral runs only."""
     first = torch.as_tensor(np.array([int(g[0]) for g in groups]), device=states.device)
-    rows = states[first].cpu().numpy()
-    regions, names, hmm_state = [], [], []
-    for q, g in enumerate(groups):
-        cells = np.sort(np.asarray(g, dtype=np.int32))
-        for c in range(len(chr_start) - 1):
-            a, b = int(chr_start[c]), int(chr_start[c + 1])
-            if b - a < 2:
-                continue
-            s = rows[q, a:b]
-            cuts = np.concatenate([[0], np.nonzero(s[1:] != s[:-1])[0] + 1, [b - a]])
-            for u, v in zip(cuts[:-1], cuts[1:]):
-                if s[u] != neutral:
-                    regions.append((a + int(u), int(v - u), cells))
-                    names.append(f"chr{c + 1}-region_{len(names) + 1}")
-                    hmm_state.append(int(s[u]))
-    return regions, names, hmm_state
+    rec, _ = device.cnv_runs(states[first].contiguous(), chr_start, neutral=neutral)
+    rec = rec.cpu().numpy()
+    cells = [np.sort(np.asarray(g, dtype=np.int32)) for g in groups]
+    regions = [(int(a), int(b - a + 1), cells[q]) for q, a, b in zip(rec[0], rec[2], rec[3])]
+    names = [f"chr{c + 1}-region_{i + 1}" for i, c in enumerate(rec[1])]
+    return regions, names, [int(v) for v in rec[4]]
 
 
 def sampler_case(L, off, tokens, sched, reps, K):
