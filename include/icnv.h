@@ -795,6 +795,59 @@ int icnv_cnv_runs_dev(const uint8_t *states, int64_t G, int64_t C, int64_t ld, c
 int icnv_cnv_runs(const uint8_t *states, int64_t G, int64_t C, const int32_t *chr_start, int32_t n_chr, const int32_t *col_idx,
                   int64_t n_cols, int32_t K, int32_t neutral, int64_t capacity, int32_t *records, int64_t *n_records, int64_t *n_runs);
 
+/* ---- hidden spike-in of the i6 HMM (K15) ---------------------------------------------------------------------------------
+ * .build_and_add_hspike (R/inferCNV_hidden_spike.R:3-165, step 3 of run()): the per-group gene tables the two smoothing
+ * splines are fitted to, and the simulation of the normal and CNV-spiked cells from them.  The splines themselves are fitted
+ * on the host (infercnv_amd/smooth_spline.py).  R's draws are unseeded, so the library owns a documented Philox stream.
+ * DESIGN.md section 4 K15, restated in tests/hspike_restate.py.
+ * icnv_group_gene_tables: .get_mean_var_table / .get_mean_vs_p0_table (R/inferCNV_meanVarSim.R:178-211,
+ *   R/inferCNV_simple_sim.R:100-154).  Groups: cell_idx / cell_off (HOST, int32, 0-based columns, cell_off[0] = 0, no group
+ *   empty; groups may overlap, cells in no group are never read).  Element (gene g, cell c) at expr[c * ld + g].  Outputs
+ *   [n_grp x G] (row q = group q): m = rowMeans, v = apply(, 1, var), nzero = sum(x == 0) (int32; -0 counts).  The arithmetic
+ *   is ICNV_DE_T's: m = correctly rounded sum / n (bit-equal to icnv_group_means_dev); v = (correctly rounded sum of
+ *   round(round(x - m)^2)) / (n - 1); n = 1 gives v = NaN as R's var does.  R's var accumulates in long double around a
+ *   long-double mean: it may differ from v in the last bits.  p0 = nzero / n is one division on the host.  A non-finite value
+ *   makes m and v of its (group, gene) non-finite by plain IEEE sums; their bits are not part of the contract.  Every
+ *   (group, cell) membership is read twice (sums, then squared deviations): disjoint groups read the matrix at most twice.
+ *   1 <= n_grp <= 65535, 1 <= G, C < 2^31: ICNV_ERR_ARG before any launch.  Synchronises.
+ * spline evaluation S(x) of (knots [nk + 4], coef [nk], nk >= 4, xmin, range): a cubic B-spline on the scaled abscissa
+ *   t = (x - xmin) / range with knots[0..3] = 0, knots[nk..nk+3] = 1 and knots[3..nk] strictly increasing.
+ *   t < 0: coef[0] + ((3 (coef[1] - coef[0])) / (knots[4] - knots[3])) t;
+ *   t > 1: coef[nk-1] + ((3 (coef[nk-1] - coef[nk-2])) / (knots[nk] - knots[nk-1])) (t - 1) -- the boundary value and the first
+ *   derivative in t, as predict.smooth.spline.fit extends linearly;
+ *   else i = the largest index in 3 .. nk - 1 with knots[i] <= t (bisection) and de Boor's recurrence on d[j] = coef[i - 3 + j]:
+ *   for r = 1, 2, 3: for j = 3 down to r: a = (t - knots[i-3+j]) / (knots[i+1+j-r] - knots[i-3+j]);
+ *   d[j] = ((1 - a) d[j-1]) + (a d[j]); S = d[3].  Every operation is rounded by itself, in this order.
+ * icnv_hspike_simulate: .get_simulated_cell_matrix_using_meanvar_trend_helper + .apply_dropout
+ *   (R/inferCNV_meanVarSim.R:23-55, 105-161) for n_mat matrices at once.  means [n_mat x n_genes] (HOST), tokens [n_mat] (HOST),
+ *   the variance spline S_var (log(v + 1) over log(m + 1)) and the dropout spline S_p0 (p0 over log(m)) (HOST arrays); out:
+ *   n_mat matrices of n_genes x num_cells, column-major, element (g, c) of matrix k at out[(k num_cells + c) n_genes + g]
+ *   (DEVICE in the _dev flavour).  Per gene row g with mean m: m <= 0: every value is 0.  Else logm = lib_log(m + 1),
+ *   var = max(lib_exp(S_var(logm)) - 1, 0), sd = sqrt(var); per cell c: u1, u2 = two .random() draws of NumPy's
+ *   Generator(Philox(key = [seed, token_k], counter = [0, g, c, 0])), z = lib_qnorm((floor(2^27 u1) + u2) / 2^27) (K12's normal
+ *   draw), w = m + sd z, val = rint(w > 0 ? w : 0) (R >= 4 rounds half to even).  Dropout of the row: sum = the sequential double
+ *   sum of val over c (exact below 2^53; means above 2^40 are refused), nz = #(val == 0); nz = num_cells: the row stays (R
+ *   divides by zero there: a deviation); p = S_p0(lib_log(sum / n)), padj = (p n - nz) / (n - nz); padj > 0: the element becomes 0
+ *   where u <= padj, u the first .random() draw of counter = [1, g, c, 0] (R draws for every element; with padj <= 0 nothing can
+ *   drop, so no draw is taken).  lib_log / lib_exp / lib_qnorm: csrc/lib_math.h.
+ *   ICNV_ERR_ARG with a message before any launch: nk < 4, a non-finite coefficient, xmin or range, range <= 0, knots that are
+ *   not as above, a non-finite mean, a mean above 2^40, n_mat outside 1 .. 65535.  Synchronises. */
+#define ICNV_HSPIKE_GENES_TOKEN 0x6873706B67656E65ull   /* "hspkgene": the stream of genes_means_use_idx (hidden_spike.py) */
+int icnv_group_gene_tables_dev(const double *expr, int64_t G, int64_t C, int64_t ld, const int32_t *cell_idx, const int32_t *cell_off,
+                               int32_t n_grp, double *m, double *v, int32_t *nzero, void *stream);
+/* The same with a HOST matrix (ld = G) and HOST outputs. */
+int icnv_group_gene_tables(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, const int32_t *cell_off, int32_t n_grp,
+                           double *m, double *v, int32_t *nzero);
+int icnv_hspike_simulate_dev(const double *means, int64_t n_genes, int32_t num_cells, int32_t n_mat, const double *var_knots,
+                             const double *var_coef, int32_t var_nk, double var_xmin, double var_range, const double *p0_knots,
+                             const double *p0_coef, int32_t p0_nk, double p0_xmin, double p0_range, uint64_t seed,
+                             const uint64_t *tokens, double *out, void *stream);
+/* The same with a HOST output. */
+int icnv_hspike_simulate(const double *means, int64_t n_genes, int32_t num_cells, int32_t n_mat, const double *var_knots,
+                         const double *var_coef, int32_t var_nk, double var_xmin, double var_range, const double *p0_knots,
+                         const double *p0_coef, int32_t p0_nk, double p0_xmin, double p0_range, uint64_t seed, const uint64_t *tokens,
+                         double *out);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

@@ -31,6 +31,7 @@ LEIDEN_CPM, LEIDEN_MODULARITY = 1, 2   # ICNV_LEIDEN_* objectives of icnv_leiden
 DE_WILCOXON, DE_T = 1, 2               # ICNV_DE_* tests of icnv_de_tests_dev
 DE_MASK_ANY, DE_MASK_MOST, DE_MASK_ALL = 0, 1, 2   # ICNV_DE_MASK_* rules of icnv_mask_non_de_dev
 DE_JITTER_TOKEN = 0x6E6F6E44456A6974   # ICNV_DE_JITTER_TOKEN: the jitter stream's second key word
+HSPIKE_GENES_TOKEN = 0x6873706B67656E65   # ICNV_HSPIKE_GENES_TOKEN: the stream of the hidden spike-in's genes_means_use_idx
 
 
 class IcnvError(RuntimeError):
@@ -154,6 +155,11 @@ PROTOTYPES = {
     "icnv_cnv_features": (ct.c_int, [_vp, _i64, _i64, _ip, _i32, _i32, _i32, _vp, _vp]),
     "icnv_cnv_runs_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _i32, _ip, _i64, _i32, _i32, _vp, _i32, _i64, _vp, _i64p, _i64p, _vp]),
     "icnv_cnv_runs": (ct.c_int, [_vp, _i64, _i64, _ip, _i32, _ip, _i64, _i32, _i32, _i64, _vp, _i64p, _i64p]),
+    "icnv_group_gene_tables_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _ip, _i32, _vp, _vp, _vp, _vp]),
+    "icnv_group_gene_tables": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp, _vp]),
+    "icnv_hspike_simulate_dev": (ct.c_int, [_dp, _i64, _i32, _i32, _dp, _dp, _i32, _dbl, _dbl, _dp, _dp, _i32, _dbl, _dbl, _u64, _u64p,
+                                            _vp, _vp]),
+    "icnv_hspike_simulate": (ct.c_int, [_dp, _i64, _i32, _i32, _dp, _dp, _i32, _dbl, _dbl, _dp, _dp, _i32, _dbl, _dbl, _u64, _u64p, _vp]),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

@@ -632,6 +632,50 @@ def mask_non_de(x, padj, p_val_thresh, base, cell_cmps, n_normal, rule="any", ma
     return out, used.value
 
 
+# ------------------------------------------------------------------ hidden spike-in (DESIGN K15)
+def group_gene_tables(x, groups):
+    """.get_mean_var_table / .get_mean_vs_p0_table (R/inferCNV_meanVarSim.R:178-211, R/inferCNV_simple_sim.R:100-154) for all
+    groups in one call (icnv_group_gene_tables_dev, DESIGN K15).  x: (C, G) CUDA float64 matrix with contiguous rows; groups:
+    list of non-empty 0-based cell index vectors (they may overlap).  Returns (m, v, nzero) CUDA tensors (n_groups, G): the
+    correctly rounded mean, the variance (NaN for a one-cell group) and the int32 number of zeros.  Synchronises the device."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    cidx, coff = pack_groups(groups)
+    cidx, cp = i32(cidx)
+    coff, cop = i32(coff)
+    n = max(len(groups), 1)
+    m = torch.empty((n, G), dtype=torch.float64, device=x.device)
+    v = torch.empty_like(m)
+    nzero = torch.empty((n, G), dtype=torch.int32, device=x.device)
+    check(L.icnv_group_gene_tables_dev(_ptr(x), G, C, ld, cp, cop, len(groups), _ptr(m), _ptr(v), _ptr(nzero), _stream()))
+    return m, v, nzero
+
+
+def hspike_simulate(means, num_cells, var_spline, p0_spline, seed, tokens, device=None):
+    """.get_simulated_cell_matrix_using_meanvar_trend_helper + .apply_dropout (R/inferCNV_meanVarSim.R:23-55, 105-161) for
+    several matrices in one launch (icnv_hspike_simulate_dev, DESIGN K15).  means: (n_mat, n_genes) host array, one row of
+    gene means per matrix; var_spline / p0_spline: objects with knots, coef, xmin and range (smooth_spline.SmoothSpline);
+    tokens: one uint64 per matrix.  Returns a (n_mat, num_cells, n_genes) CUDA float64 tensor: matrix k, cell c, gene g.
+    Synchronises the device."""
+    L = _lib.load()
+    means, mp = f64(np.atleast_2d(np.asarray(means, dtype=np.float64)))
+    n_mat, n_genes = means.shape
+    tok, tp = _u64(tokens)
+    if tok.size != n_mat:
+        raise ValueError("one token per matrix")
+    vk, vkp = f64(var_spline.knots)
+    vc, vcp = f64(var_spline.coef)
+    pk, pkp = f64(p0_spline.knots)
+    pc, pcp = f64(p0_spline.coef)
+    if vk.size != vc.size + 4 or pk.size != pc.size + 4:
+        raise ValueError("a spline has nk coefficients and nk + 4 knots")
+    out = torch.empty((n_mat, int(num_cells), n_genes), dtype=torch.float64, device=device if device is not None else "cuda")
+    check(L.icnv_hspike_simulate_dev(mp, n_genes, int(num_cells), n_mat, vkp, vcp, vc.size, float(var_spline.xmin), float(var_spline.range),
+                                     pkp, pcp, pc.size, float(p0_spline.xmin), float(p0_spline.range), int(seed) & (2**64 - 1), tp,
+                                     _ptr(out), _stream()))
+    return out
+
+
 DE_STATS = ("calls", "comparisons", "genes", "segments_lds", "segments_hbm", "waves", "us")
 
 
