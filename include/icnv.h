@@ -848,6 +848,41 @@ int icnv_hspike_simulate(const double *means, int64_t n_genes, int32_t num_cells
                          const double *p0_coef, int32_t p0_nk, double p0_xmin, double p0_range, uint64_t seed, const uint64_t *tokens,
                          double *out);
 
+/* ---- window smoothers of step 10 (K16) -----------------------------------------------------------------------------------
+ * smooth_method = "runmeans" (smooth_by_chromosome_runmeans, R/inferCNV_ops.R:2679-2704) and "coordinates"
+ * (smooth_by_chromosome_coordinates, :2534-2622) are one banded window operator; the windows and weights do not depend on
+ * the cell and are built on the host (infercnv_amd/smooth_windows.py).  DESIGN.md section 4 K16, restated in
+ * tests/smooth_windows_restate.py.  Not yet bound in the R shim.
+ *   out[g, c] = ( sum over t = 0 .. len[g] - 1 of  x[lo[g] + t, c] * w[w_off[g] + t] ) / denom[g]
+ * The sum starts at +0.0 and runs SEQUENTIALLY in t, in doubles: one rounding per product, one per add (no FMA), and one
+ * division at the end.  w = NULL means all weights 1.0 (w_off is then not read); x * 1.0 is exact, so both forms give the
+ * same bits.  Bit equality with R is not claimed: caTools::runmean keeps a compensated running sum and R's sum() accumulates
+ * in long double.
+ * Tables (HOST arrays; the library uploads them): lo, len [G] int32; w_off [G + 1] int64, window g's weights at
+ * w[w_off[g] .. w_off[g] + len[g]) with w_off[g + 1] >= w_off[g] + len[g] (a CSR: the rows of neighbouring genes follow each
+ * other); w [w_off[G]]; denom [G].
+ * _dev flavour: expr_in / expr_out are DEVICE matrices, element (g, c) at expr_in[c * ld_in + g] / expr_out[c * ld_out + g]
+ * (ld >= G: the padded_matrix layout of infercnv_amd/device.py); the padding is never read or written.
+ * ICNV_ERR_ARG before any launch, outputs untouched: a null argument, G or C outside 1 .. 2^31 - 1, ld < G, lo < 0, len < 1,
+ *   lo + len > G, a w_off that is not monotone as above, a denom that is zero or not finite, expr_out overlapping expr_in (a
+ *   window reads its neighbours, so the operator does NOT work in place).
+ * ICNV_ERR_ARG after the launch, output unspecified: a value of the input that is not finite.  The kernel raises a flag word
+ *   when it stages or sums such a value (every value inside a window is seen; no extra pass over the matrix).  caTools would
+ *   skip such values and the reference's coordinate smoother says "No handling of NAs" (:2596); the library refuses the
+ *   input, as K10 does, and does not improvise.
+ * Synchronises the stream.  Timer name: "smooth_windows". */
+int icnv_smooth_windows_dev(const double *expr_in, int64_t ld_in, double *expr_out, int64_t ld_out, int64_t G, int64_t C,
+                            const int32_t *lo, const int32_t *len, const int64_t *w_off, const double *w, const double *denom,
+                            void *stream);
+/* The same with HOST matrices (ld = G).  (R/inferCNV_ops.R:2594-2622, 2691) */
+int icnv_smooth_windows(const double *expr_in, double *expr_out, int64_t G, int64_t C, const int32_t *lo, const int32_t *len,
+                        const int64_t *w_off, const double *w, const double *denom);
+/* Counters since the last reset (R/inferCNV_ops.R:858-868), n = int64 slots (<= 6 written):
+ *   out[0] calls   out[1] gene tiles staged in LDS   out[2] gene tiles read from HBM (span beyond the LDS budget)
+ *   out[3] calls with weights   out[4] window rows (sum of len)   out[5] wall microseconds */
+int icnv_smooth_windows_stats(int64_t *out, int32_t n);
+void icnv_smooth_windows_stats_reset(void);   /* R/inferCNV_ops.R:858-868 */
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

@@ -160,6 +160,10 @@ PROTOTYPES = {
     "icnv_hspike_simulate_dev": (ct.c_int, [_dp, _i64, _i32, _i32, _dp, _dp, _i32, _dbl, _dbl, _dp, _dp, _i32, _dbl, _dbl, _u64, _u64p,
                                             _vp, _vp]),
     "icnv_hspike_simulate": (ct.c_int, [_dp, _i64, _i32, _i32, _dp, _dp, _i32, _dbl, _dbl, _dp, _dp, _i32, _dbl, _dbl, _u64, _u64p, _vp]),
+    "icnv_smooth_windows_dev": (ct.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _ip, _ip, _i64p, _dp, _dp, _vp]),
+    "icnv_smooth_windows": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _ip, _i64p, _dp, _dp]),
+    "icnv_smooth_windows_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_smooth_windows_stats_reset": (None, []),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

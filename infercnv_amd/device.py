@@ -89,6 +89,60 @@ def smooth_chain(x, chr_start, ref_groups, window_length=101, max_thresh=3.0, us
     return out, pre
 
 
+# ------------------------------------------------------------------ window smoothers of step 10 (DESIGN K16)
+def smooth_windows(x, table, out=None):
+    """The banded window operator of smooth_method "runmeans" / "coordinates" (icnv_smooth_windows_dev, DESIGN K16) on a
+    (C, G) CUDA float64 matrix with contiguous rows (a padded_matrix is fine, for x and for out): out[c, g] = the sequential
+    sum of x[c, lo[g] + t] * w[w_off[g] + t] over t < len[g], divided by denom[g].  table: smooth_windows.WindowTable in the
+    matrix's gene order.  out must not overlap x.  A non-finite input value raises IcnvError.  Synchronises the stream."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    if table.G != G:
+        raise ValueError(f"the table has {table.G} genes, the matrix {G}")
+    if out is None:
+        out = torch.empty((C, G), dtype=torch.float64, device=x.device)
+    Co, Go, ld_out = _check_matrix_ld(out)
+    if (Co, Go) != (C, G):
+        raise ValueError("out must have the shape of x")
+    lo, lop = i32(table.lo)
+    ln, lnp = i32(table.len)
+    den, denp = f64(table.denom)
+    if table.w is not None:
+        off = np.ascontiguousarray(table.w_off, dtype=np.int64)
+        offp = off.ctypes.data_as(ct.POINTER(ct.c_int64))
+        w, wp = f64(table.w)
+    else:
+        offp, wp = None, None
+    check(L.icnv_smooth_windows_dev(_ptr(x), int(ld), _ptr(out), int(ld_out), G, C, lop, lnp, offp, wp, denp, _stream()))
+    return out
+
+
+SMOOTH_WINDOWS_STATS = ("calls", "tiles_lds", "tiles_spilled", "weighted_calls", "window_rows", "us")
+
+
+def smooth_windows_stats(reset=False):
+    """icnv_smooth_windows_stats as a dict (`us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(SMOOTH_WINDOWS_STATS))()
+    check(L.icnv_smooth_windows_stats(out, len(SMOOTH_WINDOWS_STATS)))
+    if reset:
+        L.icnv_smooth_windows_stats_reset()
+    return dict(zip(SMOOTH_WINDOWS_STATS, (int(v) for v in out)))
+
+
+def smooth_chain_windows(x, chr_start, ref_groups, table, max_thresh=3.0, use_bounds=True, sd_amplifier=1.5, noise_filter=None,
+                         denoise=True, want_pre_denoise=False):
+    """smooth_chain with step 10 replaced by the window operator (smooth_method "runmeans" / "coordinates"): the chain with
+    steps 8 and 9, smooth_windows(table), then the chain with steps 11, 12, 14 (and 22) -- three library calls, the matrix
+    never leaves the device.  max_thresh None skips step 9.  Returns (out, pre_denoise or None)."""
+    m1 = _lib.ST_SUBTRACT_REF_1 | (0 if max_thresh is None else _lib.ST_MAX_THRESH)
+    m2 = _lib.ST_CENTER | _lib.ST_SUBTRACT_REF_2 | _lib.ST_INVERT_LOG2 | (_lib.ST_DENOISE if denoise else 0)
+    a, _ = smooth_chain(x, chr_start, ref_groups, max_thresh=max_thresh, use_bounds=use_bounds, stage_mask=m1)
+    b = smooth_windows(a, table)
+    return smooth_chain(b, chr_start, ref_groups, use_bounds=use_bounds, sd_amplifier=sd_amplifier, noise_filter=noise_filter,
+                        stage_mask=m2, out=a, want_pre_denoise=want_pre_denoise and denoise)
+
+
 class ChainPlan:
     """Split-phase chain (icnv_chain_* in include/icnv.h) for cell-sharded runs:
     for each reference round r: partial(r) -> all-reduce(sum) -> finish(r); then apply()."""

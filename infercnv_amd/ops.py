@@ -14,7 +14,7 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, smooth_windows as _sw
 from ._lib import Cfg, check
 from .infercnv_object import InfercnvObject
 
@@ -305,6 +305,52 @@ def smooth_by_chromosome(infercnv_obj: InfercnvObject, window_length, smooth_end
     return _with_expr(infercnv_obj, out, hs)
 
 
+def _smooth_windows(obj: InfercnvObject, smooth_method, window_length):
+    """The window operator (icnv_smooth_windows, DESIGN K16) on obj.expr_data with the table of `smooth_method`."""
+    L = _lib.load()
+    perm, _ = obj.chr_layout()
+    table = _sw.table_for(obj, smooth_method, window_length)
+    x = _as_f(obj.expr_data if perm is None else obj.expr_data[perm])
+    G, C = x.shape
+    out = np.empty_like(x, order="F")
+    lo, lop = _lib.i32(table.lo)
+    ln, lnp = _lib.i32(table.len)
+    den, denp = _lib.f64(table.denom)
+    offp = wp = None
+    if table.w is not None:
+        off = np.ascontiguousarray(table.w_off, dtype=np.int64)
+        offp = off.ctypes.data_as(ct.POINTER(ct.c_int64))
+        w, wp = _lib.f64(table.w)
+    check(L.icnv_smooth_windows(x.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), G, C, lop, lnp, offp, wp, denp))
+    if perm is not None:
+        inv = np.empty_like(perm)
+        inv[perm] = np.arange(perm.size)
+        out = out[inv]
+    return out
+
+
+def smooth_by_chromosome_runmeans(infercnv_obj: InfercnvObject, window_length) -> InfercnvObject:
+    """R/inferCNV_ops.R:2679-2704 (smooth_method = "runmeans"): caTools::runmean(k = window_length) along the genes of every
+    chromosome with more than one gene, mirrored on the hspike with the same window.  The sums are the library's sequential
+    ones (DESIGN K16): bit equality with caTools' compensated running sum is not claimed."""
+    out = _smooth_windows(infercnv_obj, "runmeans", window_length)
+    hs = None
+    if infercnv_obj.hspike is not None:  # :2697-2700
+        hs = smooth_by_chromosome_runmeans(infercnv_obj.hspike, window_length)
+    return _with_expr(infercnv_obj, out, hs)
+
+
+def smooth_by_chromosome_coordinates(infercnv_obj: InfercnvObject, window_length) -> InfercnvObject:
+    """R/inferCNV_ops.R:2534-2622 (smooth_method = "coordinates"): windows of +- window_length base pairs around every gene's
+    midpoint, the reference's quirks kept (smooth_windows.coordinate_windows); window_length < 2 returns the data unchanged
+    (:2569-2572).  The hspike is smoothed with window_length = 51 on its own gene_order (:2556-2559)."""
+    out = _smooth_windows(infercnv_obj, "coordinates", window_length)
+    hs = None
+    if infercnv_obj.hspike is not None:
+        hs = smooth_by_chromosome_coordinates(infercnv_obj.hspike, 51)
+    return _with_expr(infercnv_obj, out, hs)
+
+
 # ------------------------------------------------------------------ step 11
 def center_cell_expr_across_chromosome(infercnv_obj: InfercnvObject, method="mean") -> InfercnvObject:
     """R/inferCNV_ops.R:2074-2088; method "median" (what run() passes, :911) or "mean"."""
@@ -343,11 +389,16 @@ def clear_noise(infercnv_obj: InfercnvObject, threshold, noise_logistic=False) -
 
 # ------------------------------------------------------------------ fused entry
 def hip_smooth_chain(infercnv_obj: InfercnvObject, window_length=101, max_centered_threshold=3.0,
-                     sd_amplifier=1.5, noise_filter=None, denoise=True, return_hmm_input=False, noise_logistic=False):
+                     sd_amplifier=1.5, noise_filter=None, denoise=True, return_hmm_input=False, noise_logistic=False,
+                     smooth_method="pyramidinal"):
     """Steps 8,9,10,11,12,14(,22) of run() back to back in one fused device pass
     (SURVEY.md 8b.1).  Equivalent to calling the stand-alone wrappers in run()'s
     order.  With return_hmm_input=True also returns the object before step 22
-    (what step 17's HMM reads, R/inferCNV_ops.R:1237-1309)."""
+    (what step 17's HMM reads, R/inferCNV_ops.R:1237-1309).
+    smooth_method (R/inferCNV_ops.R:858-868): "pyramidinal" (default) is the fused pass; "runmeans" and "coordinates" run
+    the chain with steps 8 and 9, the window operator (DESIGN K16), then the chain with steps 11, 12, 14 (and 22)."""
+    if smooth_method not in ("pyramidinal", "runmeans", "coordinates"):
+        raise ValueError(f'smooth_method must be "pyramidinal", "runmeans" or "coordinates", got {smooth_method!r}')
     thr = max_centered_threshold
     mask = _lib.ST_ALL if denoise else (_lib.ST_ALL & ~_lib.ST_DENOISE)
     if isinstance(thr, str):
@@ -360,13 +411,21 @@ def hip_smooth_chain(infercnv_obj: InfercnvObject, window_length=101, max_center
     if thr is None or (isinstance(thr, float) and math.isnan(thr)):
         mask &= ~_lib.ST_MAX_THRESH
         thr = None
-    out, pre = _run_chain(infercnv_obj, mask, window_length=window_length, max_thresh=thr,
-                          sd_amplifier=sd_amplifier, noise_filter=noise_filter, want_pre_denoise=return_hmm_input,
-                          noise_logistic=noise_logistic)
+    if smooth_method == "pyramidinal":
+        out, pre = _run_chain(infercnv_obj, mask, window_length=window_length, max_thresh=thr,
+                              sd_amplifier=sd_amplifier, noise_filter=noise_filter, want_pre_denoise=return_hmm_input,
+                              noise_logistic=noise_logistic)
+    else:
+        front, _ = _run_chain(infercnv_obj, mask & (_lib.ST_SUBTRACT_REF_1 | _lib.ST_MAX_THRESH), max_thresh=thr)
+        mid = _with_expr(infercnv_obj, _smooth_windows(_with_expr(infercnv_obj, front), smooth_method, window_length))
+        out, pre = _run_chain(mid, mask & ~(_lib.ST_SUBTRACT_REF_1 | _lib.ST_MAX_THRESH | _lib.ST_SMOOTH),
+                              sd_amplifier=sd_amplifier, noise_filter=noise_filter, want_pre_denoise=return_hmm_input and denoise,
+                              noise_logistic=noise_logistic)
     hs = None
     if infercnv_obj.hspike is not None:
-        # the hspike mirrors steps 8..14 but not the denoise (reference: commented out)
-        hs = hip_smooth_chain(infercnv_obj.hspike, window_length, thr, sd_amplifier, noise_filter, denoise=False)
+        # the hspike mirrors steps 8..14 but not the denoise (reference: commented out); its coordinate windows are 51 (:2558)
+        hs = hip_smooth_chain(infercnv_obj.hspike, 51 if smooth_method == "coordinates" else window_length, thr, sd_amplifier,
+                              noise_filter, denoise=False, smooth_method=smooth_method)
     res = _with_expr(infercnv_obj, out, hs)
     if return_hmm_input:
         return res, _with_expr(infercnv_obj, pre if denoise else out, hs)
