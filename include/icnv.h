@@ -883,6 +883,64 @@ int icnv_smooth_windows(const double *expr_in, double *expr_out, int64_t G, int6
 int icnv_smooth_windows_stats(int64_t *out, int32_t n);
 void icnv_smooth_windows_stats_reset(void);   /* R/inferCNV_ops.R:858-868 */
 
+/* ---- data layer of plot_cnv (K17) ---------------------------------------------------------------------------------------
+ * What plot_cnv (R/inferCNV_heatmap.R) computes from the matrix: the "auto" x.range quantiles (:159), the colour key's
+ * hist() (:2524) and the binned panel that image() draws.  DESIGN.md section 4 K17, restated in tests/heatmap_restate.py.
+ * Not yet bound in the R shim.
+ * Matrices: _dev flavours take a DEVICE matrix, element (g, c) at x[c * ld + g] with ld >= G (the padded_matrix layout of
+ * infercnv_amd/device.py; the padding is never read); the flavours without _dev take a HOST matrix with ld = G.  Every other
+ * array is a HOST array unless it says otherwise (the library uploads cell lists and breaks).  Element offsets are int64.
+ * Common refusals, ICNV_ERR_ARG before any launch: a null argument, G or C outside 1 .. 2^31 - 1, ld < G.
+ * On ANY error every output is left exactly as it was.  All calls synchronise the stream.
+ *
+ * icnv_quantiles_excluding: quantile(x[x != exclude], probs, type = 7), exactly.
+ *   Kept values: x != exclude under IEEE comparison (exclude = NaN keeps everything; exclude = 0.0 drops -0.0 too).
+ *   Order: -0.0 is canonicalised to +0.0 first, so both are one value, reported as +0.0.
+ *   With n = n_kept and, per probability p:  index = (n - 1) * p  in double, lo = floor(index), hi = ceil(index), h = index - lo,
+ *     quantile = x_(lo)  if index == lo or x_(hi) == x_(lo),  else (1 - h) * x_(lo) + h * x_(hi)
+ *   (x_(k): the k-th smallest kept value, 0-based), evaluated on the host in that operation order, without FMA.  This is
+ *   R's arithmetic as read from its sources, not checked against an R run.
+ *   Outputs: quantiles [n_probs]; order_stats [2 * n_probs] = x_(lo), x_(hi) per probability (nullable); counts [2] = n_kept,
+ *   n_excluded (nullable); minmax [2] = min and max over ALL values, excluded ones included (nullable; plot_cnv logs them, :131-136).
+ *   ICNV_ERR_ARG: n_probs outside 1 .. 8, a probability outside [0, 1] or NaN (before any launch); a value of x that is not
+ *   finite, or n_kept == 0 (found by the first pass).
+ *   Method: radix selection on the order-preserving 64-bit key, 8 bits per pass.  A pass reads the matrix once and counts one
+ *   digit under every tracked prefix (at most 16: a probability's lo and hi may part) into int64 totals, so the result does
+ *   not depend on arrival order; the first pass also makes the non-finite check, n_kept and min / max.  Once the bins that
+ *   hold the wanted ranks count <= 4096 values together, one more pass compacts them and one workgroup sorts them; a bin
+ *   that never shrinks (most of the matrix is one value) is followed through all 8 digits instead.  Timer names:
+ *   "heatmap_radix", "heatmap_compact", "heatmap_sort". */
+int icnv_quantiles_excluding_dev(const double *x, int64_t ld, int64_t G, int64_t C, double exclude, const double *probs,
+                                 int32_t n_probs, double *quantiles, double *order_stats, int64_t *counts, double *minmax,
+                                 void *stream);
+int icnv_quantiles_excluding(const double *x, int64_t G, int64_t C, double exclude, const double *probs, int32_t n_probs,
+                             double *quantiles, double *order_stats, int64_t *counts, double *minmax);
+/* icnv_heatmap_bins: hist(x[, rows], breaks = breaks)$counts (R/inferCNV_heatmap.R:2524) over the cells listed in rows
+ *   [n_rows] (any order or subset; a cell listed twice counts twice).  Each value is first forced into
+ *   [breaks[0], breaks[nb - 1]] (:1934-1935); bin b holds breaks[b] < v <= breaks[b + 1] and v == breaks[0] goes in bin 0
+ *   (.bincode(right = TRUE, include.lowest = TRUE)).  counts [nb - 1] int64, exact, from one read of the listed rows.
+ *   ICNV_ERR_ARG: nb outside 2 .. 257, a break that is not finite, breaks not strictly ascending, n_rows outside
+ *   1 .. 2^31 - 1, a list entry outside 0 .. C - 1 (before any launch); a NaN in a listed row (+-Inf is clamped like any
+ *   other value).  Timer name: "heatmap_bins". */
+int icnv_heatmap_bins_dev(const double *x, int64_t ld, int64_t G, int64_t C, const int32_t *rows, int64_t n_rows,
+                          const double *breaks, int32_t nb, int64_t *counts, void *stream);
+int icnv_heatmap_bins(const double *x, int64_t G, int64_t C, const int32_t *rows, int64_t n_rows, const double *breaks, int32_t nb,
+                      int64_t *counts);
+/* icnv_heatmap_raster: the panel as an H x W uint8 image of bin indices (same binning), row-major, nearest-neighbour sampled
+ *   as R's useRaster = TRUE at device resolution is believed to behave:
+ *     pixel row i shows cell order[((2 i + 1) * n) / (2 H)],  pixel column j shows gene ((2 j + 1) * G) / (2 W)
+ *   in int64 integer arithmetic; H and W may be smaller or larger than n and G.  image: DEVICE [H * W] in the _dev flavour,
+ *   HOST otherwise.  Refusals as icnv_heatmap_bins, plus H or W outside 1 .. 2^31 - 1; a sampled NaN is ICNV_ERR_ARG (the
+ *   panel is rendered aside and copied only on success).  Timer name: "heatmap_raster". */
+int icnv_heatmap_raster_dev(const double *x, int64_t ld, int64_t G, int64_t C, const int32_t *order, int64_t n,
+                            const double *breaks, int32_t nb, int64_t H, int64_t W, uint8_t *image, void *stream);
+int icnv_heatmap_raster(const double *x, int64_t G, int64_t C, const int32_t *order, int64_t n, const double *breaks, int32_t nb,
+                        int64_t H, int64_t W, uint8_t *image);
+/* Counters since the last reset, n = int64 slots (<= 4 written):
+ *   out[0] calls (of the three entry points)   out[1] radix passes   out[2] compacted candidates   out[3] wall microseconds */
+int icnv_heatmap_stats(int64_t *out, int32_t n);
+void icnv_heatmap_stats_reset(void);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

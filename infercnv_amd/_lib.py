@@ -164,6 +164,14 @@ PROTOTYPES = {
     "icnv_smooth_windows": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _ip, _i64p, _dp, _dp]),
     "icnv_smooth_windows_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_smooth_windows_stats_reset": (None, []),
+    "icnv_quantiles_excluding_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _dbl, _dp, _i32, _dp, _dp, _i64p, _dp, _vp]),
+    "icnv_quantiles_excluding": (ct.c_int, [_vp, _i64, _i64, _dbl, _dp, _i32, _dp, _dp, _i64p, _dp]),
+    "icnv_heatmap_bins_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _i64, _dp, _i32, _i64p, _vp]),
+    "icnv_heatmap_bins": (ct.c_int, [_vp, _i64, _i64, _ip, _i64, _dp, _i32, _i64p]),
+    "icnv_heatmap_raster_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _i64, _dp, _i32, _i64, _i64, _vp, _vp]),
+    "icnv_heatmap_raster": (ct.c_int, [_vp, _i64, _i64, _ip, _i64, _dp, _i32, _i64, _i64, _vp]),
+    "icnv_heatmap_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_heatmap_stats_reset": (None, []),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

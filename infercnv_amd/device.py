@@ -130,6 +130,86 @@ def smooth_windows_stats(reset=False):
     return dict(zip(SMOOTH_WINDOWS_STATS, (int(v) for v in out)))
 
 
+# ------------------------------------------------------------------ data layer of plot_cnv (DESIGN K17)
+def quantiles_excluding_into(x, exclude, probs, quantiles, order_stats, counts, minmax):
+    """icnv_quantiles_excluding_dev into caller-owned numpy arrays (float64 [n], float64 [2 n], int64 [2], float64 [2]; the
+    last three may be None).  On an IcnvError they are left as they were."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    pr, prp = f64(probs)
+    for a, dt in ((quantiles, np.float64), (order_stats, np.float64), (counts, np.int64), (minmax, np.float64)):
+        if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous):
+            raise TypeError("the outputs are contiguous numpy arrays of float64 / float64 / int64 / float64")
+    if quantiles.size < pr.size or (order_stats is not None and order_stats.size < 2 * pr.size) or \
+            (counts is not None and counts.size < 2) or (minmax is not None and minmax.size < 2):
+        raise ValueError("an output array is too short")
+    dp = lambda a: a.ctypes.data_as(ct.POINTER(ct.c_double)) if a is not None else None
+    cp = counts.ctypes.data_as(ct.POINTER(ct.c_int64)) if counts is not None else None
+    check(L.icnv_quantiles_excluding_dev(_ptr(x), int(ld), G, C, float(exclude), prp, int(pr.size), dp(quantiles), dp(order_stats),
+                                         cp, dp(minmax), _stream()))
+
+
+def quantiles_excluding(x, exclude, probs):
+    """quantile(x[x != exclude], probs, type = 7) of a (C, G) CUDA float64 matrix with contiguous rows (a padded_matrix is
+    fine), exactly and without a sort (icnv_quantiles_excluding_dev, DESIGN K17): the "auto" x.range of plot_cnv
+    (R/inferCNV_heatmap.R:159).  exclude = NaN keeps every value; up to 8 probabilities per call.  Returns a dict of
+    numpy values: quantiles [n], lo / hi [n] (the two order statistics each quantile interpolates), n_kept, n_excluded, min,
+    max (over all values).  A non-finite value, no kept value or a probability outside [0, 1] raises IcnvError."""
+    n = np.asarray(probs, dtype=np.float64).size
+    q, st = np.zeros(n), np.zeros(2 * n)
+    cnt, mm = np.zeros(2, dtype=np.int64), np.zeros(2)
+    quantiles_excluding_into(x, exclude, probs, q, st, cnt, mm)
+    return {"quantiles": q, "lo": st[0::2].copy(), "hi": st[1::2].copy(), "n_kept": int(cnt[0]), "n_excluded": int(cnt[1]),
+            "min": float(mm[0]), "max": float(mm[1])}
+
+
+def heatmap_bins(x, breaks, rows=None, out=None):
+    """hist(x[rows, ], breaks)$counts after forcing every value into [breaks[0], breaks[-1]] (icnv_heatmap_bins_dev, DESIGN
+    K17; R/inferCNV_heatmap.R:1934-1935, :2524): bin b holds breaks[b] < v <= breaks[b + 1], v == breaks[0] goes in bin 0.
+    rows: 0-based cells in any order or subset (default: all).  Returns int64 numpy counts [len(breaks) - 1] (written into
+    `out` when given; untouched on an IcnvError)."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    br, brp = f64(breaks)
+    r, rp = i32(np.arange(C) if rows is None else rows)
+    if out is None:
+        out = np.zeros(max(br.size - 1, 1), dtype=np.int64)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.int64 and out.flags.c_contiguous and out.size >= br.size - 1):
+        raise TypeError("out must be a contiguous int64 numpy array of len(breaks) - 1 entries")
+    check(L.icnv_heatmap_bins_dev(_ptr(x), int(ld), G, C, rp, int(r.size), brp, int(br.size), out.ctypes.data_as(ct.POINTER(ct.c_int64)),
+                                  _stream()))
+    return out
+
+
+def heatmap_raster(x, breaks, order, H, W, out=None):
+    """The heatmap panel as an (H, W) CUDA uint8 image of bin indices (icnv_heatmap_raster_dev, DESIGN K17): pixel row i shows
+    cell order[((2 i + 1) n) // (2 H)], pixel column j gene ((2 j + 1) G) // (2 W), binned as heatmap_bins bins.  order:
+    0-based cells, top row first.  `out` (contiguous CUDA uint8 (H, W)) is untouched on an IcnvError."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    br, brp = f64(breaks)
+    o, op = i32(order)
+    if out is None:
+        out = torch.empty((int(H), int(W)), dtype=torch.uint8, device=x.device)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (int(H), int(W))):
+        raise TypeError("out must be a contiguous CUDA uint8 tensor of shape (H, W)")
+    check(L.icnv_heatmap_raster_dev(_ptr(x), int(ld), G, C, op, int(o.size), brp, int(br.size), int(H), int(W), _ptr(out), _stream()))
+    return out
+
+
+HEATMAP_STATS = ("calls", "radix_passes", "candidates", "us")
+
+
+def heatmap_stats(reset=False):
+    """icnv_heatmap_stats as a dict (`us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(HEATMAP_STATS))()
+    check(L.icnv_heatmap_stats(out, len(HEATMAP_STATS)))
+    if reset:
+        L.icnv_heatmap_stats_reset()
+    return dict(zip(HEATMAP_STATS, (int(v) for v in out)))
+
+
 def smooth_chain_windows(x, chr_start, ref_groups, table, max_thresh=3.0, use_bounds=True, sd_amplifier=1.5, noise_filter=None,
                          denoise=True, want_pre_denoise=False):
     """smooth_chain with step 10 replaced by the window operator (smooth_method "runmeans" / "coordinates"): the chain with
