@@ -469,6 +469,61 @@ int icnv_snn_graph_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off
 int icnv_leiden_stats(int64_t *out, int32_t n);
 void icnv_leiden_stats_reset(void);   /* R/inferCNV_tumor_subclusters.R:736 */
 
+/* ---- PCA route of the Leiden subclustering (K18) -----------------------------------------------------------------------
+ * .leiden_seurat_preprocess_routine (R/inferCNV_tumor_subclusters.R:699-723), the reference's default leiden_method = "PCA"
+ * (R/inferCNV_ops.R:289, R/inferCNV_tumor_subclusters.R:5): CreateSeuratObject -> FindVariableFeatures -> ScaleData ->
+ * RunPCA(npcs = 10) -> FindNeighbors(k.param = k_nn) -> graph_from_adjacency_matrix(snn, mode = "min", weighted = TRUE) ->
+ * cluster_leiden, for a BATCH of problems.  Seurat's loess (kd-tree interpolation), irlba (randomised, truncated), annoy
+ * (approximate) and igraph's RNG cannot be restated: the library defines each stage exactly (DESIGN.md section 4 K18,
+ * restated in tests/leiden_pca_restate.py); "as Seurat does" below is believed, not verified.
+ * A problem is n cells (cell list, HOST) and its genes (gene list, HOST, in list order); element (gene g, cell c) at
+ * expr[c * ld + g].  mean / sd / v_std are DEVICE arrays with one entry per (problem, gene), packed like gene_idx.
+ *
+ * icnv_lpca_vstd_dev (FindVariableFeatures, selection.method = "vst", clip.max = "auto"; :706): mean = K15's mean of the gene
+ *   over the problem's cells (icnv_group_gene_tables_dev), sd = sqrt(10^fit) of the host's trend (infercnv_amd/loess_fit.py):
+ *   v_std = (sum over the cells in list order of min(sqrt(n), (x - mean) / sd)^2) / (n - 1), a sequential fp64 sum, every
+ *   operation rounded by itself (no FMA).  sd = 0 (a gene outside the fit: constant over the cells) gives 0.  n >= 2.
+ * icnv_lpca_scale_dev (ScaleData, :707-708): z = min(10, (x - mean) / sd) with sd = sqrt(K15's variance); sd = 0 gives 0.
+ *   Written feature-major: problem p's block starts at the sum over q < p of F_q ldz_q doubles, F_p rows (the listed genes in
+ *   order) of ldz_p = n_p + (n_p & 1) doubles, the padding element 0.
+ * icnv_lpca_gram_dev (RunPCA, :709): M_p = Z_p Z_p^T (F_p x F_p, row-major, packed one after another) on the fp64 matrix
+ *   cores: the upper triangle of 64 x 64 tiles, each value written to (a, b) and (b, a): exactly symmetric.  Per entry
+ *   |M - sum z_a z_b| <= gamma_n sum |z_a z_b|, gamma_n = n u / (1 - n u), u = 2^-53, whatever the summation order.
+ * icnv_lpca_project_dev: E_p = Z_p^T V_p, V_p (F_p x npcs_p, row-major, packed) the eigenvectors: per (cell, component) the
+ *   sequential fp64 sum over the features in ascending order of the rounded products (no FMA).  E: (sum n_p, e_ld) rows in
+ *   problem order, the components >= npcs_p zero: the matrix icnv_knn_dev searches (npcs "genes").  npcs_p <= e_ld <= 64.
+ * icnv_snn_begin_dev / _fill_dev / _end (Seurat's ComputeSNN, prune.SNN = 1/15, on the (n, k) index block of icnv_knn_dev):
+ *   s_ij = |N(i) n N(j)| for every pair i != j that shares a neighbour; kept iff 16 s_ij >= 2 k (s / (2 k - s) >= 1/15 in
+ *   integers).  begin builds the transposed lists (count, scan, fill, sort per row), counts every row and returns the exact
+ *   number of entries (HOST); fill writes the CSR (DEVICE): row_off [sum n_p + 1] over the batch, col ascending positions
+ *   within the problem, shared = s_ij, weight = (2 s 2^24 + d) / (2 d) with d = 2 k - s in integer division (s / d in 24-bit
+ *   fixed point, rounded to nearest), loop [sum n_p] = 1 (s_ii = k: every node carries a loop of weight 2^24).  An nn_idx
+ *   entry outside [0, n_p): ICNV_ERR_ARG from a device check.  1 <= k <= min(128, n_p).  end frees the state.
+ * icnv_leiden_graph_dev: icnv_leiden_dev (K11, its contract above word for word) on a caller's weighted graphs instead of
+ *   nn_idx: level 0 has the edge weights `weight` (int64 >= 1), s_i = sum of row i's weights + 2 loop_weight loop_i; node
+ *   weight 1 (CPM) or s_i (modularity); r = gamma (CPM: the caller scales gamma by its weight unit) or gamma / sum s.  The CSR
+ *   must be symmetric (not checked); rows ascending, without the node itself, col in [0, n_p), loop in {0, 1}: ICNV_ERR_ARG
+ *   from a device check.  Total edge weight of a problem (sum s / 2) >= 2^53: ICNV_ERR_UNSUPPORTED (the int64 -> double
+ *   conversions of the gain must be exact).  Scratch is sized by the entries of the CSR.  Every call synchronises. */
+typedef struct icnv_snn icnv_snn_t;
+int icnv_lpca_vstd_dev(const double *expr, int64_t G, int64_t C, int64_t ld, const int32_t *gene_idx, const int32_t *gene_off,
+                       const int32_t *cell_idx, const int32_t *cell_off, int32_t n_prob, const double *mean, const double *sd,
+                       double *v_std, void *stream);
+int icnv_lpca_scale_dev(const double *expr, int64_t G, int64_t C, int64_t ld, const int32_t *gene_idx, const int32_t *gene_off,
+                        const int32_t *cell_idx, const int32_t *cell_off, int32_t n_prob, const double *mean, const double *sd,
+                        double *Z, void *stream);
+int icnv_lpca_gram_dev(const double *Z, const int32_t *n_feat, const int32_t *n_cells, int32_t n_prob, double *M, void *stream);
+int icnv_lpca_project_dev(const double *Z, const double *V, const int32_t *n_feat, const int32_t *n_cells, const int32_t *npcs,
+                          int32_t n_prob, double *E, int32_t e_ld, void *stream);
+int icnv_snn_begin_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, icnv_snn_t **out, int64_t *nnz,
+                       void *stream);
+int icnv_snn_fill_dev(icnv_snn_t *h, int64_t *row_off, int32_t *col, int32_t *shared, int64_t *weight, int32_t *loop, void *stream);
+void icnv_snn_end(icnv_snn_t *h);   /* R/inferCNV_tumor_subclusters.R:710 */
+int icnv_leiden_graph_dev(const int64_t *row_off, const int32_t *col, const int64_t *weight, const int32_t *loop, int64_t loop_weight,
+                          const int32_t *node_off, int32_t n_prob, int32_t objective, const double *resolution, double beta,
+                          int32_t n_iterations, uint64_t seed, const uint64_t *token, int32_t *membership, int32_t *n_clusters,
+                          void *stream);
+
 /* ---- HMM ---------------------------------------------------------------- */
 /* Viterbi.dthmm.adj (R/inferCNV_HMM.R:1101-1176) for every (cell, chromosome):
  * predict_CNV_via_HMM_on_indiv_cells (R/inferCNV_HMM.R:284-324) with K = 6 and

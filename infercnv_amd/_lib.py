@@ -28,6 +28,7 @@ ST_NA_AWARE = 0x100     # the matrix may hold NaN: cells that do are recomputed 
 
 OK, ERR_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_UNDERFLOW, ERR_NOMEM = 0, 1, 2, 3, 4, 5
 LEIDEN_CPM, LEIDEN_MODULARITY = 1, 2   # ICNV_LEIDEN_* objectives of icnv_leiden_dev
+SNN_WEIGHT_ONE = 1 << 24               # the 24-bit fixed-point 1 of icnv_snn_fill_dev's weights (a node's loop)
 DE_WILCOXON, DE_T = 1, 2               # ICNV_DE_* tests of icnv_de_tests_dev
 DE_MASK_ANY, DE_MASK_MOST, DE_MASK_ALL = 0, 1, 2   # ICNV_DE_MASK_* rules of icnv_mask_non_de_dev
 DE_JITTER_TOKEN = 0x6E6F6E44456A6974   # ICNV_DE_JITTER_TOKEN: the jitter stream's second key word
@@ -136,6 +137,14 @@ PROTOTYPES = {
     "icnv_leiden_dev": (ct.c_int, [_vp, _i32, _ip, _i32, _i32, _dp, _dbl, _i32, _u64, _u64p, _vp, _ip, _vp]),
     "icnv_leiden": (ct.c_int, [_vp, _i32, _ip, _i32, _i32, _dp, _dbl, _i32, _u64, _u64p, _vp, _ip]),
     "icnv_snn_graph_dev": (ct.c_int, [_vp, _i32, _ip, _i32, _vp, _vp, _vp, _vp]),
+    "icnv_leiden_graph_dev": (ct.c_int, [_vp, _vp, _vp, _vp, _i64, _ip, _i32, _i32, _dp, _dbl, _i32, _u64, _u64p, _vp, _ip, _vp]),
+    "icnv_lpca_vstd_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _ip, _ip, _ip, _i32, _vp, _vp, _vp, _vp]),
+    "icnv_lpca_scale_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _ip, _ip, _ip, _i32, _vp, _vp, _vp, _vp]),
+    "icnv_lpca_gram_dev": (ct.c_int, [_vp, _ip, _ip, _i32, _vp, _vp]),
+    "icnv_lpca_project_dev": (ct.c_int, [_vp, _vp, _ip, _ip, _ip, _i32, _vp, _i32, _vp]),
+    "icnv_snn_begin_dev": (ct.c_int, [_vp, _i32, _ip, _i32, ct.POINTER(_vp), _i64p, _vp]),
+    "icnv_snn_fill_dev": (ct.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "icnv_snn_end": (None, [_vp]),
     "icnv_leiden_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_leiden_stats_reset": (None, []),
     "icnv_de_tests_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _ip, _i32, _ip, _i32, _i32, _i32, _u64, _vp, _vp, _vp, _vp]),

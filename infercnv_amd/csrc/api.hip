@@ -19,6 +19,7 @@
 #include "hclust_internal.h"
 #include "random_trees_internal.h"
 #include "leiden_internal.h"
+#include "leiden_pca_internal.h"
 
 namespace icnv {
 
@@ -2590,18 +2591,16 @@ int icnv_snn_graph_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off
     return ICNV_OK;
 }
 
-int icnv_leiden_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, int32_t objective,
-                    const double *resolution, double beta, int32_t n_iterations, uint64_t seed, const uint64_t *token,
-                    int32_t *membership, int32_t *n_clusters, void *stream) {
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = leiden_validate(nn_idx, k, node_off, n_prob);
-    if (rc || (rc = leiden_validate_run(n_prob, objective, resolution, beta, n_iterations, membership, n_clusters))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    LeidenGraphBufs b;
-    if ((rc = leiden_build_graph(nn_idx, k, node_off, n_prob, s, b))) return rc;
-    const int64_t tn = b.noff[n_prob], to = tn + n_prob, E = 2 * (int64_t)k * tn;
+// the Leiden run of a batch whose graphs are on the device: g (CSR, strengths), the problems' edge regions (edge_off null:
+// 2 k node_off[p], icnv_leiden_dev's), the level-0 edge weights (ew0 null: 1) and E, the entries of all regions together
+static int leiden_run(const LeidenGraph &g, const std::vector<int64_t> &noff, const int64_t *edge_off, const int64_t *ew0, int64_t E,
+                      int32_t n_prob, int32_t objective, const double *resolution, double beta, int32_t n_iterations, uint64_t seed,
+                      const uint64_t *token, int32_t *membership, int32_t *n_clusters, hipStream_t s,
+                      std::chrono::steady_clock::time_point t0) {
+    int rc;
+    const int64_t tn = noff[n_prob], to = tn + n_prob;
     std::vector<int64_t> ssum(n_prob);
-    ICNV_HIP(hipMemcpyAsync(ssum.data(), b.d_ssum.p, ssum.size() * 8, hipMemcpyDeviceToHost, s));
+    ICNV_HIP(hipMemcpyAsync(ssum.data(), g.strength_sum, ssum.size() * 8, hipMemcpyDeviceToHost, s));
     ICNV_HIP(hipStreamSynchronize(s));
     std::vector<double> r(n_prob);
     for (int32_t p = 0; p < n_prob; ++p)   // R's wrapper: resolution_parameter / sum(strength) for modularity
@@ -2617,7 +2616,7 @@ int icnv_leiden_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off, i
         (rc = d_cnt.alloc((size_t)n_prob * LEIDEN_CNT_N * 8)))
         return rc;
     LeidenArgs a;
-    a.g = b.g; a.objective = objective; a.r = d_r.as<double>(); a.beta = beta; a.n_iterations = n_iterations; a.seed = seed;
+    a.g = g; a.edge_off = edge_off; a.ew0 = ew0; a.total_e = E; a.objective = objective; a.r = d_r.as<double>(); a.beta = beta; a.n_iterations = n_iterations; a.seed = seed;
     a.token = d_tok.as<uint64_t>(); a.i64 = d_i64.as<int64_t>(); a.offs = d_offs.as<int64_t>(); a.i32 = d_i32.as<int32_t>();
     a.cum = d_cum.as<double>(); a.nbr = d_nbr.as<int32_t>(); a.ew = d_ew.as<int64_t>(); a.total_n = tn;
     a.membership = d_memb.as<int32_t>(); a.n_clusters = d_ncl.as<int32_t>(); a.status = d_status.as<int32_t>();
@@ -2645,6 +2644,77 @@ int icnv_leiden_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off, i
         for (int c = 0; c < LEIDEN_CNT_N; ++c) g_ld[2 + c] += cnt[(size_t)p * LEIDEN_CNT_N + c];
     g_ld[6] += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     return ICNV_OK;
+}
+
+
+int icnv_leiden_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, int32_t objective,
+                    const double *resolution, double beta, int32_t n_iterations, uint64_t seed, const uint64_t *token,
+                    int32_t *membership, int32_t *n_clusters, void *stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = leiden_validate(nn_idx, k, node_off, n_prob);
+    if (rc || (rc = leiden_validate_run(n_prob, objective, resolution, beta, n_iterations, membership, n_clusters))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    LeidenGraphBufs b;
+    if ((rc = leiden_build_graph(nn_idx, k, node_off, n_prob, s, b))) return rc;
+    const int64_t tn = b.noff[n_prob];
+    return leiden_run(b.g, b.noff, nullptr, nullptr, 2 * (int64_t)k * tn, n_prob, objective, resolution, beta, n_iterations, seed, token,
+                      membership, n_clusters, s, t0);
+}
+
+int icnv_leiden_graph_dev(const int64_t *row_off, const int32_t *col, const int64_t *weight, const int32_t *loop, int64_t loop_weight,
+                          const int32_t *node_off, int32_t n_prob, int32_t objective, const double *resolution, double beta,
+                          int32_t n_iterations, uint64_t seed, const uint64_t *token, int32_t *membership, int32_t *n_clusters,
+                          void *stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!row_off || !col || !weight || !loop || !node_off) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: null argument");
+    if (n_prob < 1) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: n_prob must be >= 1");
+    if (loop_weight < 1 || loop_weight > ((int64_t)1 << 53)) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: loop_weight must be in [1, 2^53]");
+    if (node_off[0] != 0) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: offsets must start at 0");
+    for (int32_t p = 0; p < n_prob; ++p)
+        if (node_off[p + 1] <= node_off[p]) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: problem " + std::to_string(p) + " has no node");
+    int rc = leiden_validate_run(n_prob, objective, resolution, beta, n_iterations, membership, n_clusters);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t tn = node_off[n_prob], to = tn + n_prob;
+    std::vector<int64_t> roff((size_t)tn + 1), noff(node_off, node_off + n_prob + 1), off((size_t)to), eoff((size_t)n_prob + 1);
+    ICNV_HIP(hipMemcpyAsync(roff.data(), row_off, roff.size() * 8, hipMemcpyDeviceToHost, s));
+    ICNV_HIP(hipStreamSynchronize(s));
+    if (roff[0] != 0) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: row_off must start at 0");
+    for (int64_t i = 0; i < tn; ++i)
+        if (roff[i + 1] < roff[i]) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: row_off must be monotone");
+    const int64_t E = roff[tn];
+    if (E > ((int64_t)1 << 31) - 1) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "leiden_graph: batch too large (the entries must stay below 2^31)");
+    for (int32_t p = 0; p < n_prob; ++p) {   // problem p's offsets within its own edge region, n_p + 1 of them
+        const int64_t n0 = noff[p], n = noff[p + 1] - n0;
+        eoff[p] = roff[n0];
+        for (int64_t i = 0; i <= n; ++i) off[n0 + p + i] = roff[n0 + i] - roff[n0];
+    }
+    eoff[n_prob] = E;
+    DevBuf d_noff, d_off, d_eoff, d_strength, d_ssum, d_bad;
+    if ((rc = upload(d_noff, noff.data(), noff.size(), s)) || (rc = upload(d_off, off.data(), off.size(), s)) ||
+        (rc = upload(d_eoff, eoff.data(), eoff.size(), s)) || (rc = d_strength.alloc((size_t)tn * 8)) ||
+        (rc = d_ssum.alloc((size_t)n_prob * 8)) || (rc = d_bad.alloc(sizeof(uint32_t))))
+        return rc;
+    LgCheck c{};
+    c.node_off = d_noff.as<int64_t>(); c.row_off = row_off; c.col = col; c.loop = loop; c.weight = weight; c.loop_weight = loop_weight;
+    c.n_prob = n_prob; c.off = d_off.as<int64_t>(); c.edge_off = d_eoff.as<int64_t>(); c.strength = d_strength.as<int64_t>();
+    c.strength_sum = d_ssum.as<int64_t>(); c.bad = d_bad.as<uint32_t>();
+    uint32_t bad = 0;
+    std::vector<int64_t> ssum(n_prob);
+    ICNV_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
+    if ((rc = launch_lg_check(c, s))) return rc;
+    ICNV_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ICNV_HIP(hipMemcpyAsync(ssum.data(), d_ssum.p, ssum.size() * 8, hipMemcpyDeviceToHost, s));
+    ICNV_HIP(hipStreamSynchronize(s));
+    if (bad) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: a row is not ascending within [0, n_p) without its own node, a weight is < 1, or a loop flag is not 0 / 1");
+    for (int32_t p = 0; p < n_prob; ++p)   // the int64 -> double conversions of the gain must be exact
+        if (ssum[p] / 2 >= ((int64_t)1 << 53))
+            ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "leiden_graph: the total edge weight of problem " + std::to_string(p) + " reaches 2^53");
+    LeidenGraph g{};
+    g.k = 0; g.n_prob = n_prob; g.node_off = d_noff.as<int64_t>(); g.off = d_off.as<int64_t>(); g.col = const_cast<int32_t *>(col);
+    g.strength = d_strength.as<int64_t>(); g.strength_sum = d_ssum.as<int64_t>();
+    return leiden_run(g, noff, d_eoff.as<int64_t>(), weight, E, n_prob, objective, resolution, beta, n_iterations, seed, token, membership,
+                      n_clusters, s, t0);
 }
 
 int icnv_leiden(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, int32_t objective,

@@ -36,6 +36,9 @@ struct LeidenGraph {              // the graphs of a batch: problem p's nodes at
 
 struct LeidenArgs {               // one call; every pointer device memory, per-node arrays indexed like the graph
     LeidenGraph g;
+    const int64_t *edge_off;      // [n_prob] first entry of problem p's edge region (null: 2 k node_off[p])
+    const int64_t *ew0;           // level-0 edge weights, indexed like g.col (null: every weight 1)
+    int64_t total_e;              // entries of all edge regions together: the stride of the A / B edge arrays
     int32_t objective;            // ICNV_LEIDEN_CPM / ICNV_LEIDEN_MODULARITY
     const double *r;              // [n_prob] resolution (gamma, or gamma / sum s for modularity)
     double beta;
@@ -46,7 +49,7 @@ struct LeidenArgs {               // one call; every pointer device memory, per-
     int64_t *offs;                // 2 offset arrays (per node + 1 per problem): A, B
     int32_t *i32;                 // LEIDEN_I32_ARRAYS per-node arrays
     double *cum;                  // per node
-    int32_t *nbr;                 // 2 edge arrays (2 k per node): A, B
+    int32_t *nbr;                 // 2 edge arrays (total_e entries each): A, B
     int64_t *ew;                  // 2 edge weight arrays: A, B
     int64_t total_n;
     int32_t *membership;          // [sum n_p] 1-based

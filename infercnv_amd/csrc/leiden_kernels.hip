@@ -128,7 +128,7 @@ __global__ void __launch_bounds__(LD_GRAPH_NT) leiden_graph_kernel(LeidenGraph g
 struct Level {                    // the graph of one level of one problem
     const int64_t *off;
     const int32_t *nbr;
-    const int64_t *ew;            // null: every edge weight 1 (level 0)
+    const int64_t *ew;            // null: every edge weight 1 (level 0 of a kNN graph)
     const int64_t *w;             // null: every node weight 1 (CPM, level 0)
     __device__ int64_t wt(int64_t v) const { return w ? w[v] : 1; }
     __device__ int64_t ewt(int64_t t) const { return ew ? ew[t] : 1; }
@@ -474,7 +474,8 @@ __device__ void aggregate(const Level &L, int64_t N, int64_t n2, Prob &P, int64_
 
 __global__ void __launch_bounds__(LD_WAVE) leiden_kernel(LeidenArgs a) {
     const int p = blockIdx.x;
-    const int64_t n0 = a.g.node_off[p], n = a.g.node_off[p + 1] - n0, E = 2 * (int64_t)a.g.k;
+    const int64_t n0 = a.g.node_off[p], n = a.g.node_off[p + 1] - n0;
+    const int64_t eb = a.edge_off ? a.edge_off[p] : 2 * (int64_t)a.g.k * n0;   // the problem's edge region
     const int64_t tn = a.total_n, to = a.total_n + a.g.n_prob;
     Prob P;
     int64_t *I = a.i64 + n0;
@@ -485,8 +486,8 @@ __global__ void __launch_bounds__(LD_WAVE) leiden_kernel(LeidenArgs a) {
                                         &P.aggof, &P.renum, &P.perm, &P.members, &P.boff, &P.cursor, &P.cands, &P.fin};
     for (int i = 0; i < LEIDEN_I32_ARRAYS; ++i) *arr[i] = J + i * (tn + a.g.n_prob);
     P.cum = a.cum + n0;
-    P.nbrA = a.nbr + E * n0; P.nbrB = P.nbrA + E * tn;
-    P.ewA = a.ew + E * n0; P.ewB = P.ewA + E * tn;
+    P.nbrA = a.nbr + eb; P.nbrB = P.nbrA + a.total_e;
+    P.ewA = a.ew + eb; P.ewB = P.ewA + a.total_e;
     const double r = a.r[p];
     const uint64_t token = a.token[p];
     int64_t cnt_levels = 0, cnt_move = 0, cnt_refine = 0, cnt_draws = 0;
@@ -497,7 +498,7 @@ __global__ void __launch_bounds__(LD_WAVE) leiden_kernel(LeidenArgs a) {
     __syncthreads();
     for (int it = 0; it < a.n_iterations && status == LEIDEN_OK; ++it) {
         Level L;
-        L.off = a.g.off + n0 + p; L.nbr = a.g.col + E * n0; L.ew = nullptr;
+        L.off = a.g.off + n0 + p; L.nbr = a.g.col + eb; L.ew = a.ew0 ? a.ew0 + eb : nullptr;
         L.w = a.objective == ICNV_LEIDEN_MODULARITY ? a.g.strength + n0 : nullptr;
         for (int64_t v = lane_id(); v < n; v += LD_WAVE) { P.memb[v] = P.fin[v]; P.aggof[v] = (int32_t)v; }
         __syncthreads();

@@ -699,6 +699,135 @@ def snn_graph(nn_idx, sizes):
     return row_off, col[:int(row_off[-1].item())], strength[:n]
 
 
+def leiden_graph(row_off, col, weight, loop, sizes, objective, resolution, beta=0.01, n_iterations=2, seed=0, tokens=None,
+                 loop_weight=_lib.SNN_WEIGHT_ONE):
+    """`leiden` on a batch of weighted graphs instead of kNN blocks (icnv_leiden_graph_dev, DESIGN K18): the CSR of
+    `snn_jaccard` -- row_off int64 (sum n_p + 1), col int32, weight int64, loop int32 (sum n_p) CUDA tensors.  For CPM the
+    resolution is in units of the weights (the PCA route passes gamma * 2^24).  Returns (membership, n_clusters) as `leiden`."""
+    L = _lib.load()
+    for t, dt, name in ((row_off, torch.int64, "row_off"), (col, torch.int32, "col"), (weight, torch.int64, "weight"),
+                        (loop, torch.int32, "loop")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.dim() == 1 and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous 1-d {dt} CUDA tensor")
+    off = np.zeros(len(sizes) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(np.asarray(sizes, dtype=np.int64))
+    if off[-1] + 1 != row_off.shape[0] or loop.shape[0] < off[-1] or col.shape[0] != weight.shape[0]:
+        raise ValueError("the problem sizes must add up to the rows of the CSR")
+    off, op = i32(off)
+    P = len(sizes)
+    res, rp = f64(np.broadcast_to(np.asarray(resolution, dtype=np.float64), (P,)))
+    tok, tp = _u64([0] * P if tokens is None else tokens)
+    if tok.size != P:
+        raise ValueError("one token per problem")
+    if P and int(row_off[-1].item()) > col.shape[0]:
+        raise ValueError("col and weight are shorter than row_off says")
+    memb = torch.empty(max(int(off[-1]), 1), dtype=torch.int32, device=col.device)
+    ncl = np.zeros(max(P, 1), dtype=np.int32)
+    check(L.icnv_leiden_graph_dev(_ptr(row_off), _ptr(col), _ptr(weight), _ptr(loop), int(loop_weight), op, P,
+                                  _leiden_objective(objective), rp, float(beta), int(n_iterations), int(seed) & (2**64 - 1), tp,
+                                  _ptr(memb), ncl.ctypes.data_as(_lib._ip), _stream()))
+    return memb[:int(off[-1])], ncl[:P]
+
+
+def snn_jaccard(nn_idx, sizes):
+    """Seurat's ComputeSNN (prune.SNN = 1/15) on the kNN blocks of `knn` (icnv_snn_begin_dev / _fill_dev, DESIGN K18).
+    Returns (row_off int64, col int32, shared int32, weight int64, loop int32) CUDA tensors: one ascending CSR over the batch
+    (problem p's rows follow each other, columns are positions within the problem), the shared-neighbour counts s, their
+    24-bit fixed-point Jaccard weights s / (2 k - s) and the loop flags (always 1).  Synchronises the device."""
+    L = _lib.load()
+    off, op = _leiden_offsets(nn_idx, sizes)
+    n, k = int(off[-1]), int(nn_idx.shape[1])
+    h, nnz = ct.c_void_p(0), ct.c_int64(0)
+    check(L.icnv_snn_begin_dev(_ptr(nn_idx), k, op, len(sizes), ct.byref(h), ct.byref(nnz), _stream()))
+    try:
+        dev = nn_idx.device
+        row_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        col = torch.empty(max(nnz.value, 1), dtype=torch.int32, device=dev)
+        shared = torch.empty(max(nnz.value, 1), dtype=torch.int32, device=dev)
+        weight = torch.empty(max(nnz.value, 1), dtype=torch.int64, device=dev)
+        loop = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        check(L.icnv_snn_fill_dev(h, _ptr(row_off), _ptr(col), _ptr(shared), _ptr(weight), _ptr(loop), _stream()))
+    finally:
+        L.icnv_snn_end(h)
+    return row_off, col[:nnz.value], shared[:nnz.value], weight[:nnz.value], loop[:n]
+
+
+def _lpca_lists(x, problems):
+    C, G, ld = _check_matrix_ld(x)
+    gidx, goff = pack_groups([g for g, _ in problems])
+    cidx, coff = pack_groups([c for _, c in problems])
+    return C, G, ld, i32(gidx), i32(goff), i32(cidx), i32(coff)
+
+
+def _check_packed(t, n, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n):
+        raise ValueError(f"{name} must be a contiguous CUDA float64 tensor with one entry per (problem, gene)")
+
+
+def lpca_vstd(x, problems, mean, sd):
+    """The standardised variance of FindVariableFeatures (icnv_lpca_vstd_dev, DESIGN K18) for a batch of (genes, cells)
+    problems: mean and sd = sqrt(10^trend) packed per (problem, gene) as CUDA float64 tensors; returns v_std packed likewise."""
+    L = _lib.load()
+    C, G, ld, (gi, gp), (go, gop), (ci, cp), (co, cop) = _lpca_lists(x, problems)
+    n = int(go[-1]) if go.size else 0
+    _check_packed(mean, n, "mean")
+    _check_packed(sd, n, "sd")
+    out = torch.empty(max(n, 1), dtype=torch.float64, device=x.device)
+    check(L.icnv_lpca_vstd_dev(_ptr(x), G, C, ld, gp, gop, cp, cop, len(problems), _ptr(mean), _ptr(sd), _ptr(out), _stream()))
+    return out[:n]
+
+
+def lpca_z_layout(n_feat, n_cells):
+    """(offsets int64 (P + 1), ldz int64 (P)) of the feature-major blocks of `lpca_scale`: F_p rows of ldz_p = n_p + (n_p & 1)."""
+    n_cells = np.asarray(n_cells, dtype=np.int64)
+    ldz = n_cells + (n_cells & 1)
+    off = np.zeros(len(n_cells) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(np.asarray(n_feat, dtype=np.int64) * ldz)
+    return off, ldz
+
+
+def lpca_scale(x, problems, mean, sd):
+    """ScaleData of the features (icnv_lpca_scale_dev, DESIGN K18): z = min(10, (x - mean) / sd), feature-major blocks packed
+    as `lpca_z_layout` says.  problems: (features, cells); mean, sd packed per (problem, feature)."""
+    L = _lib.load()
+    C, G, ld, (gi, gp), (go, gop), (ci, cp), (co, cop) = _lpca_lists(x, problems)
+    n = int(go[-1]) if go.size else 0
+    _check_packed(mean, n, "mean")
+    _check_packed(sd, n, "sd")
+    off, _ = lpca_z_layout([len(g) for g, _ in problems], [len(c) for _, c in problems])
+    Z = torch.empty(max(int(off[-1]), 1), dtype=torch.float64, device=x.device)
+    check(L.icnv_lpca_scale_dev(_ptr(x), G, C, ld, gp, gop, cp, cop, len(problems), _ptr(mean), _ptr(sd), _ptr(Z), _stream()))
+    return Z[:int(off[-1])]
+
+
+def lpca_gram(Z, n_feat, n_cells):
+    """M_p = Z_p Z_p^T on the matrix cores (icnv_lpca_gram_dev, DESIGN K18): the (F_p, F_p) blocks packed one after another."""
+    L = _lib.load()
+    off, _ = lpca_z_layout(n_feat, n_cells)
+    _check_packed(Z, int(off[-1]), "Z")
+    nf, nfp = i32(n_feat)
+    nc, ncp = i32(n_cells)
+    total = int(np.sum(nf.astype(np.int64) ** 2))
+    M = torch.empty(max(total, 1), dtype=torch.float64, device=Z.device)
+    check(L.icnv_lpca_gram_dev(_ptr(Z), nfp, ncp, nf.size, _ptr(M), _stream()))
+    return M[:total]
+
+
+def lpca_project(Z, V, n_feat, n_cells, npcs, e_ld=10):
+    """E = Z^T V per problem (icnv_lpca_project_dev, DESIGN K18).  V: the (F_p, npcs_p) row-major blocks packed one after
+    another (CUDA float64).  Returns the (sum n_p, e_ld) embedding matrix, rows in problem order, unused components zero."""
+    L = _lib.load()
+    off, _ = lpca_z_layout(n_feat, n_cells)
+    _check_packed(Z, int(off[-1]), "Z")
+    nf, nfp = i32(n_feat)
+    nc, ncp = i32(n_cells)
+    npc, npp = i32(npcs)
+    _check_packed(V, int(np.sum(nf.astype(np.int64) * npc)), "V")
+    E = torch.empty((max(int(nc.sum()), 1), int(e_ld)), dtype=torch.float64, device=Z.device)
+    check(L.icnv_lpca_project_dev(_ptr(Z), _ptr(V), nfp, ncp, npp, nf.size, _ptr(E), int(e_ld), _stream()))
+    return E[:int(nc.sum())]
+
+
 LEIDEN_STATS = ("calls", "problems", "levels", "move_visits", "refine_visits", "draws", "us")
 
 

@@ -13,15 +13,24 @@ distance matrix ever leaving the device.
 
 The random-trees subclustering (R/inferCNV_tumor_subclusters.random_smoothed_trees.R, DESIGN K10) runs its permutation
 statistic on the GPU (icnv_random_trees_dev), one call per recursion level: `define_signif_tumor_subclusters_via_random_smooothed_trees`,
-with the recursion itself in the pure-Python `random_trees_partition`."""
+with the recursion itself in the pure-Python `random_trees_partition`.
+
+The reference's default Leiden route, leiden_method = "PCA" (.leiden_seurat_preprocess_routine, :699-723, DESIGN K18), runs
+its variable-feature statistic, scaling, Gram matrix, projection, SNN graph and weighted Leiden on the GPU (`pca_stages`,
+`leiden_seurat_preprocess_routine`); the trend fit (loess_fit.py) and the eigenpairs of the at most 2000 x 2000 Gram matrix
+(numpy.linalg.eigh) are host work."""
 from __future__ import annotations
 
+import logging
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import device
+from . import _lib, device
 from .infercnv_object import InfercnvObject
+from .loess_fit import loess_fit, window_points
+
+log = logging.getLogger("infercnv_amd")
 
 
 def parallelDist(infercnv_obj: InfercnvObject, cells, as_dist: bool = True):
@@ -390,19 +399,199 @@ def _resolution(leiden_resolution, n):
     return auto_leiden_resolution(n) if isinstance(leiden_resolution, str) and leiden_resolution == "auto" else float(leiden_resolution)
 
 
-def _leiden_problems(x, genes, problems, k_nn, leiden_method, objective, leiden_resolution, leiden_fn):
-    """One K8 call and one Leiden call for every (cells, token) problem: a list of 1-based partitions."""
+# ------------------------------------------------------------------ the PCA route of the Leiden subclustering (DESIGN K18)
+PCA_NFEATURES = 2000        # FindVariableFeatures' nfeatures
+PCA_NPCS = 10               # RunPCA(npcs = 10) (:711)
+FALLBACK_MESSAGE = "Got a warning:\n\t%s\n\nFalling back to simple Leiden clustering for this chromosome.\n"   # :704
+
+
+def vst_trend_sd(mean, var):
+    """The expected standard deviation of FindVariableFeatures' "vst" for one problem's genes: sqrt(10^fit) of the local
+    quadratic trend of log10(var) on log10(mean) (loess_fit.py) over the genes with var > 0, 0 elsewhere.  Returns (sd_e, None),
+    or (None, reason) when the reference's FindVariableFeatures would warn and the route falls back.  A mean <= 0 among the
+    fitted genes is a ValueError (R's loess stops on the NaN)."""
+    mean = np.asarray(mean, dtype=np.float64)
+    var = np.asarray(var, dtype=np.float64)
+    pos = var > 0
+    if np.any(mean[pos] <= 0):
+        raise ValueError("a gene with positive variance has a mean <= 0: log10(mean) is not defined (R's loess stops)")
+    m = int(np.count_nonzero(pos))
+    q = window_points(m)
+    if q < 4:
+        return None, f"span is too small: {q} of {m} genes in a window"
+    fit, ok = loess_fit(np.log10(mean[pos]), np.log10(var[pos]))
+    if not ok:
+        return None, "a window of the trend has fewer than 3 distinct means of positive weight"
+    sd_e = np.zeros(mean.size, dtype=np.float64)
+    sd_e[pos] = np.sqrt(np.power(10.0, fit))
+    return sd_e, None
+
+
+def select_features(v_std, nfeatures=PCA_NFEATURES):
+    """head(order(-v_std), nfeatures): positions by decreasing v_std, ties by position."""
+    v_std = np.asarray(v_std, dtype=np.float64)
+    return np.argsort(-v_std, kind="stable")[:min(int(nfeatures), v_std.size)]
+
+
+def top_eigenvectors(M, npcs):
+    """The top `npcs` eigenvectors of the symmetric M (numpy.linalg.eigh on the host), by decreasing eigenvalue, each with its
+    largest-magnitude entry positive (the first on ties): (values (npcs,), V (F, npcs))."""
+    lam, vec = np.linalg.eigh(np.asarray(M, dtype=np.float64))
+    lam, vec = lam[::-1][:npcs], vec[:, ::-1][:, :npcs]
+    V = np.ascontiguousarray(vec)
+    for j in range(V.shape[1]):
+        if V[int(np.argmax(np.abs(V[:, j]))), j] < 0:
+            V[:, j] = -V[:, j]
+    return lam.copy(), V
+
+
+def pca_stages(x, genes, cells, k_nn, timings=None):
+    """Stages 1-4 of the PCA route (include/icnv.h, K18) for a batch of problems on the (C, G) device matrix x: problem p has
+    the genes genes[p] (list order) and the cells cells[p]; x must be a CUDA tensor (there is no host route:
+    NotImplementedError).  Returns a dict:
+      active / fallback   the problems that went through / the (problem, reason) pairs that fall back to the simple route
+    and, for the active problems in order (device tensors unless noted): mean, var (host, per problem over its genes), sd_e
+    (host), v_std (host), features (host positions within genes[p]), Z, n_feat, n_cells, npcs, M, eigenvalues (host), V (host
+    blocks), E, nn_idx, and the SNN graph row_off, col, shared, weight, loop.  timings: a dict that receives the wall
+    milliseconds of every stage (each stage synchronises the device)."""
+    import time
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        # no quiet host route: every stage but the trend fit and the eigenpairs is a device kernel on the resident matrix
+        raise NotImplementedError('leiden_method = "PCA" is implemented on the device-resident (cells, genes) matrix only; '
+                                  'there is no host route (use "simple" likewise on the device, or partition_method = "none")')
+    t_last = [time.perf_counter()]
+
+    def lap(name):
+        if timings is not None:
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + (now - t_last[0]) * 1e3
+            t_last[0] = now
+
+    P = len(cells)
+    cells = [np.asarray(c, dtype=np.int32) for c in cells]
+    genes = [np.asarray(g, dtype=np.int32) for g in genes]
+    m_all, v_all, _ = device.group_gene_tables(x, cells)
+    lap("moments")
+    out = {"fallback": []}
+    mean, var, sd_e = {}, {}, {}
+    for p in range(P):
+        gi = torch.from_numpy(genes[p].astype(np.int64)).to(x.device)
+        mean[p] = m_all[p, gi].cpu().numpy()
+        var[p] = v_all[p, gi].cpu().numpy()
+        sd_e[p], why = vst_trend_sd(mean[p], var[p])
+        if sd_e[p] is None:
+            out["fallback"].append((p, why))
+    failed = {p for p, _ in out["fallback"]}
+    act = [p for p in range(P) if p not in failed]
+    lap("trend_host")
+
+    def dev(parts):
+        return torch.from_numpy(np.ascontiguousarray(np.concatenate(parts), dtype=np.float64)).to(x.device)
+
+    v_std, feats = {}, {}
+    if act:
+        packed = device.lpca_vstd(x, [(genes[p], cells[p]) for p in act], dev([mean[p] for p in act]),
+                                  dev([sd_e[p] for p in act])).cpu().numpy()
+        g0 = 0
+        for p in act:
+            v_std[p] = packed[g0:g0 + genes[p].size]
+            g0 += genes[p].size
+            feats[p] = select_features(v_std[p])
+            if min(PCA_NPCS, feats[p].size - 1, cells[p].size - 1) < 1:
+                out["fallback"].append((p, "fewer than 2 features or cells: no principal component"))
+        failed = {p for p, _ in out["fallback"]}
+        act = [p for p in act if p not in failed]
+    lap("v_std_and_features")
+    out["fallback"].sort()
+    out["active"] = act
+    out.update(mean=[mean[p] for p in act], var=[var[p] for p in act], sd_e=[sd_e[p] for p in act], v_std=[v_std[p] for p in act],
+               features=[feats[p] for p in act])
+    if not act:
+        return out
+    n_feat = [int(feats[p].size) for p in act]
+    n_cells = [int(cells[p].size) for p in act]
+    npcs = [min(PCA_NPCS, f - 1, n - 1) for f, n in zip(n_feat, n_cells)]
+    Z = device.lpca_scale(x, [(genes[p][feats[p]], cells[p]) for p in act], dev([mean[p][feats[p]] for p in act]),
+                          dev([np.sqrt(var[p][feats[p]]) for p in act]))
+    lap("scale")
+    M = device.lpca_gram(Z, n_feat, n_cells)
+    lap("gram")
+    lam, V, m0 = [], [], 0
+    for f, c in zip(n_feat, npcs):
+        l, v = top_eigenvectors(M[m0:m0 + f * f].reshape(f, f).cpu().numpy(), c)
+        lam.append(l)
+        V.append(v)
+        m0 += f * f
+    lap("eigh_host")
+    E = device.lpca_project(Z, dev([v.ravel() for v in V]), n_feat, n_cells, npcs, PCA_NPCS)
+    lap("project")
+    rows = np.concatenate([[0], np.cumsum(n_cells)])
+    nn_idx, _ = device.knn(E, [(np.arange(c, dtype=np.int32), np.arange(rows[i], rows[i + 1], dtype=np.int32))
+                               for i, c in enumerate(npcs)], k_nn)
+    lap("knn")
+    row_off, col, shared, weight, loop = device.snn_jaccard(nn_idx, n_cells)
+    lap("snn")
+    out.update(Z=Z, n_feat=n_feat, n_cells=n_cells, npcs=npcs, M=M, eigenvalues=lam, V=V, E=E, nn_idx=nn_idx, row_off=row_off, col=col,
+               shared=shared, weight=weight, loop=loop)
+    return out
+
+
+def _device_leiden_graph(seed):
+    def fn(row_off, col, weight, loop, sizes, objective, gammas, tokens):
+        memb, _ = device.leiden_graph(row_off, col, weight, loop, sizes, objective, gammas, LEIDEN_BETA, LEIDEN_ITERATIONS, seed, tokens)
+        return memb.cpu().numpy()
+    return fn
+
+
+def _graph_resolution(objective, gamma):
+    """CPM's resolution in units of the 24-bit fixed-point weights (an exact scaling); modularity's is homogeneous."""
+    return gamma * _lib.SNN_WEIGHT_ONE if objective == "CPM" else gamma
+
+
+def leiden_seurat_preprocess_routine(infercnv_obj: InfercnvObject, cells, k_nn, resolution_parameter, objective_function="CPM",
+                                     genes=None, seed=0, token=0):
+    """.leiden_seurat_preprocess_routine(expr.data[genes, cells], k_nn, resolution_parameter, objective_function)
+    (R/inferCNV_tumor_subclusters.R:699-723) for one problem, by the library's contract (include/icnv.h, K18): a 1-based numpy
+    int32 membership.  Falls back to `leiden_simple_snn` where the reference's FindVariableFeatures would warn."""
+    cells = np.asarray(cells, dtype=np.int32)
+    G = np.asarray(infercnv_obj.expr_data).shape[0]
+    genes = np.arange(G, dtype=np.int32) if genes is None else np.asarray(genes, dtype=np.int32)
+    return _leiden_problems(_to_device(infercnv_obj), [genes], [(cells, token)], k_nn, "PCA", objective_function, resolution_parameter,
+                            _device_leiden(seed), _device_leiden_graph(seed))[0]
+
+
+def _leiden_problems(x, genes, problems, k_nn, leiden_method, objective, leiden_resolution, leiden_fn, leiden_graph_fn=None):
+    """One K8 call and one Leiden call for every (cells, token) problem: a list of 1-based partitions.  leiden_method "PCA":
+    the batch goes through `pca_stages` and the weighted Leiden; the problems that fall back form a batch of the simple route."""
     if not problems:
         return []
+    out = [None] * len(problems)
+    simple = list(range(len(problems)))
     if leiden_method == "PCA":
-        raise NotImplementedError('leiden_method = "PCA" (Seurat vst / irlba / annoy) is not implemented; use "simple"')
-    idx, _ = device.knn(x, [(g, c) for g, (c, _) in zip(genes, problems)], k_nn)
-    sizes = [c.size for c, _ in problems]
-    memb = leiden_fn(idx, sizes, objective, [_resolution(leiden_resolution, n) for n in sizes], [t for _, t in problems])
-    out, r0 = [], 0
-    for n in sizes:
-        out.append(np.asarray(memb[r0:r0 + n]))
-        r0 += n
+        st = pca_stages(x, genes, [c for c, _ in problems], k_nn)
+        for p, why in st["fallback"]:
+            log.info(FALLBACK_MESSAGE, why)
+        simple = [p for p, _ in st["fallback"]]
+        act = st["active"]
+        if act:
+            sizes = st["n_cells"]
+            gammas = [_graph_resolution(objective, _resolution(leiden_resolution, n)) for n in sizes]
+            memb = leiden_graph_fn(st["row_off"], st["col"], st["weight"], st["loop"], sizes, objective, gammas,
+                                   [problems[p][1] for p in act])
+            r0 = 0
+            for p, n in zip(act, sizes):
+                out[p] = np.asarray(memb[r0:r0 + n])
+                r0 += n
+    if simple:
+        idx, _ = device.knn(x, [(genes[p], problems[p][0]) for p in simple], k_nn)
+        sizes = [problems[p][0].size for p in simple]
+        memb = leiden_fn(idx, sizes, objective, [_resolution(leiden_resolution, n) for n in sizes], [problems[p][1] for p in simple])
+        r0 = 0
+        for p, n in zip(simple, sizes):
+            out[p] = np.asarray(memb[r0:r0 + n])
+            r0 += n
     return out
 
 
@@ -411,10 +600,10 @@ def define_signif_tumor_subclusters(infercnv_obj: InfercnvObject, p_val=0.1, k_n
                                     leiden_function_per_chr="modularity", leiden_resolution_per_chr=1, hclust_method="ward.D2",
                                     cluster_by_groups=True, partition_method="leiden", per_chr_hmm_subclusters=False,
                                     per_chr_hmm_subclusters_references=False, z_score_filter=0.8, restrict_to_DE_genes=False,
-                                    seed=0, leiden_fn=None):
-    """define_signif_tumor_subclusters (R/inferCNV_tumor_subclusters.R:2-177) with leiden_method(_per_chr) = "simple" or
-    partition_method = "none", on the GPU: per route one K8 call, one Leiden call (K11) and one K9 call over every group and
-    partition.  Returns (copy of the object with tumor_subclusters = {"hc": {group: ...}, "subclusters": {group: {name:
+                                    seed=0, leiden_fn=None, leiden_graph_fn=None):
+    """define_signif_tumor_subclusters (R/inferCNV_tumor_subclusters.R:2-177) with leiden_method(_per_chr) = "PCA" (the
+    reference's default, K18) or "simple", or partition_method = "none", on the GPU: per route one K8 call, one Leiden call
+    (K11) and one K9 call over every group and partition; the PCA route's stages run as batches before them (`pca_stages`).  Returns (copy of the object with tumor_subclusters = {"hc": {group: ...}, "subclusters": {group: {name:
     0-based cells}}}, subclusters_per_chr or None).
 
     hc[group]: None (< 3 cells), one HClust (k_nn >= n, or "none"), or the list of the partitions' HClust of >= 2 cells in
@@ -422,11 +611,14 @@ def define_signif_tumor_subclusters(infercnv_obj: InfercnvObject, p_val=0.1, k_n
     named "<group>_s<label>", by decreasing size then label (:604) -- ascending label on the per-chromosome route (:687).
     The streams are keyed by seed and FNV-1a-64 of the group name (of chr + "\\0" + group per chromosome); R's are
     igraph's.  leiden_fn(nn_idx, sizes, objective, gammas, tokens) -> 1-based memberships replaces the device Leiden
-    (tests hold the driver to the restatement with it)."""
+    (tests hold the driver to the restatement with it); leiden_graph_fn(row_off, col, weight, loop, sizes, objective, gammas,
+    tokens) is its sibling for the weighted graphs of the PCA route (CUDA tensors of `device.snn_jaccard`; CPM's gammas
+    already in units of the weights)."""
     leiden_method_per_chr = leiden_method_per_chr if per_chr_hmm_subclusters else "simple"
     _check_leiden_args(leiden_method, leiden_function, partition_method, restrict_to_DE_genes)
     _check_leiden_args(leiden_method_per_chr, leiden_function_per_chr, partition_method, False)
     leiden_fn = _device_leiden(seed) if leiden_fn is None else leiden_fn
+    leiden_graph_fn = _device_leiden_graph(seed) if leiden_graph_fn is None else leiden_graph_fn
     kept = zscore_kept_genes(infercnv_obj, z_score_filter)
     if kept.size == 0:
         raise ValueError("the z-score filter keeps no gene (R: expr.data[-integer(0), ] has no row)")
@@ -454,7 +646,7 @@ def define_signif_tumor_subclusters(infercnv_obj: InfercnvObject, p_val=0.1, k_n
                 problems.append((c.astype(np.int32), fnv1a64(g)))
                 keys.append(g)
         parts = _leiden_problems(x, [kept32] * len(problems), problems, k_nn, leiden_method, leiden_function,
-                                 leiden_resolution, leiden_fn)
+                                 leiden_resolution, leiden_fn, leiden_graph_fn)
         for g, (c, _), part in zip(keys, problems, parts):
             labels, sizes = np.unique(part, return_counts=True)
             subclusters[g] = {}
@@ -487,7 +679,7 @@ def define_signif_tumor_subclusters(infercnv_obj: InfercnvObject, p_val=0.1, k_n
             chr_groups = obs if cluster_by_groups else {
                 "all_observations": np.concatenate(list(obs.values())) if obs else np.zeros(0, dtype=np.int64)}
         per_chr = _leiden_per_chr(infercnv_obj, x, kept, chr_groups, k_nn, leiden_method_per_chr, leiden_function_per_chr,
-                                  leiden_resolution_per_chr, leiden_fn)
+                                  leiden_resolution_per_chr, leiden_fn, leiden_graph_fn)
         if not per_chr_hmm_subclusters_references:
             refs = {k: np.asarray(v, dtype=np.int64) for k, v in infercnv_obj.reference_grouped_cell_indices.items()}
             for c in per_chr:
@@ -498,7 +690,7 @@ def define_signif_tumor_subclusters(infercnv_obj: InfercnvObject, p_val=0.1, k_n
     return out, per_chr
 
 
-def _leiden_per_chr(infercnv_obj, x, kept, groups, k_nn, leiden_method, objective, leiden_resolution, leiden_fn):
+def _leiden_per_chr(infercnv_obj, x, kept, groups, k_nn, leiden_method, objective, leiden_resolution, leiden_fn, leiden_graph_fn=None):
     """.whole_dataset_leiden_subclustering_per_chr (R/inferCNV_tumor_subclusters.R:646-697) on the filtered genes."""
     chr_all = np.asarray(infercnv_obj.gene_order.chr).astype(str)
     chrs = chr_all[kept]
@@ -520,7 +712,7 @@ def _leiden_per_chr(infercnv_obj, x, kept, groups, k_nn, leiden_method, objectiv
                 problems.append((cells.astype(np.int32), fnv1a64(f"{c}\0{g}")))
                 genes.append(genes_c)
                 keys.append((c, g))
-    parts = _leiden_problems(x, genes, problems, k_nn, leiden_method, objective, leiden_resolution, leiden_fn)
+    parts = _leiden_problems(x, genes, problems, k_nn, leiden_method, objective, leiden_resolution, leiden_fn, leiden_graph_fn)
     for (c, g), (cells, _), part in zip(keys, problems, parts):
         entries = {}
         for i in np.unique(part):                                            # unique(partition[grouping(partition)])
