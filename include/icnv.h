@@ -1000,7 +1000,9 @@ void icnv_heatmap_stats_reset(void);
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole
  * reference group, cells in stored order -- out[p,q] = median over the clamped
- * (window_size+2)^2 neighbourhood.  Cells in no tile are copied through. */
+ * (window_size+2)^2 neighbourhood.  Cells in no tile are copied through.
+ * A NaN is not looked for: a window that holds one gets a value that depends on
+ * the kernel that served it.  icnv_median_filter_na[_dev] below honours R's NA. */
 int icnv_median_filter(const double *expr_in, double *expr_out, int64_t G, int64_t C,
                        const int32_t *chr_start, int32_t n_chr, const int32_t *tile_idx,
                        const int32_t *tile_off, int32_t n_tiles, int32_t window_size);
@@ -1008,6 +1010,34 @@ int icnv_median_filter_dev(const double *expr_in, double *expr_out, int64_t G, i
                            const int32_t *chr_start, int32_t n_chr, const int32_t *tile_idx,
                            const int32_t *tile_off, int32_t n_tiles, int32_t window_size,
                            void *stream);
+/* The same filter with R's NA result (K19, csrc/median_na_kernels.hip): median() returns NA as soon as its argument holds
+ * one NA or NaN (R/noise_reduction.R:107), so an output is NA exactly when its window holds one.  Opt-in, like
+ * ICNV_ST_NA_AWARE for the chain; icnv_median_filter[_dev] keep their contract and their code path.
+ *   NA        an element whose bits satisfy (bits & 0x7FFFFFFFFFFFFFFF) > 0x7FF0000000000000: any NaN, R's NA_real_
+ *             included (the bits are tested, never x != x).  +-Inf is a number, as in the plain entry.
+ *   blocks    as icnv_median_filter: one block per (tile, chromosome) pair, a tile's cells in the order of its index list.
+ *   window    of output (p, q) of an n x m block, 1-based: [max(1, p - h), min(n, p + h)] x [max(1, q - h), min(m, q + h)]
+ *             with h = (window_size - 1) / 2 + 1.  The reference's ifelse pairs (:102-106) reduce to exactly this clamp:
+ *             `p <= h ? 1 : p - h` is max(1, p - h), and `p >= n - h ? n : p + h` is min(n, p + h).
+ *   tiled     out[p, q] = NA_real_ (bits 0x7FF00000000007A2) if the window holds at least one NA; otherwise bit for bit
+ *             what icnv_median_filter returns for that output on the same input -- whatever the NAs elsewhere hold.
+ *   untiled   cells in no tile are copied through bit for bit, NaN payloads included; they poison nothing.
+ *   n_na_out  HOST, nullable: the number of NA elements of the matrix, tiled or not.
+ * Refusals, window_size limits and the aliasing rule are icnv_median_filter's, checked before any launch.  A cell listed in
+ * several tiles is NA if one of its windows holds an NA and otherwise as the plain entry leaves it.  The entry reads the
+ * matrix once to look for NAs (a bit mask of G * C / 8 bytes of pool scratch), WAITS for the count on `stream` -- the one
+ * host wait, so it cannot be captured into a graph -- and without an NA launches the plain filter on the caller's input.
+ * With NAs it filters a cleaned copy (G * C doubles of pool scratch) and stores the NAs of the dilated mask afterwards.
+ * The host-buffer entry deals whole tiles to the devices of icnv_set_devices as icnv_median_filter does.
+ * Timer names: "median_na_scan", "median_na_clean", "median_na_fixup" (and the plain filter's "median_filter"). */
+int icnv_median_filter_na(const double *expr_in, double *expr_out, int64_t G, int64_t C,
+                          const int32_t *chr_start, int32_t n_chr, const int32_t *tile_idx,
+                          const int32_t *tile_off, int32_t n_tiles, int32_t window_size,
+                          int64_t *n_na_out);
+int icnv_median_filter_na_dev(const double *expr_in, double *expr_out, int64_t G, int64_t C,
+                              const int32_t *chr_start, int32_t n_chr, const int32_t *tile_idx,
+                              const int32_t *tile_off, int32_t n_tiles, int32_t window_size,
+                              int64_t *n_na_out /* HOST, nullable */, void *stream);
 
 /* ---- profiling hooks (used by bench.py) --------------------------------- */
 /* When enabled, every kernel launch is bracketed by hipEvents recorded on the

@@ -207,6 +207,8 @@ PROTOTYPES = {
     "icnv_cells_moments_partial_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _i64, ct.c_int32, ct.c_double, _dp, _vp]),
     "icnv_median_filter": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _i32, _ip, _ip, _i32, _i32]),
     "icnv_median_filter_dev": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _i32, _ip, _ip, _i32, _i32, _vp]),
+    "icnv_median_filter_na": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _i32, _ip, _ip, _i32, _i32, ct.POINTER(ct.c_int64)]),
+    "icnv_median_filter_na_dev": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _i32, _ip, _ip, _i32, _i32, ct.POINTER(ct.c_int64), _vp]),
     "icnv_timing_enable": (None, [ct.c_int]),
     "icnv_timing_reset": (None, []),
     "icnv_timing_get": (ct.c_int, [ct.c_char_p, _dp, ct.POINTER(_i64)]),

@@ -3170,15 +3170,19 @@ int icnv_median_filter_dev(const double *expr_in, double *expr_out, int64_t G, i
 namespace icnv {
 int median_filter_host_one(const double *expr_in, double *expr_out, int64_t G, int64_t C, const int32_t *chr_start,
                            int32_t n_chr, const int32_t *tile_idx, const int32_t *tile_off, int32_t n_tiles,
-                           int32_t window_size) {
+                           int32_t window_size, bool na_aware, int64_t *n_na_out) {
     if (!expr_in || !expr_out) ICNV_FAIL(ICNV_ERR_ARG, "null argument");
     MatrixLease in;
     DevBuf dout;
     int rc;
     const size_t bytes = (size_t)G * (size_t)C * sizeof(double);
     if ((rc = acquire_input(expr_in, G * C, nullptr, in)) || (rc = dout.alloc(bytes))) return rc;
-    rc = icnv_median_filter_dev(in.dev, dout.as<double>(), G, C, chr_start, n_chr, tile_idx, tile_off, n_tiles,
-                                window_size, nullptr);
+    if (na_aware)
+        rc = icnv_median_filter_na_dev(in.dev, dout.as<double>(), G, C, chr_start, n_chr, tile_idx, tile_off, n_tiles,
+                                       window_size, n_na_out, nullptr);
+    else
+        rc = icnv_median_filter_dev(in.dev, dout.as<double>(), G, C, chr_start, n_chr, tile_idx, tile_off, n_tiles,
+                                    window_size, nullptr);
     if (rc) return rc;
     ICNV_HIP(hipMemcpy(expr_out, dout.p, bytes, hipMemcpyDeviceToHost));
     publish_output(expr_out, G * C, std::move(dout));

@@ -980,8 +980,11 @@ int icnv_viterbi_groups(const double *expr, uint8_t *states, int64_t G, int64_t 
     return ICNV_OK;
 }
 
-int icnv_median_filter(const double *expr_in, double *expr_out, int64_t G, int64_t C, const int32_t *chr_start, int32_t n_chr,
-                       const int32_t *tile_idx, const int32_t *tile_off, int32_t n_tiles, int32_t window_size) {
+// icnv_median_filter and icnv_median_filter_na: the same dealing of whole tiles; the NA-aware one (na_aware) calls the NA-aware
+// device entry per device and adds up the NA counts -- every tiled cell sits on one device, the untiled ones are counted here
+static int median_filter_host(const double *expr_in, double *expr_out, int64_t G, int64_t C, const int32_t *chr_start, int32_t n_chr,
+                              const int32_t *tile_idx, const int32_t *tile_off, int32_t n_tiles, int32_t window_size, bool na_aware,
+                              int64_t *n_na_out) {
     if (!expr_in || !expr_out || G < 1 || C < 0) ICNV_FAIL(ICNV_ERR_ARG, "bad argument");
     if (expr_in == expr_out) ICNV_FAIL(ICNV_ERR_ARG, "median filter cannot run in place");   // (as the one-device path)
     const int nd = (int)std::max<int64_t>(1, std::min<int64_t>(g_ndev.load(), n_tiles));
@@ -994,14 +997,28 @@ int icnv_median_filter(const double *expr_in, double *expr_out, int64_t G, int64
             seen[(size_t)tile_idx[i]] = 1;
         }
     }
-    if (nd == 1 || !disjoint) return median_filter_host_one(expr_in, expr_out, G, C, chr_start, n_chr, tile_idx, tile_off, n_tiles, window_size);
+    if (nd == 1 || !disjoint)
+        return median_filter_host_one(expr_in, expr_out, G, C, chr_start, n_chr, tile_idx, tile_off, n_tiles, window_size, na_aware, n_na_out);
     std::vector<GroupDeal> deal;
     deal_groups(tile_idx, tile_off, n_tiles, nd, C, deal);
     std::vector<char> covered((size_t)std::max<int64_t>(C, 1), 0);
     for (int32_t i = 0; i < tile_off[n_tiles]; ++i) covered[(size_t)tile_idx[i]] = 1;
     for (int64_t c = 0; c < C; ++c)   // cells in no tile pass through (R/noise_reduction.R:57-86 touches the tiles only)
         if (!covered[(size_t)c]) std::memcpy(expr_out + c * G, expr_in + c * G, (size_t)G * sizeof(double));
-    return on_devices(nd, [&](int w, hipStream_t s, int rc0) -> int {
+    std::atomic<int64_t> na_total{0};
+    if (na_aware) {
+        int64_t n_na = 0;
+        for (int64_t c = 0; c < C; ++c) {
+            if (covered[(size_t)c]) continue;
+            for (int64_t g = 0; g < G; ++g) {
+                uint64_t bits;
+                std::memcpy(&bits, expr_in + c * G + g, sizeof(bits));
+                n_na += (bits & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull;
+            }
+        }
+        na_total += n_na;
+    }
+    int rc_all = on_devices(nd, [&](int w, hipStream_t s, int rc0) -> int {
         if (rc0) return rc0;
         const GroupDeal &d = deal[(size_t)w];
         const int64_t nc = (int64_t)d.cells.size();
@@ -1012,14 +1029,32 @@ int icnv_median_filter(const double *expr_in, double *expr_out, int64_t G, int64
         int r;
         if ((r = dx.alloc(xin.size() * sizeof(double))) || (r = dout.alloc(xin.size() * sizeof(double)))) return r;
         ICNV_HIP(hipMemcpyAsync(dx.p, xin.data(), xin.size() * sizeof(double), hipMemcpyHostToDevice, s));
-        if ((r = icnv_median_filter_dev(dx.as<double>(), dout.as<double>(), G, nc, chr_start, n_chr, d.idx.data(), d.off.data(),
-                                        (int32_t)d.gids.size(), window_size, s)))
+        if (na_aware) {
+            int64_t n_na = 0;
+            if ((r = icnv_median_filter_na_dev(dx.as<double>(), dout.as<double>(), G, nc, chr_start, n_chr, d.idx.data(), d.off.data(),
+                                               (int32_t)d.gids.size(), window_size, &n_na, s)))
+                return r;
+            na_total += n_na;
+        } else if ((r = icnv_median_filter_dev(dx.as<double>(), dout.as<double>(), G, nc, chr_start, n_chr, d.idx.data(), d.off.data(),
+                                               (int32_t)d.gids.size(), window_size, s)))
             return r;
         ICNV_HIP(hipMemcpyAsync(xin.data(), dout.p, xin.size() * sizeof(double), hipMemcpyDeviceToHost, s));
         ICNV_HIP(hipStreamSynchronize(s));
         for (int64_t j = 0; j < nc; ++j) std::memcpy(expr_out + (int64_t)d.cells[(size_t)j] * G, &xin[(size_t)(j * G)], (size_t)G * sizeof(double));
         return ICNV_OK;
     });
+    if (!rc_all && n_na_out) *n_na_out = na_total.load();
+    return rc_all;
+}
+
+int icnv_median_filter(const double *expr_in, double *expr_out, int64_t G, int64_t C, const int32_t *chr_start, int32_t n_chr,
+                       const int32_t *tile_idx, const int32_t *tile_off, int32_t n_tiles, int32_t window_size) {
+    return median_filter_host(expr_in, expr_out, G, C, chr_start, n_chr, tile_idx, tile_off, n_tiles, window_size, false, nullptr);
+}
+
+int icnv_median_filter_na(const double *expr_in, double *expr_out, int64_t G, int64_t C, const int32_t *chr_start, int32_t n_chr,
+                          const int32_t *tile_idx, const int32_t *tile_off, int32_t n_tiles, int32_t window_size, int64_t *n_na_out) {
+    return median_filter_host(expr_in, expr_out, G, C, chr_start, n_chr, tile_idx, tile_off, n_tiles, window_size, true, n_na_out);
 }
 
 }  // extern "C"

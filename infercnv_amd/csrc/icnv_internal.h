@@ -59,7 +59,8 @@ int viterbi_groups_host_one(const double *expr, uint8_t *states, int64_t G, int6
                             const int32_t *grp_idx, const int32_t *grp_off, int32_t n_grp, int32_t K, const double *mean,
                             const double *sd_shared_per_grp, const double *logPi, const double *logDelta);
 int median_filter_host_one(const double *expr_in, double *expr_out, int64_t G, int64_t C, const int32_t *chr_start, int32_t n_chr,
-                           const int32_t *tile_idx, const int32_t *tile_off, int32_t n_tiles, int32_t window_size);
+                           const int32_t *tile_idx, const int32_t *tile_off, int32_t n_tiles, int32_t window_size,
+                           bool na_aware = false, int64_t *n_na_out = nullptr);   // (na_aware: through icnv_median_filter_na_dev)
 // api.hip: the fused apply pass over the columns [c0, c1) of the chain's matrix (the reference statistics are in place);
 // -1000 when this chain needs the whole-matrix call (three-pass chain, noise_logistic, HMM input without a denoise stage)
 int chain_apply_columns(icnv_chain_t *ch, const double *expr_in, double *expr_out, double *pre_denoise, int64_t c0, int64_t c1,

@@ -1205,8 +1205,13 @@ def cells_moments_partial(x, cell_idx, phase, mean=0.0):
 
 
 # ------------------------------------------------------------------ median filter
-def median_filter(x, chr_start, tiles, window_size=7, out=None):
-    """apply_median_filtering (R/noise_reduction.R:43-113) on device tensors."""
+def median_filter(x, chr_start, tiles, window_size=7, out=None, na_aware=False, return_na_count=False):
+    """apply_median_filtering (R/noise_reduction.R:43-113) on device tensors.  The plain entry does not look for NaN;
+    na_aware=True takes icnv_median_filter_na_dev: an output whose window holds a NaN is R's NA_real_, every other output is
+    the plain entry's bit for bit (one extra read of the matrix and one host wait for the NA count).  return_na_count=True
+    (with na_aware) returns (out, number of NA elements of x)."""
+    if return_na_count and not na_aware:
+        raise ValueError("return_na_count needs na_aware=True: the plain entry does not look for NaN")
     L = _lib.load()
     C, G = _check_matrix(x)
     cs, cp = i32(chr_start)
@@ -1215,6 +1220,11 @@ def median_filter(x, chr_start, tiles, window_size=7, out=None):
     off, op = i32(off)
     if out is None:
         out = torch.empty_like(x)
+    if na_aware:
+        n_na = ct.c_int64(0)
+        check(L.icnv_median_filter_na_dev(_ptr(x), _ptr(out), G, C, cp, cs.size - 1, ip, op, len(tiles), int(window_size),
+                                          ct.byref(n_na), _stream()))
+        return (out, n_na.value) if return_na_count else out
     check(L.icnv_median_filter_dev(_ptr(x), _ptr(out), G, C, cp, cs.size - 1, ip, op, len(tiles), int(window_size),
                                    _stream()))
     return out

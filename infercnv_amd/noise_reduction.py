@@ -35,8 +35,13 @@ def apply_median_filtering(infercnv_obj: InfercnvObject, window_size=7, on_obser
     idx, ip = i32(idx)
     off, op = i32(off)
     out = np.empty_like(x, order="F")
-    check(L.icnv_median_filter(x.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), G, C, cp, cs.size - 1,
-                               ip, op, len(tiles), int(window_size)))
+    if np.isnan(x).any():
+        # median() is NA as soon as its window holds one NA (:107): the NA-aware entry, as ops._run_chain picks ICNV_ST_NA_AWARE
+        check(L.icnv_median_filter_na(x.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), G, C, cp, cs.size - 1,
+                                      ip, op, len(tiles), int(window_size), None))
+    else:
+        check(L.icnv_median_filter(x.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), G, C, cp, cs.size - 1,
+                                   ip, op, len(tiles), int(window_size)))
     if perm is not None:
         inv = np.empty_like(perm)
         inv[perm] = np.arange(perm.size)

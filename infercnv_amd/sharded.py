@@ -170,9 +170,9 @@ class DeviceGroupEngine:
         from . import device
         return device.viterbi_groups(x_local, chr_start, groups_local, means, sds, logPi, logDelta)[0]
 
-    def median_filter(self, x_local, chr_start, tiles_local, window_size):
+    def median_filter(self, x_local, chr_start, tiles_local, window_size, na_aware=False):
         from . import device
-        return device.median_filter(x_local, chr_start, tiles_local, window_size)
+        return device.median_filter(x_local, chr_start, tiles_local, window_size, na_aware=na_aware)
 
 
 class ShardedGroupHMM:
@@ -242,12 +242,16 @@ class ShardedGroupHMM:
 
 class ShardedMedianFilter:
     """apply_median_filtering (R/noise_reduction.R:43-113) on a cell-sharded matrix whose tiles are whole on their ranks:
-    rank-local, no collective."""
+    rank-local, no collective.  na_aware=True gives R's NA result (device.median_filter): a rank whose shard holds no NaN
+    takes the plain launches, one that holds some takes the cleaned copy -- the filter has no collective and a window never
+    leaves its tile, so every rank may decide for itself."""
 
     def __init__(self, engine=None):
         self.engine = engine or DeviceGroupEngine()
 
-    def run(self, x_local, chr_start, tiles_local, window_size=7):
+    def run(self, x_local, chr_start, tiles_local, window_size=7, na_aware=False):
+        if na_aware:      # (an engine without the keyword refuses: no silent fall-back to the plain filter)
+            return self.engine.median_filter(x_local, chr_start, tiles_local, window_size, na_aware=True)
         return self.engine.median_filter(x_local, chr_start, tiles_local, window_size)
 
 
