@@ -996,6 +996,57 @@ int icnv_heatmap_raster(const double *x, int64_t G, int64_t C, const int32_t *or
 int icnv_heatmap_stats(int64_t *out, int32_t n);
 void icnv_heatmap_stats_reset(void);
 
+/* ---- matrix files of plot_cnv (K20) ---------------------------------------------------------------------------------------
+ * The text of `expr.<name>.dat`, `<name>.observations.txt`, `<name>.references.txt` and `General_HCL_<g>_members.txt`, which
+ * plot_cnv writes with write.table (R/inferCNV_heatmap.R:147 expr.<name>.dat, :672 and :774 the members files, :906 the
+ * observations, :1197 the references).  DESIGN.md section 4 K20, restated in tests/table_text_restate.py.  Not yet bound in
+ * the R shim.  R's own bytes are believed, not verified against an R run: the rule below is the one K17's host writer states.
+ *
+ * The text of one field, for a double x:
+ *   NaN gives `NaN`, +-Inf gives `Inf` / `-Inf`, +-0 gives `0`.
+ *   Otherwise take the 15 significant decimal digits of |x|, correctly rounded, ties to even on the exact binary value
+ *   (this is what "%.14e" gives): digits D, decimal exponent E.  Drop trailing zeros.  Use fixed notation unless scientific
+ *   notation is strictly narrower.  Scientific notation is d[.ddd]e+-XX, with a two-digit exponent and three digits from 100
+ *   on.  A negative number starts with `-`.  A field is at most 22 bytes.
+ * A file row is the optional label bytes and the separator, then the fields joined by the separator, then `\n`.
+ * Element (gene g, cell c) sits at x[c * ld + g].  Two orientations:
+ *   ICNV_TABLE_GENE_ROWS  the table has G rows; file row i is gene i, its fields run over cells[0 .. n_cells) in that order.
+ *   ICNV_TABLE_CELL_ROWS  the table has n_cells rows; file row i is cell cells[i], its fields run over the genes 0 .. G - 1.
+ * The call formats the file rows row0 .. row0 + n_rows - 1 into `out` (capacity bytes; DEVICE in the _dev flavour, HOST
+ * otherwise) and stops before the first row that does not fit: *rows_done rows (>= 1) take *n_bytes bytes, row i of them at
+ * row_offsets[i] .. row_offsets[i + 1] (HOST [n_rows + 1], nullable; entries 0 .. *rows_done are written).  A caller streams a
+ * file in chunks of whole rows by calling again with row0 + *rows_done.  One call attempts as many rows as fit when every
+ * field takes its 22 bytes (at least one row), so it may stop before the capacity is used up.
+ * cells, labels and label_off are HOST arrays.  label_off [n_rows + 1] (nullable: no labels, and then labels must be null):
+ * the label of file row row0 + i is labels[label_off[i] .. label_off[i + 1]), written as it is (the caller quotes);
+ * label_off[0] = 0.  An empty label is still followed by the separator.  sep: a C string of exactly one byte.
+ * ICNV_ERR_ARG before any launch: a null x, cells, sep, out, rows_done or n_bytes; G or C outside 1 .. 2^31 - 1; ld < G; an
+ *   unknown orientation; n_cells outside 1 .. 2^31 - 1; a list entry outside 0 .. C - 1; an empty row range or one that leaves
+ *   the table; sep not one byte; label offsets that do not start at 0 or descend, or come without label bytes (or bytes
+ *   without offsets); a capacity below the shortest row possible (label, separator, one-byte fields).  A capacity below
+ *   the actual first row is ICNV_ERR_ARG too, found after the lengths pass.  ICNV_ERR_UNSUPPORTED: a chunk of more than
+ *   2^31 - 1 elements.  On an error *rows_done, *n_bytes and row_offsets are left as they were; `out` is written only by
+ *   a call that succeeds.  The call synchronises the stream.
+ * Method: a digits pass computes D = round(|x| 10^(14 - E)) in integer arithmetic from a 128-bit power-of-ten table and
+ *   certifies the rounding; the elements it cannot certify -- every exact tie among them -- are formatted on the host with
+ *   snprintf("%.14e") and their records replaced before any length is used.  A lengths pass sums the bytes of 256-field
+ *   segments and of rows; the rows' offsets are scanned on the host.  An emit pass assembles each segment in LDS and stores
+ *   it in aligned 16-byte words.  Timer names: "table_text_digits", "table_text_collect", "table_text_lengths",
+ *   "table_text_emit". */
+#define ICNV_TABLE_GENE_ROWS 0
+#define ICNV_TABLE_CELL_ROWS 1
+int icnv_format_table_dev(const double *x, int64_t ld, int64_t G, int64_t C, int32_t orientation, int64_t row0, int64_t n_rows,
+                          const int32_t *cells, int64_t n_cells, const uint8_t *labels, const int64_t *label_off, const char *sep,
+                          uint8_t *out, int64_t capacity, int64_t *row_offsets, int64_t *rows_done, int64_t *n_bytes, void *stream);
+int icnv_format_table(const double *x, int64_t G, int64_t C, int32_t orientation, int64_t row0, int64_t n_rows, const int32_t *cells,
+                      int64_t n_cells, const uint8_t *labels, const int64_t *label_off, const char *sep, uint8_t *out, int64_t capacity,
+                      int64_t *row_offsets, int64_t *rows_done, int64_t *n_bytes);
+/* Counters since the last reset, n = int64 slots (<= 7 written); a refused call counts nowhere:
+ *   out[0] calls   out[1] rows written   out[2] elements that went through the digits pass   out[3] elements formatted on the host
+ *   out[4] bytes written   out[5] extra collection rounds (more than 65536 flagged elements at once)   out[6] wall microseconds */
+int icnv_table_text_stats(int64_t *out, int32_t n);
+void icnv_table_text_stats_reset(void);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

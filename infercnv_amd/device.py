@@ -210,6 +210,89 @@ def heatmap_stats(reset=False):
     return dict(zip(HEATMAP_STATS, (int(v) for v in out)))
 
 
+# ------------------------------------------------------------------ matrix files of plot_cnv (DESIGN K20)
+TABLE_ORIENTATIONS = {"gene_rows": _lib.TABLE_GENE_ROWS, "cell_rows": _lib.TABLE_CELL_ROWS}   # ICNV_TABLE_* of include/icnv.h
+
+
+def pack_labels(labels):
+    """Row labels (str or bytes, written as they are) as (uint8 bytes, int64 offsets [n + 1]) for format_table_into."""
+    enc = [l if isinstance(l, bytes) else str(l).encode("utf-8") for l in labels]
+    off = np.zeros(len(enc) + 1, dtype=np.int64)
+    np.cumsum([len(b) for b in enc], out=off[1:])
+    return np.frombuffer(b"".join(enc) + b"\0", dtype=np.uint8), off
+
+
+def format_table_into(x, out, row0, n_rows, cells, orientation, packed_labels=None, sep=" "):
+    """icnv_format_table_dev into `out`, a contiguous CUDA uint8 tensor whose size is the capacity: the file rows row0 ..
+    row0 + n_rows - 1, as many as the call attempts and `out` holds.  cells: a contiguous int32 numpy array.  packed_labels:
+    pack_labels() of the labels of ALL rows of the table (the range is cut out here), or None.  Returns (rows done, bytes,
+    int64 row offsets [rows done + 1]).  Synchronises the stream."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous()):
+        raise TypeError("out must be a contiguous one-dimensional CUDA uint8 tensor")
+    if not (isinstance(cells, np.ndarray) and cells.dtype == np.int32 and cells.flags.c_contiguous):
+        raise TypeError("cells must be a contiguous int32 numpy array")
+    sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
+    row0, n_rows = int(row0), int(n_rows)
+    labp, offp, off = None, None, None
+    if packed_labels is not None:
+        lab, off_all = packed_labels
+        if row0 < 0 or n_rows < 0 or row0 + n_rows + 1 > off_all.size:
+            raise ValueError("the labels do not cover the row range")
+        off = np.ascontiguousarray(off_all[row0:row0 + n_rows + 1] - off_all[row0])
+        offp = off.ctypes.data_as(ct.POINTER(ct.c_int64))
+        labp = ct.c_void_p(lab.ctypes.data + int(off_all[row0]))
+    offsets = np.zeros(max(n_rows, 0) + 1, dtype=np.int64)
+    done, nbytes = ct.c_int64(0), ct.c_int64(0)
+    check(L.icnv_format_table_dev(_ptr(x), int(ld), G, C, int(orientation), row0, n_rows, cells.ctypes.data_as(ct.POINTER(ct.c_int32)),
+                                  int(cells.size), labp, offp, sep_b, _ptr(out), int(out.numel()),
+                                  offsets.ctypes.data_as(ct.POINTER(ct.c_int64)), ct.byref(done), ct.byref(nbytes), _stream()))
+    return int(done.value), int(nbytes.value), offsets[:int(done.value) + 1]
+
+
+def format_table(x, *, rows, cells, orientation, labels=None, sep=" ", out=None, capacity=None):
+    """A chunk of a matrix file as R's write.table prints it (icnv_format_table_dev, DESIGN K20): every number with 15
+    significant digits, correctly rounded, trailing zeros dropped, fixed notation unless scientific is strictly narrower.
+    x: (C, G) CUDA float64 with contiguous rows (a padded_matrix is fine).  orientation "gene_rows": file row i is gene i and
+    its fields run over `cells` in the order given; "cell_rows": file row i is cell cells[i] and its fields run over all
+    genes.  rows = (first file row, number of rows).  labels: one str or bytes per row of the range, written as it is before
+    the row's first separator (None: no labels).  out: a CUDA uint8 tensor that serves as the device buffer (its size is the
+    capacity; default: `capacity` bytes, or what the range needs when every field takes its 22 bytes).  Returns (bytes, rows
+    done): the call stops before the first row that does not fit, and a caller goes on from there."""
+    C, G, _ = _check_matrix_ld(x)
+    row0, n_rows = (int(v) for v in rows)
+    cells = np.ascontiguousarray(cells, dtype=np.int32)
+    code = TABLE_ORIENTATIONS[orientation] if isinstance(orientation, str) else int(orientation)
+    packed = None
+    if labels is not None:
+        if len(labels) != n_rows:
+            raise ValueError("one label per row of the range")
+        lab, off = pack_labels(labels)
+        packed = (lab, np.concatenate([np.zeros(max(row0, 0), dtype=np.int64), off]))   # rows before the range: no bytes
+    if out is None:
+        if capacity is None:
+            n_fields = cells.size if code == _lib.TABLE_GENE_ROWS else G
+            capacity = max(n_rows, 1) * max(n_fields, 1) * 23 + (int(packed[1][-1]) + n_rows if packed else 0)
+        out = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=x.device)
+    done, nbytes, _ = format_table_into(x, out, row0, n_rows, cells, code, packed, sep)
+    return out[:nbytes].cpu().numpy().tobytes(), done
+
+
+TABLE_TEXT_STATS = ("calls", "rows", "elements", "host_formatted", "bytes", "collect_rounds", "us")
+
+
+def table_text_stats(reset=False):
+    """icnv_table_text_stats as a dict (`host_formatted`: elements the digits pass could not certify, formatted by the host;
+    `us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(TABLE_TEXT_STATS))()
+    check(L.icnv_table_text_stats(out, len(TABLE_TEXT_STATS)))
+    if reset:
+        L.icnv_table_text_stats_reset()
+    return dict(zip(TABLE_TEXT_STATS, (int(v) for v in out)))
+
+
 def smooth_chain_windows(x, chr_start, ref_groups, table, max_thresh=3.0, use_bounds=True, sd_amplifier=1.5, noise_filter=None,
                          denoise=True, want_pre_denoise=False):
     """smooth_chain with step 10 replaced by the window operator (smooth_method "runmeans" / "coordinates"): the chain with

@@ -16,9 +16,13 @@ Believed, not verified against an R run (R is not installed where this was writt
 from __future__ import annotations
 
 import json
+import locale
 import math
 import os
+import queue
 import struct
+import threading
+import time
 import zlib
 
 import numpy as np
@@ -161,6 +165,98 @@ def write_table(path, rows, row_names=None, col_names=None, quote=True, sep=" ")
             if row_names is not None:
                 cells.insert(0, fmt(str(row_names[i])))
             f.write(sep.join(cells) + "\n")
+
+
+
+TABLE_TEXT_CHUNK = 256 << 20       # bytes of one chunk of write_matrix; ICNV_TABLE_TEXT_CHUNK (developer switch) overrides it
+
+
+def write_matrix(path, x, cells, orientation, row_names=None, col_names=None, quote=True, sep=" "):
+    """write.table of a matrix that lives on the device (DESIGN K20): the file write_table writes for the same names, with the
+    numbers formatted by device.format_table_into instead of r_num.  x: (C, G) CUDA float64 with contiguous rows.
+    orientation "gene_rows": one line per gene, its numbers over `cells` in the order given (expr.<name>.dat, the
+    observations / references files, the one-member General_HCL file); "cell_rows": one line per listed cell, its numbers
+    over all genes (the other members files).  row_names: one per line, or None.
+
+    The header line is written here.  The body is streamed in chunks of whole rows through two device buffers and two pinned
+    host buffers: while the library formats chunk i + 1, chunk i is copied to the host on a second stream and a writer thread
+    hands chunk i - 1 to the file.  Returns a dict of counts and seconds (format_s: inside the library; copy_wait_s and
+    write_s: the writer thread waiting for a copy and inside f.write; stall_s: this thread waiting for a free buffer)."""
+    code = device.TABLE_ORIENTATIONS[orientation]
+    C, G = x.shape
+    cells = np.ascontiguousarray(cells, dtype=np.int32)
+    n_rows, n_fields = (G, cells.size) if code == device._lib.TABLE_GENE_ROWS else (cells.size, G)
+    enc = locale.getpreferredencoding(False)
+    fmt = lambda v: _q(v) if quote else str(v)
+    packed = None
+    if row_names is not None:
+        if len(row_names) != n_rows:
+            raise ValueError("one row name per line")
+        packed = device.pack_labels([fmt(str(r)).encode(enc) for r in row_names])
+    worst = n_rows * n_fields * 23 + (int(packed[1][-1]) + n_rows if packed else 0)
+    cap = max(1, min(int(os.environ.get("ICNV_TABLE_TEXT_CHUNK", TABLE_TEXT_CHUNK)), worst))
+    stats = {"bytes": 0, "chunks": 0, "format_s": 0.0, "copy_wait_s": 0.0, "write_s": 0.0, "stall_s": 0.0}
+    dev = [torch.empty(cap, dtype=torch.uint8, device=x.device) for _ in range(2)]
+    pin = [torch.empty(cap, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+    copy_stream = torch.cuda.Stream(device=x.device)
+    jobs, free, failure = queue.Queue(), [threading.Semaphore(1), threading.Semaphore(1)], []
+    t_start = time.perf_counter()
+    with open(path, "wb") as f:
+        if col_names is not None:
+            f.write((sep.join(fmt(str(c)) for c in col_names) + "\n").encode(enc))
+
+        def writer():
+            while True:
+                job = jobs.get()
+                if job is None:
+                    return
+                slot, nbytes, event = job
+                try:
+                    if not failure:
+                        t0 = time.perf_counter()
+                        event.synchronize()
+                        t1 = time.perf_counter()
+                        f.write(memoryview(pin[slot].numpy())[:nbytes])
+                        stats["copy_wait_s"] += t1 - t0
+                        stats["write_s"] += time.perf_counter() - t1
+                except Exception as exc:          # handed to the caller's thread below
+                    failure.append(exc)
+                finally:
+                    free[slot].release()
+
+        thread = threading.Thread(target=writer, daemon=True)
+        thread.start()
+        try:
+            row, i = 0, 0
+            while row < n_rows and not failure:
+                slot = i % 2
+                t0 = time.perf_counter()
+                free[slot].acquire()               # chunk i - 2 has left this pair of buffers
+                t1 = time.perf_counter()
+                try:
+                    done, nbytes, _ = device.format_table_into(x, dev[slot], row, n_rows - row, cells, code, packed, sep)
+                except Exception:
+                    free[slot].release()
+                    raise
+                stats["stall_s"] += t1 - t0
+                stats["format_s"] += time.perf_counter() - t1
+                copy_stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(copy_stream):
+                    pin[slot][:nbytes].copy_(dev[slot][:nbytes], non_blocking=True)
+                    event = torch.cuda.Event()
+                    event.record(copy_stream)
+                jobs.put((slot, nbytes, event))
+                row += done
+                i += 1
+                stats["bytes"] += nbytes
+                stats["chunks"] += 1
+        finally:
+            jobs.put(None)
+            thread.join()
+        if failure:
+            raise failure[0]
+    stats["wall_s"] = time.perf_counter() - t_start
+    return stats
 
 
 # ------------------------------------------------------------------ PNG
@@ -431,8 +527,8 @@ def plot_cnv(infercnv_obj: InfercnvObject, out_dir=".", title="inferCNV", obs_ti
     x = torch.from_numpy(np.ascontiguousarray(expr.T)).cuda()
     out = lambda name: os.path.join(out_dir, name)
 
-    if write_expr_matrix:
-        write_table(out(f"expr.{output_filename}.dat"), expr.tolist(), genes, cells, quote=False, sep="\t")
+    if write_expr_matrix:                        # (the matrix as it came, before the clamp)
+        write_matrix(out(f"expr.{output_filename}.dat"), x, np.arange(C), "gene_rows", genes, cells, quote=False, sep="\t")
 
     if x_range is None:
         mm = device.quantiles_excluding(x, float("nan"), (0.0, 1.0))
@@ -474,17 +570,14 @@ def plot_cnv(infercnv_obj: InfercnvObject, out_dir=".", title="inferCNV", obs_ti
 
     ordered, split, ann, seps, members = observation_order(obj, x, obs_cells, obs_group_of, obs_names, cluster_by_groups,
                                                            int(k_obs_groups), hclust_method)
-    host = None
-    if members or write_expr_matrix:
-        host = x.cpu().numpy()                   # (C, G), clamped
-    if members:
+    if members:                                  # (x: the clamped matrix, on the device)
         for grp in dict.fromkeys(split):
             memb = [c for c, s in zip(ordered, split) if s == grp]
             path = out(f"General_HCL_{r_num(grp) if not isinstance(grp, str) else grp}_members.txt")
             if len(memb) == 1:                   # obs_data[one name, ] drops to a vector: as.matrix makes it a column "V1"
-                write_table(path, [[v] for v in host[memb[0]].tolist()], genes, ["V1"])
+                write_matrix(path, x, memb, "gene_rows", genes, ["V1"])
             else:
-                write_table(path, host[memb].tolist(), [cells[c] for c in memb], genes)
+                write_matrix(path, x, memb, "cell_rows", [cells[c] for c in memb], genes)
 
     split_idx = {g: i for i, g in enumerate(dict.fromkeys(split))}
     dend_pal = group_colors(len(split_idx))
@@ -501,10 +594,9 @@ def plot_cnv(infercnv_obj: InfercnvObject, out_dir=".", title="inferCNV", obs_ti
         ref_ordered, ref_split, ref_seps = reference_order(x, list(obj.reference_grouped_cell_indices.values()),
                                                            cluster_references, hclust_method)
     if write_expr_matrix:
-        write_table(out(f"{output_filename}.observations.txt"), host[ordered].T.tolist(), genes, [cells[c] for c in ordered])
+        write_matrix(out(f"{output_filename}.observations.txt"), x, ordered, "gene_rows", genes, [cells[c] for c in ordered])
         if ref_names:
-            write_table(out(f"{output_filename}.references.txt"), host[ref_ordered].T.tolist(), genes,
-                        [cells[c] for c in ref_ordered])
+            write_matrix(out(f"{output_filename}.references.txt"), x, ref_ordered, "gene_rows", genes, [cells[c] for c in ref_ordered])
 
     if output_format == "png":
         geo = page_geometry(obs_names, ref_names, nobs, png_res, 0 if dynamic_resize is None or dynamic_resize < 0 else dynamic_resize)
