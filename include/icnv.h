@@ -203,7 +203,8 @@ int icnv_chain_get_denoise(icnv_chain_t *chain, double *mu_s, void *stream);
 void icnv_chain_end(icnv_chain_t *chain);
 
 /* get_average_bounds (R/inferCNV_ops.R:2723-2742): out2 = {mean_c min_g x,
- * mean_c max_g x}; threshold "auto" of step 9 is mean(abs(out2)). */
+ * mean_c max_g x}; threshold "auto" of step 9 is mean(abs(out2)).  NaN entries are skipped per cell (quantile(x,
+ * na.rm = TRUE)); a cell that holds nothing but NaN makes both bounds NaN, as R's mean() over an NA does. */
 int icnv_average_bounds(const double *expr, int64_t G, int64_t C, double *out2);
 int icnv_average_bounds_dev(const double *expr, int64_t G, int64_t C, double *out2_host, void *stream);
 
@@ -216,7 +217,9 @@ int icnv_scale_genes_dev(const double *expr_in, double *expr_out, int64_t G, int
 /* remove_outliers_norm (step 16 of run(), R/inferCNV_ops.R:1969-2054; between the chain and the HMM when prune_outliers
  * is set): values below / above the bounds are set to the bounds.  Both bounds given (not NaN) = hard thresholds
  * (:2017-2022); otherwise out_method = "average_bound", the bounds of icnv_average_bounds over the input (:2029-2033).
- * bounds_used2 (nullable, host) receives {lower, upper}.  expr_out may alias expr_in in the _dev form. */
+ * bounds_used2 (nullable, host) receives {lower, upper}.  expr_out may alias expr_in in the _dev form.  NaN average
+ * bounds (a cell of nothing but NaN) are passed on, not refused: bounds_used2 = {NaN, NaN} and the matrix is copied
+ * unchanged, which is what R's two assignments do with an NA bound (an NA subscript assigns nothing). */
 int icnv_remove_outliers(const double *expr_in, double *expr_out, int64_t G, int64_t C, double lower_bound, double upper_bound,
                          double *bounds_used2);
 int icnv_remove_outliers_dev(const double *expr_in, double *expr_out, int64_t G, int64_t C, double lower_bound,
@@ -232,7 +235,9 @@ int icnv_remove_outliers_dev(const double *expr_in, double *expr_out, int64_t G,
  *   min_cells_per_gene    <= 0: no filter; a gene needs counts > 0 in at least that many cells
  *   normalize_factor      NaN: median(colSums) over the kept genes (the reference's default, normalize_factor = NA)
  *   keep_idx [G], G_out   the kept genes (ascending, 0-based) and their number; "All genes removed" is an error (:2194)
- *   expr_out              capacity G x C doubles, filled G_out x C; h2d_bytes (nullable): bytes uploaded */
+ *   expr_out              capacity G x C doubles, filled G_out x C; h2d_bytes (nullable): bytes uploaded
+ * CSC: a (gene, cell) pair may be stored at most once (explicitly stored zeros are fine).  Duplicates are NOT detected:
+ * the statistics and the column sums would add them, apply would keep one of them. */
 typedef struct icnv_counts {
     const int32_t *dense;    /* dense form, or NULL */
     const int64_t *colptr;   /* CSC form, or NULL */
