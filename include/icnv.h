@@ -1052,6 +1052,62 @@ int icnv_format_table(const double *x, int64_t G, int64_t C, int32_t orientation
 int icnv_table_text_stats(int64_t *out, int32_t n);
 void icnv_table_text_stats_reset(void);
 
+/* ---- count matrices from text (K21) -----------------------------------------------------------------------------------------
+ * The inverse of the entries above: a chunk of a text table, as read.table(sep = <one byte>, header = TRUE, row.names = 1)
+ * takes it in CreateInfercnvObject (R/inferCNV.R:146-156), becomes doubles in the library's layout.  DESIGN.md section 4 K21,
+ * restated in tests/create_object_restate.py.  Not bound in the R shim.  Agreement with the bits of R's own R_strtod, which
+ * works in long double, is believed for short decimals and not verified; the values here are C's strtod, bit for bit.
+ *
+ * The chunk: n_bytes (1 .. 2^31 - 2) of text that consists of whole lines, without the file's header line (the caller reads
+ * that).  text_dev is the DEVICE copy (16-byte aligned), text_host the HOST copy of the same bytes; the host flavour takes one.
+ * Grammar -- everything else is refused, nothing is quietly misparsed:
+ *   lines     end in "\n" or "\r\n"; the last line may lack the terminator.  A line that is empty (or a lone "\r") is skipped.
+ *   row       a label and n_cols numeric fields, separated by the one byte of `sep` (not a line end, not a quote).
+ *   label     the row's first field, opaque bytes up to the first separator; it may be enclosed in a pair of `"`, which the
+ *             reported range leaves out.  A quote anywhere else in a label is refused, and a separator inside a quoted label
+ *             is a separator (so such a row is refused for its field count or for the field that follows).
+ *   number    [+-] (digits [. [digits]] | . digits) [(e|E) [+-] digits], or NaN, Inf, +Inf, -Inf, or NA or the empty field.
+ *             NA and the empty field give R's NA_real_ (bits 0x7FF00000000007A2, as K19 stores it), NaN gives
+ *             0x7FF8000000000000.  Hex floats, quoted numbers, blanks around a number and other spellings are refused.
+ * Value: every number becomes the correctly rounded double (ties to even), what strtod returns.
+ * Output: row i (counting the chunk's rows that are not blank), column c goes to out[c * ld + row0 + i] -- DEVICE in the _dev
+ *   flavour, HOST otherwise --, the (cells, genes) matrix of every *_dev entry when the file has a line per gene.
+ *   label_ranges (HOST, [2 * max_rows]): the label of row i is the chunk's bytes label_ranges[2 i] .. label_ranges[2 i + 1].
+ *   *n_rows: the rows found (0 for a chunk of blank lines).
+ * ICNV_ERR_ARG before any launch: a null pointer; n_bytes out of range; a device text that is not 16-byte aligned; a bad sep;
+ *   n_cols outside 1 .. 2^31 - 1; line0 < 1; row0 < 0, max_rows < 1 or row0 + max_rows > ld.  ICNV_ERR_ARG after the passes:
+ *   more rows than max_rows, or a refusal, whose message reads "parse_table: line L, field K: <what>: '<bytes>'" with L the
+ *   1-based file line (line0 is the file line of the chunk's first line, blank lines count), K the 1-based field of that line
+ *   (the label is field 1; for a row with a field count other than n_cols + 1: the count).  Of several refusals the one at the
+ *   smallest byte offset is reported (a ragged row counts at its first byte; among more than 65536 uncertified fields only
+ *   those of the first round are looked at).  On any error out, label_ranges and *n_rows are
+ *   left as they were: the values are staged and reach `out` only when every field of the chunk is known.  Synchronises.
+ * Method: a structure pass marks row and field starts, 16 positions per lane, counts them per 4096-byte segment and scans the
+ *   counts; an index pass lists the starts; a rows pass checks field counts and labels; a parse pass runs one lane per field:
+ *   at most 19 significant digits with a significand below 2^53 and a decimal exponent within +-22 take one exact multiply or
+ *   divide, other fields of at most 19 digits a product with a 128-bit power of ten (csrc/tp_pow10_table.h, exponents -342 ..
+ *   308) that is stored only when its rounding is certified (csrc/table_parse_num.h).  Everything else -- exact ties, more
+ *   than 19 digits, fields longer than 40 bytes, subnormal results, underflow, overflow -- is parsed here with strtod from
+ *   text_host and patched in.  A transpose pass moves the staged values to `out` through 64 x 64 LDS tiles.
+ *   Timer names: "table_parse_structure", "table_parse_index", "table_parse_fields", "table_parse_collect",
+ *   "table_parse_transpose". */
+int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols,
+                         int64_t line0, double *out, int64_t ld, int64_t row0, int64_t max_rows, int64_t *label_ranges, int64_t *n_rows,
+                         void *stream);
+int icnv_parse_table(const uint8_t *text, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0, double *out, int64_t ld,
+                     int64_t row0, int64_t max_rows, int64_t *label_ranges, int64_t *n_rows);
+/* Counters since the last reset, n = int64 slots (<= 7 written); a refused call counts nowhere:
+ *   out[0] calls   out[1] rows   out[2] numeric fields   out[3] fields parsed on the host   out[4] bytes
+ *   out[5] extra collection rounds (more than 65536 uncertified fields at once)   out[6] wall microseconds */
+int icnv_table_parse_stats(int64_t *out, int32_t n);
+void icnv_table_parse_stats_reset(void);
+/* The last step of CreateInfercnvObject: out[j * ld_out + i] = in[cells[j] * ld_in + genes[i]] for a (C_in, G_in) DEVICE matrix
+ * whose rows lie ld_in apart; genes / cells are HOST lists, 0-based, in any order (null: all of them, in order, and the
+ * count is ignored).  `out` must not overlap `in`.  ICNV_ERR_ARG: a null matrix, dimensions outside 1 .. 2^31 - 1, ld_in < G_in,
+ * ld_out < n_genes, an empty list or an entry that is not a gene / cell.  Synchronises.  Timer name: "gather_matrix". */
+int icnv_gather_matrix_dev(const double *in, int64_t ld_in, int64_t G_in, int64_t C_in, const int32_t *genes, int64_t n_genes,
+                           const int32_t *cells, int64_t n_cells, double *out, int64_t ld_out, void *stream);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

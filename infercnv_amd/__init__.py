@@ -8,5 +8,6 @@ Cell-sharded multi-GPU: `sharded`.  All compute is in libicnv_hip.so
 """
 from ._lib import IcnvError, LIB_PATH, load  # noqa: F401
 from .infercnv_object import GeneOrder, InfercnvObject  # noqa: F401
+from .create_object import CreateInfercnvObject  # noqa: F401
 
-__all__ = ["IcnvError", "LIB_PATH", "load", "GeneOrder", "InfercnvObject"]
+__all__ = ["IcnvError", "LIB_PATH", "load", "GeneOrder", "InfercnvObject", "CreateInfercnvObject"]

@@ -187,6 +187,11 @@ PROTOTYPES = {
     "icnv_format_table": (ct.c_int, [_vp, _i64, _i64, _i32, _i64, _i64, _ip, _i64, _vp, _i64p, ct.c_char_p, _vp, _i64, _i64p, _i64p, _i64p]),
     "icnv_table_text_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_table_text_stats_reset": (None, []),
+    "icnv_parse_table_dev": (ct.c_int, [_vp, _vp, _i64, ct.c_char_p, _i64, _i64, _vp, _i64, _i64, _i64, _i64p, _i64p, _vp]),
+    "icnv_parse_table": (ct.c_int, [_vp, _i64, ct.c_char_p, _i64, _i64, _vp, _i64, _i64, _i64, _i64p, _i64p]),
+    "icnv_table_parse_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_table_parse_stats_reset": (None, []),
+    "icnv_gather_matrix_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _i64, _ip, _i64, _vp, _i64, _vp]),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

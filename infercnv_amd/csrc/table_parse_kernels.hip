@@ -1,0 +1,297 @@
+// K21: a chunk of a text table to doubles in the library's layout (include/icnv.h "count matrices from text").  Passes over a
+// chunk of whole lines: structure (row and field starts counted per segment, scanned), index (the lists of field and row
+// starts), rows (field counts, labels), parse (one lane per field), transpose (file order to cell-major through LDS).  The
+// host side -- validation, strtod for the fields the parse does not certify, the error text -- is table_parse_api.hip.
+// DESIGN.md section 4 K21.
+#include "icnv_internal.h"
+#include "table_parse_internal.h"
+
+namespace icnv {
+
+namespace {
+
+// ---- structure ------------------------------------------------------------------------------------------------------------
+// Position p of the text (0 .. n; n is a position because a last line without '\n' may end in a separator) is
+//   a row start    when it begins a line (p == 0 or text[p - 1] == '\n') that is not blank (tp_at_line_end(p) is false);
+//   a field start  when it is a row start or text[p - 1] is the separator.
+// A lane looks at TP_BYTES positions from `base`: b[k] is the byte at base - 1 + k, '\n' on either side of the text, which
+// makes position 0 a line start and keeps every position beyond n from being anything.  Bit j of the masks is position base + j.
+__device__ inline void tp_masks(const TpArgs &a, int64_t base, uint32_t &rows, uint32_t &fields) {
+    uint8_t b[TP_BYTES + 2];
+    b[0] = (base > 0 && base - 1 < a.n) ? a.text[base - 1] : (uint8_t)'\n';
+    if (base + TP_BYTES <= a.n) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(a.text + base);
+        const uint32_t word[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < TP_BYTES; ++j) b[1 + j] = (uint8_t)(word[j >> 2] >> (8 * (j & 3)));
+    } else {
+#pragma unroll
+        for (int j = 0; j < TP_BYTES; ++j) b[1 + j] = base + j < a.n ? a.text[base + j] : (uint8_t)'\n';
+    }
+    b[TP_BYTES + 1] = base + TP_BYTES < a.n ? a.text[base + TP_BYTES] : (uint8_t)'\n';
+    rows = 0;
+    fields = 0;
+#pragma unroll
+    for (int j = 0; j < TP_BYTES; ++j) {
+        const int k = j + 1;
+        const bool line_start = b[k - 1] == '\n';
+        const bool line_end = b[k] == '\n' || (b[k] == '\r' && b[k + 1] == '\n');
+        const bool row = line_start && !line_end;
+        rows |= (uint32_t)row << j;
+        fields |= (uint32_t)(row || b[k - 1] == a.sep) << j;
+    }
+}
+
+__device__ inline uint32_t tp_packed_counts(uint32_t rows, uint32_t fields) { return ((uint32_t)__popc(rows) << 16) | (uint32_t)__popc(fields); }
+
+// Inclusive scan of one word per lane over the workgroup (s_scan: TP_NT words).
+__device__ inline uint32_t tp_block_scan(uint32_t v, uint32_t *s_scan) {
+    const int tid = threadIdx.x;
+    s_scan[tid] = v;
+    __syncthreads();
+    for (int d = 1; d < TP_NT; d <<= 1) {
+        const uint32_t add = tid >= d ? s_scan[tid - d] : 0u;
+        __syncthreads();
+        s_scan[tid] += add;
+        __syncthreads();
+    }
+    return s_scan[tid];
+}
+
+__global__ __launch_bounds__(TP_NT) void tp_count_kernel(TpArgs a) {
+    __shared__ uint32_t s_part[TP_NT / 64];
+    uint32_t rows, fields;
+    tp_masks(a, ((int64_t)blockIdx.x * TP_NT + threadIdx.x) * TP_BYTES, rows, fields);
+    uint32_t v = tp_packed_counts(rows, fields);             // at most 4096 of either in a segment: the halves do not meet
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) a.seg_count[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
+
+// One workgroup: the exclusive scans of the segments' row and field counts, and the totals.
+__global__ __launch_bounds__(TP_NT) void tp_scan_kernel(TpArgs a) {
+    __shared__ uint32_t s_scan[TP_NT];
+    uint32_t carry_r = 0, carry_f = 0;
+    for (int64_t i0 = 0; i0 < a.n_seg; i0 += TP_NT) {
+        const int64_t i = i0 + threadIdx.x;
+        const uint32_t c = i < a.n_seg ? a.seg_count[i] : 0u, r = c >> 16, f = c & 0xffffu;
+        const uint32_t inc_r = tp_block_scan(r, s_scan), tot_r = s_scan[TP_NT - 1];
+        __syncthreads();
+        const uint32_t inc_f = tp_block_scan(f, s_scan), tot_f = s_scan[TP_NT - 1];
+        __syncthreads();
+        if (i < a.n_seg) {
+            a.seg_row_off[i] = carry_r + inc_r - r;
+            a.seg_field_off[i] = carry_f + inc_f - f;
+        }
+        carry_r += tot_r;
+        carry_f += tot_f;
+    }
+    if (threadIdx.x == 0) {
+        a.totals[0] = carry_r;
+        a.totals[1] = carry_f;
+    }
+}
+
+// ---- index ----------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TP_NT) void tp_index_kernel(TpArgs a) {
+    __shared__ uint32_t s_scan[TP_NT];
+    const int64_t base = ((int64_t)blockIdx.x * TP_NT + threadIdx.x) * TP_BYTES;
+    uint32_t rows, fields;
+    tp_masks(a, base, rows, fields);
+    const uint32_t mine = tp_packed_counts(rows, fields), excl = tp_block_scan(mine, s_scan) - mine;
+    int64_t r = (int64_t)a.seg_row_off[blockIdx.x] + (excl >> 16), f = (int64_t)a.seg_field_off[blockIdx.x] + (excl & 0xffffu);
+    while (fields) {
+        const int j = __ffs((int)fields) - 1;
+        fields &= fields - 1;
+        if ((rows >> j) & 1u) {
+            if (r < a.n_rows) {
+                a.row_pos[r] = (uint32_t)(base + j);
+                a.row_field0[r] = (uint32_t)f;
+            }
+            ++r;
+        }
+        if (f < a.n_fields && r >= 1 && r <= a.n_rows) {
+            a.field_pos[f] = (uint32_t)(base + j);
+            a.field_row[f] = (uint32_t)(r - 1);
+        }
+        ++f;
+    }
+}
+
+__device__ inline void tp_refuse(const TpArgs &a, int64_t offset, int code) {
+    atomicMin(a.error, ((unsigned long long)offset << 8) | (unsigned long long)code);
+}
+
+// One lane per row: the field count, the label's range and its quotes.
+__global__ __launch_bounds__(TP_NT) void tp_rows_kernel(TpArgs a) {
+    const int64_t r = (int64_t)blockIdx.x * TP_NT + threadIdx.x;
+    if (r >= a.n_rows) return;
+    const int64_t f0 = a.row_field0[r], f1 = r + 1 < a.n_rows ? (int64_t)a.row_field0[r + 1] : a.n_fields, p0 = a.row_pos[r];
+    if (f1 - f0 != a.n_cols + 1) tp_refuse(a, p0, 1 /* TP_E_RAGGED */);
+    const int64_t e = tp_field_end(a.text, a.n, p0, a.sep);
+    const bool quoted = e - p0 >= 2 && a.text[p0] == '"' && a.text[e - 1] == '"';
+    for (int64_t i = p0; i < e; ++i)
+        if (a.text[i] == '"' && !(quoted && (i == p0 || i == e - 1))) {
+            tp_refuse(a, i, 3 /* TP_E_LABEL */);
+            break;
+        }
+    a.label_range[2 * r] = (int32_t)p0;
+    a.label_range[2 * r + 1] = (int32_t)e;
+}
+
+// ---- parse ----------------------------------------------------------------------------------------------------------------
+__device__ inline void tp_flag(const TpArgs &a, int64_t slot, int64_t pos) {
+    const uint32_t t = atomicAdd(a.n_flagged, 1u);
+    if (t < (uint32_t)TP_FLAG_CAP) a.flagged[t] = TpFlagged{slot, pos};
+}
+
+// One lane per field start.  The label (field 0) and the fields of a ragged row beyond n_cols are left alone; the rows pass
+// refuses such a chunk.  The values are staged in file order: row r, column c at vals[r * n_cols + c].
+__global__ __launch_bounds__(TP_NT) void tp_parse_kernel(TpArgs a) {
+    const int64_t f = (int64_t)blockIdx.x * TP_NT + threadIdx.x;
+    if (f >= a.n_fields) return;
+    const int64_t p = a.field_pos[f], r = a.field_row[f];
+    if (p > a.n || r >= a.n_rows) return;                      // cannot happen: the index pass wrote every entry from the same masks
+    const int64_t c = f - (int64_t)a.row_field0[r];
+    if (c < 1 || c > a.n_cols) return;
+    const int64_t slot = r * a.n_cols + c - 1;
+    int64_t end = p;
+    while (end - p <= TP_MAX_SCAN && !tp_at_line_end(a.text, a.n, end) && a.text[end] != a.sep) ++end;
+    uint64_t bits = TP_PENDING, w;
+    int q;
+    bool neg;
+    int kind = TP_HOST;
+    if (end - p <= TP_MAX_SCAN) kind = tp_scan_number(a.text + p, end - p, bits, w, q, neg);
+    if (kind == TP_DECIMAL) kind = tp_convert(w, q, neg, bits) ? TP_VALUE : TP_HOST;
+    if (kind == TP_BAD) tp_refuse(a, p, 2 /* TP_E_NUMBER */);
+    if (kind != TP_VALUE) bits = TP_PENDING;
+    if (kind == TP_HOST) tp_flag(a, slot, p);
+    a.vals[slot] = bits;
+}
+
+// More than TP_FLAG_CAP uncertified fields: list (up to the capacity) those that are still pending.  Runs only on a chunk
+// whose rows all have n_cols + 1 fields.
+__global__ __launch_bounds__(TP_NT) void tp_collect_kernel(TpArgs a) {
+    const int64_t n = a.n_rows * a.n_cols;
+    for (int64_t i = (int64_t)blockIdx.x * TP_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * TP_NT) {
+        if (a.vals[i] != TP_PENDING) continue;
+        const int64_t r = i / a.n_cols, c = i % a.n_cols;
+        tp_flag(a, i, a.field_pos[(int64_t)a.row_field0[r] + c + 1]);
+    }
+}
+
+__global__ __launch_bounds__(TP_NT) void tp_patch_kernel(uint64_t *vals, const int64_t *slot, const uint64_t *bits, int32_t n) {
+    const int i = blockIdx.x * TP_NT + threadIdx.x;
+    if (i < n) vals[slot[i]] = bits[i];
+}
+
+// ---- transpose ------------------------------------------------------------------------------------------------------------
+// A 64 rows x 64 columns tile: the reads run along the columns of one file row (contiguous in vals), the stores along the rows
+// of one column (contiguous in out).  The padded LDS row keeps both sides free of bank conflicts.
+__global__ __launch_bounds__(TP_NT) void tp_transpose_kernel(TpArgs a) {
+    __shared__ uint64_t s_tile[TP_TILE][TP_TILE + 1];
+    const int64_t tiles_c = (a.n_cols + TP_TILE - 1) / TP_TILE;
+    const int64_t r_base = ((int64_t)blockIdx.x / tiles_c) * TP_TILE, c_base = ((int64_t)blockIdx.x % tiles_c) * TP_TILE;
+    const int tx = threadIdx.x & (TP_TILE - 1), ty = threadIdx.x >> 6;
+    for (int rr = ty; rr < TP_TILE; rr += TP_NT / TP_TILE) {
+        const int64_t r = r_base + rr, c = c_base + tx;
+        if (r < a.n_rows && c < a.n_cols) s_tile[rr][tx] = a.vals[r * a.n_cols + c];
+    }
+    __syncthreads();
+    for (int cc = ty; cc < TP_TILE; cc += TP_NT / TP_TILE) {
+        const int64_t r = r_base + tx, c = c_base + cc;
+        if (r < a.n_rows && c < a.n_cols) a.out[c * a.ld + a.row0 + r] = __longlong_as_double((long long)s_tile[tx][cc]);
+    }
+}
+
+// ---- gather ---------------------------------------------------------------------------------------------------------------
+// out[j * ld_out + i] = in[cells[j] * ld_in + genes[i]]; a null list is the identity.  One workgroup per (cell, 256 genes).
+__global__ __launch_bounds__(TP_NT) void gather_matrix_kernel(const double *in, int64_t ld_in, const int32_t *genes, int64_t n_genes,
+                                                              const int32_t *cells, int64_t gene_blocks, double *out, int64_t ld_out) {
+    const int64_t j = (int64_t)blockIdx.x / gene_blocks, i = ((int64_t)blockIdx.x % gene_blocks) * TP_NT + threadIdx.x;
+    if (i >= n_genes) return;
+    const int64_t c = cells ? (int64_t)cells[j] : j, g = genes ? (int64_t)genes[i] : i;
+    out[j * ld_out + i] = in[c * ld_in + g];
+}
+
+int tp_grid(int64_t blocks, unsigned &grid) {
+    if (blocks < 1 || blocks > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "parse_table: the chunk needs more than 2^31 - 1 workgroups");
+    grid = (unsigned)blocks;
+    return ICNV_OK;
+}
+
+}  // namespace
+
+int launch_tp_structure(const TpArgs &a, hipStream_t s) {
+    KernelTimer kt("table_parse_structure", s);
+    unsigned grid;
+    int rc;
+    if ((rc = tp_grid(a.n_seg, grid))) return rc;
+    hipLaunchKernelGGL(tp_count_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(tp_scan_kernel, dim3(1), dim3(TP_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_tp_index(const TpArgs &a, hipStream_t s) {
+    KernelTimer kt("table_parse_index", s);
+    unsigned grid;
+    int rc;
+    if ((rc = tp_grid(a.n_seg, grid))) return rc;
+    hipLaunchKernelGGL(tp_index_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    if ((rc = tp_grid((a.n_rows + TP_NT - 1) / TP_NT, grid))) return rc;
+    hipLaunchKernelGGL(tp_rows_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_tp_parse(const TpArgs &a, hipStream_t s) {
+    KernelTimer kt("table_parse_fields", s);
+    unsigned grid;
+    int rc;
+    if ((rc = tp_grid((a.n_fields + TP_NT - 1) / TP_NT, grid))) return rc;
+    hipLaunchKernelGGL(tp_parse_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_tp_collect(const TpArgs &a, hipStream_t s) {
+    KernelTimer kt("table_parse_collect", s);
+    const int64_t blocks = (a.n_rows * a.n_cols + TP_NT - 1) / TP_NT, cap = (int64_t)num_cus() * 8;
+    hipLaunchKernelGGL(tp_collect_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(TP_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_tp_patch(const TpArgs &a, const int64_t *slot, const uint64_t *bits, int32_t n, hipStream_t s) {
+    hipLaunchKernelGGL(tp_patch_kernel, dim3((unsigned)((n + TP_NT - 1) / TP_NT)), dim3(TP_NT), 0, s, a.vals, slot, bits, n);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_tp_transpose(const TpArgs &a, hipStream_t s) {
+    KernelTimer kt("table_parse_transpose", s);
+    unsigned grid;
+    int rc;
+    if ((rc = tp_grid(((a.n_rows + TP_TILE - 1) / TP_TILE) * ((a.n_cols + TP_TILE - 1) / TP_TILE), grid))) return rc;
+    hipLaunchKernelGGL(tp_transpose_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_gather_matrix(const double *in, int64_t ld_in, const int32_t *genes, int64_t n_genes, const int32_t *cells, int64_t n_cells,
+                         double *out, int64_t ld_out, hipStream_t s) {
+    KernelTimer kt("gather_matrix", s);
+    const int64_t gene_blocks = (n_genes + TP_NT - 1) / TP_NT;
+    unsigned grid;
+    int rc;
+    if ((rc = tp_grid(gene_blocks * n_cells, grid))) return rc;
+    hipLaunchKernelGGL(gather_matrix_kernel, dim3(grid), dim3(TP_NT), 0, s, in, ld_in, genes, n_genes, cells, gene_blocks, out, ld_out);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+}  // namespace icnv

@@ -293,6 +293,287 @@ def table_text_stats(reset=False):
     return dict(zip(TABLE_TEXT_STATS, (int(v) for v in out)))
 
 
+# ------------------------------------------------------------------ count matrices from text (DESIGN K21)
+TABLE_PARSE_STATS = ("calls", "rows", "fields", "host_parsed", "bytes", "collect_rounds", "us")
+READ_TABLE_CHUNK = 64 << 20        # bytes of one chunk of read_table; ICNV_READ_TABLE_CHUNK (developer switch) overrides it
+
+
+def table_parse_stats(reset=False):
+    """icnv_table_parse_stats as a dict (`host_parsed`: fields the parse pass could not certify, parsed by the host's strtod;
+    `us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(TABLE_PARSE_STATS))()
+    check(L.icnv_table_parse_stats(out, len(TABLE_PARSE_STATS)))
+    if reset:
+        L.icnv_table_parse_stats_reset()
+    return dict(zip(TABLE_PARSE_STATS, (int(v) for v in out)))
+
+
+def parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, line0=1):
+    """icnv_parse_table_dev: the first n_bytes of `text_dev` (contiguous CUDA uint8) and of `text_host` (a contiguous uint8
+    numpy array or CPU tensor with the same bytes) are whole lines of a table with out.shape[0] numeric columns; row i of them
+    goes to out[:, row0 + i].  out: a CUDA float64 (n_cols, ld) tensor with contiguous rows.  Returns (rows found, int64 label
+    ranges [rows, 2] into the bytes).  On an IcnvError `out` is as it was.  Synchronises the stream."""
+    L = _lib.load()
+    if not (isinstance(text_dev, torch.Tensor) and text_dev.is_cuda and text_dev.dtype == torch.uint8 and text_dev.dim() == 1
+            and text_dev.is_contiguous()):
+        raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
+    host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
+    if not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
+        raise TypeError("text_host must be a contiguous one-dimensional uint8 array")
+    n_bytes = int(n_bytes)
+    if n_bytes < 1 or n_bytes > text_dev.numel() or n_bytes > host.size:
+        raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
+    n_cols, _, ld = _check_matrix_ld(out)
+    row0, max_rows = int(row0), int(max_rows)
+    if row0 < 0 or max_rows < 1 or row0 + max_rows > out.shape[1]:
+        raise ValueError("rows row0 .. row0 + max_rows - 1 must be columns of out")
+    if n_cols == 1:
+        ld = out.shape[1]
+    sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
+    ranges = np.zeros((max_rows, 2), dtype=np.int64)
+    n_rows = ct.c_int64(0)
+    check(L.icnv_parse_table_dev(_ptr(text_dev), ct.c_void_p(host.ctypes.data), n_bytes, sep_b, n_cols, int(line0), _ptr(out), int(ld), row0,
+                                 max_rows, ranges.ctypes.data_as(ct.POINTER(ct.c_int64)), ct.byref(n_rows), _stream()))
+    return int(n_rows.value), ranges[:int(n_rows.value)]
+
+
+def gather_matrix(x, genes=None, cells=None, out=None):
+    """out[j, i] = x[cells[j], genes[i]] on the device (icnv_gather_matrix_dev): the kept, ordered genes and the kept cells of
+    CreateInfercnvObject in one pass.  x: (C, G) CUDA float64 with contiguous rows; genes / cells: 0-based, any order, None for
+    all of them in order.  Returns the contiguous (len(cells), len(genes)) tensor."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    g, gp = i32(genes) if genes is not None else (None, None)
+    c, cp = i32(cells) if cells is not None else (None, None)
+    ng, nc = (g.size if g is not None else G), (c.size if c is not None else C)
+    if out is None:
+        out = torch.empty((nc, ng), dtype=torch.float64, device=x.device)
+    if _check_matrix(out) != (nc, ng):
+        raise ValueError("out must have the shape (cells, genes) of the lists")
+    check(L.icnv_gather_matrix_dev(_ptr(x), int(ld), G, C, gp, ng, cp, nc, _ptr(out), ng, _stream()))
+    return out
+
+
+def _unquote(b):
+    return b[1:-1] if len(b) >= 2 and b[:1] == b"\"" and b[-1:] == b"\"" else b
+
+
+def _pinned(n):
+    return torch.empty(int(n), dtype=torch.uint8, pin_memory=True)
+
+
+def _last_newline(arr, n):
+    """Index of the last '\\n' of arr[:n], or -1."""
+    hi = n
+    while hi > 0:
+        lo = max(0, hi - (1 << 16))
+        hit = np.flatnonzero(arr[lo:hi] == 10)
+        if hit.size:
+            return lo + int(hit[-1])
+        hi = lo
+    return -1
+
+
+def _count_newlines(path, n_bytes):
+    """'\\n' among the first n_bytes of the (decompressed) file: the error path of read_table."""
+    import gzip
+    count = 0
+    with (gzip.open(path, "rb") if str(path).endswith(".gz") else open(path, "rb")) as f:
+        while n_bytes > 0:
+            block = f.read(min(n_bytes, 1 << 24))
+            if not block:
+                break
+            count += block.count(b"\n")
+            n_bytes -= len(block)
+    return count
+
+
+def read_table(path, sep="\t", chunk_bytes=None):
+    """read.table(path, sep = sep, header = TRUE, row.names = 1, check.names = FALSE) of a numeric table, parsed on the device
+    (icnv_parse_table_dev, DESIGN K21; the grammar and what is refused: include/icnv.h "count matrices from text").
+    Returns (row names, column names, x, stats): x is the (n_cols, n_rows) CUDA float64 tensor -- for a genes x cells file the
+    (cells, genes) matrix every device.* entry takes --, stats a dict of counts and seconds (the counters of table_parse_stats
+    for this call among them).
+
+    The header line is read here: it has one name per numeric column, as write.table writes it, or one more with a corner
+    label in front.  Quotes around a name are dropped.  The body is streamed in chunks of whole lines through two pinned and two
+    device buffers: a thread reads chunk i + 1 from the file while chunk i is copied and parsed; a buffer grows when one line
+    is longer than chunk_bytes.  A path that ends in .gz is decompressed by Python's gzip into the same pinned chunks
+    (R/inferCNV.R:146-150 reads it through gzfile); .rds is not read (NotImplementedError).  A refused byte raises IcnvError
+    with the file line and the field."""
+    import gzip
+    import queue
+    import threading
+    import time
+    path = os.fspath(path)
+    if path.endswith(".rds"):
+        raise NotImplementedError("read_table: .rds input is not read; pass the matrix as an array")
+    sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
+    if len(sep_b) != 1:
+        raise ValueError("sep must be one byte")
+    cap0 = max(64, int(chunk_bytes if chunk_bytes is not None else os.environ.get("ICNV_READ_TABLE_CHUNK", READ_TABLE_CHUNK)))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stats = {"bytes": 0, "chunks": 0, "read_s": 0.0, "parse_s": 0.0, "stall_s": 0.0, "grown": 0}
+    before = table_parse_stats()
+    jobs, free, failure = queue.Queue(), [threading.Semaphore(1), threading.Semaphore(1)], []
+    stop = threading.Event()
+    t_start = time.perf_counter()
+    pin = [_pinned(cap0), _pinned(cap0)]
+
+    def reader():
+        try:
+            with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb", buffering=0)) as f:
+                slot, fill, eof = 0, 0, False
+                free[0].acquire()
+                while not eof and not stop.is_set():
+                    t0 = time.perf_counter()
+                    arr = pin[slot].numpy()
+                    total = fill
+                    while total < arr.size:
+                        got = f.readinto(memoryview(arr)[total:])
+                        if not got:
+                            eof = True
+                            break
+                        total += got
+                    cut = total if eof else _last_newline(arr, total) + 1
+                    stats["read_s"] += time.perf_counter() - t0
+                    if cut == 0 and not eof:                      # one line is longer than the buffer: grow it and read on
+                        bigger = _pinned(2 * arr.size)
+                        bigger[:total].copy_(pin[slot][:total])
+                        pin[slot], fill = bigger, total
+                        stats["grown"] += 1
+                        continue
+                    jobs.put((slot, pin[slot], cut))              # only this thread writes a buffer, and only while it holds it
+                    nxt = 1 - slot
+                    free[nxt].acquire()                           # the chunk before this one has left that buffer
+                    tail = total - cut
+                    if pin[nxt].numel() <= tail:
+                        pin[nxt] = _pinned(2 * tail)
+                    if tail:
+                        pin[nxt][:tail].copy_(pin[slot][cut:total])
+                    slot, fill = nxt, tail
+        except Exception as exc:                                  # handed to the caller's thread below
+            failure.append(exc)
+        finally:
+            jobs.put(None)
+
+    copy_stream = torch.cuda.Stream(device=dev)
+    dbuf = [None, None]
+
+    def upload(job, start):
+        slot, buf, n = job
+        if dbuf[slot] is None or dbuf[slot].numel() < n - start:
+            dbuf[slot] = torch.empty(max(cap0, n - start), dtype=torch.uint8, device=dev)
+        event = torch.cuda.Event()
+        with torch.cuda.stream(copy_stream):
+            dbuf[slot][:n - start].copy_(buf[start:n], non_blocking=True)
+            event.record(copy_stream)
+        return event
+
+    def next_newline(arr, p, n):
+        while p < n:
+            hi = min(n, p + (1 << 16))
+            hit = np.flatnonzero(arr[p:hi] == 10)
+            if hit.size:
+                return p + int(hit[0])
+            p = hi
+        return n
+
+    row_names, header_names, col_names, n_cols, parts, scratch = [], None, None, None, [], None
+    offset, ahead = 0, None                                        # bytes of the file before this chunk; (job, event) copied ahead
+    thread = threading.Thread(target=reader, daemon=True)
+    thread.start()
+    try:
+        job = jobs.get()
+        while job is not None:
+            slot, buf, n = job
+            arr = buf.numpy()
+            start = 0
+            if header_names is None and n:                         # the header line
+                first = next_newline(arr, 0, n)
+                line = arr[:first].tobytes()
+                header_names = [_unquote(t) for t in (line[:-1] if line.endswith(b"\r") else line).split(sep_b)]
+                start = min(first + 1, n)
+            if n_cols is None:                                     # the first data line decides which header shape this is
+                p = start
+                while p < n and n_cols is None:
+                    e = next_newline(arr, p, n)
+                    raw = arr[p:e].tobytes()
+                    if raw not in (b"", b"\r"):
+                        k = raw.count(sep_b) + 1
+                        if len(header_names) == k - 1:
+                            col_names = header_names
+                        elif len(header_names) == k and k >= 2:
+                            col_names = header_names[1:]
+                        else:
+                            raise ValueError(f"read_table: the header has {len(header_names)} names, the first row has {k} fields")
+                        n_cols = len(col_names)
+                        if n_cols < 1:
+                            raise ValueError("read_table: the table has no numeric column")
+                    p = e + 1
+            nb = n - start
+            if n_cols is not None and nb > 0:
+                event = ahead[1] if ahead is not None and ahead[0] is job else upload(job, start)
+                ahead = None
+                max_rows = nb // (n_cols + 1) + 1                  # a row is at least its separators and its line end
+                if scratch is None or scratch.shape[1] < max_rows:
+                    scratch = torch.empty((n_cols, max_rows), dtype=torch.float64, device=dev)
+                t0 = time.perf_counter()
+                try:                                               # the next chunk's copy runs beside this parse
+                    peek = jobs.get_nowait()
+                    if peek is None:
+                        jobs.put(None)
+                    else:
+                        ahead = (peek, upload(peek, 0))
+                except queue.Empty:
+                    pass
+                torch.cuda.current_stream().wait_event(event)
+                host = arr[start:n]
+                try:
+                    rows, ranges = parse_table_into(dbuf[slot], host, nb, sep_b, scratch, 0, max_rows)
+                except _lib.IcnvError as exc:
+                    short = "max_rows" in str(exc)                 # more lines than full rows fit: some row is too short
+                    if exc.code != _lib.ERR_ARG or not (short or "line " in str(exc)):
+                        raise
+                    if short:
+                        max_rows = int(np.count_nonzero(host == 10)) + 1
+                        scratch = torch.empty((n_cols, max_rows), dtype=torch.float64, device=dev)
+                    line0 = 1 + _count_newlines(path, offset + start)     # the refusal again, with the file's line number
+                    parse_table_into(dbuf[slot], host, nb, sep_b, scratch, 0, max_rows, line0=line0)
+                    raise
+                stats["parse_s"] += time.perf_counter() - t0
+                if rows:
+                    parts.append(scratch[:, :rows].clone())
+                    for b, e in ranges.tolist():
+                        row_names.append(host[b:e].tobytes().decode("utf-8", "surrogateescape"))
+                stats["chunks"] += 1
+            offset += n
+            stats["bytes"] += n
+            free[slot].release()
+            t0 = time.perf_counter()
+            job = ahead[0] if ahead is not None else jobs.get()
+            stats["stall_s"] += time.perf_counter() - t0
+    finally:
+        stop.set()
+        torch.cuda.synchronize()                                   # a copy ahead may still read a pinned buffer
+        for sem in free:
+            sem.release()
+        thread.join()
+    if failure:
+        raise failure[0]
+    if n_cols is None or not parts:
+        raise ValueError("read_table: the file has no data row")
+    x = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+    x = x.contiguous()
+    col_names = [c.decode("utf-8", "surrogateescape") for c in col_names]
+    after = table_parse_stats()
+    stats.update({k: after[k] - before[k] for k in TABLE_PARSE_STATS})
+    torch.cuda.synchronize()                                       # the last chunk's copy and the concatenation are part of the total
+    stats["wall_s"] = time.perf_counter() - t_start
+    return row_names, col_names, x, stats
+
+
 def smooth_chain_windows(x, chr_start, ref_groups, table, max_thresh=3.0, use_bounds=True, sd_amplifier=1.5, noise_filter=None,
                          denoise=True, want_pre_denoise=False):
     """smooth_chain with step 10 replaced by the window operator (smooth_method "runmeans" / "coordinates"): the chain with
