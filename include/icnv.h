@@ -1108,6 +1108,93 @@ void icnv_table_parse_stats_reset(void);
 int icnv_gather_matrix_dev(const double *in, int64_t ld_in, int64_t G_in, int64_t C_in, const int32_t *genes, int64_t n_genes,
                            const int32_t *cells, int64_t n_cells, double *out, int64_t ld_out, void *stream);
 
+/* ---- sparse count matrices (K22) ----------------------------------------------------------------------------------------------
+ * The count matrix as it arrives at production size -- a MatrixMarket coordinate file (10x: matrix.mtx) or a sparse matrix in
+ * memory -- becomes an icnv_counts in CSC form on the device and stays sparse through .order_reduce and the cell filter of
+ * CreateInfercnvObject (R/inferCNV.R:133-337 keeps a dgCMatrix sparse likewise).  DESIGN.md section 4 K22, restated in
+ * tests/sparse_counts_restate.py.  Device entries only; not bound in the R shim.  The triplet grammar is the MatrixMarket
+ * specification's; there is no R here, so no byte of Matrix::writeMM or Seurat::Read10X was compared: scipy's reader is the
+ * independent check.  All arithmetic is integer; every result is the same on every run and for every launch shape.
+ *
+ * icnv_parse_triplets_dev: a chunk of the BODY of a coordinate file (the caller reads the banner, the % comments and the size
+ * line) to three int32 arrays.  text_dev is the DEVICE copy (16-byte aligned), text_host the HOST copy of the same n_bytes
+ * (1 .. 2^31 - 2) of whole lines; the host copy is read only to word a refusal.
+ * Grammar -- everything else is refused, nothing is quietly misparsed:
+ *   lines     end in "\n" or "\r\n"; the last line may lack the terminator.  A line that is empty, a lone "\r" or only blanks
+ *             (space, tab) is skipped.  Every other line is an entry; the k-th of the chunk goes to slot k of the arrays.
+ *   entry     `i j v`, with field = ICNV_MM_PATTERN `i j` and v = 1.  The fields are separated by one or more blanks; blanks
+ *             before the first and after the last field are allowed.  Another number of fields is refused, and so is a line
+ *             whose first field begins with `%`.
+ *   i, j      plain unsigned decimals of at most 10 digits, 1-based, in 1 .. n_rows and 1 .. n_cols; stored 0-based.  A sign,
+ *             another byte or a value outside the range is refused.
+ *   v         (ICNV_MM_INTEGER and ICNV_MM_REAL alike) a field of at most 40 bytes in the number grammar of "count matrices from
+ *             text" above, accepted when the double nearest to it is an integer in 0 .. 2^31 - 1: 3, +3, 3.0, 3e0 and
+ *             3.000000000000000e+00 are 3, and an explicit 0 is kept as a stored zero.  A field whose exact value is such an
+ *             integer is taken by integer arithmetic, whatever its spelling; any other field is converted as there
+ *             (csrc/table_parse_num.h), so 2147483646.999999999 is 2147483647.  Refused: a negative value (-0 included), a
+ *             fraction, 2147483648 and above, NA, the empty field, NaN, Inf, more than 19 significant digits, and a field
+ *             that is no integer and whose rounding cannot be certified (an underflow; no such field of at most 19 digits
+ *             rounds to an integer).  No host fallback.
+ * Output: row_dev / col_dev / val_dev (DEVICE, `capacity` elements each) receive the entries in file order; *n_entries (HOST)
+ *   their number (0 for a chunk of blank lines).
+ * ICNV_ERR_ARG before any launch: a null pointer; n_bytes out of range; a device text that is not 16-byte aligned; an unknown
+ *   field; n_rows or n_cols outside 1 .. 2^31 - 1; line0 < 1; capacity < 0.  ICNV_ERR_ARG after the passes: more entries than
+ *   capacity (nothing is written past the end), or a refusal, whose message reads
+ *   "parse_triplets: line L, field K: <what>: '<bytes>'" with L the 1-based file line (line0 is the file line of the chunk's
+ *   first line; blank lines count), K the 1-based field and <bytes> at most 60 bytes of it.  A wrong number of fields and a
+ *   comment line are reported at the line's first byte with the line's bytes, K being the number of fields (1 for a comment).
+ *   Of several refusals the one at the smallest byte offset is reported.  On any error the three arrays and *n_entries are
+ *   left as they were: the entries are staged and copied only when the whole chunk is known.  Synchronises.
+ * Method: a structure pass marks the first byte of every line that is not blank, 16 positions per lane, counts them per
+ *   4096-byte segment and scans the counts; an index pass lists them; a parse pass runs one lane per entry.  The one atomic is
+ *   the 64-bit atomicMin on the error word.  A line that begins with a blank is walked to its first other byte by the lane
+ *   that owns its first byte.  Timer names: "triplets_structure", "triplets_index", "triplets_parse". */
+#define ICNV_MM_INTEGER 0
+#define ICNV_MM_REAL 1
+#define ICNV_MM_PATTERN 2
+int icnv_parse_triplets_dev(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, int32_t field, int64_t n_rows,
+                            int64_t n_cols, int64_t line0, int32_t *row_dev, int32_t *col_dev, int32_t *val_dev, int64_t capacity,
+                            int64_t *n_entries, void *stream);
+/* The column pointers of triplets that are sorted: row_dev / col_dev [nnz] (DEVICE, 0-based, nnz >= 0) must have strictly
+ * ascending 64-bit keys col * G + row -- column-major order, what 10x, Matrix::writeMM and scipy.io.mmwrite of a CSC matrix
+ * write (believed of the first two, not verified here).  Then row and the values ARE the CSC's rowidx and vals, without a copy,
+ * and colptr_dev [C + 1] (DEVICE, int64) is written by boundary detection: entry k stores k into
+ * colptr[col[k - 1] + 1 .. col[k]] (col[-1] = -1), the last entry also nnz into colptr[col + 1 .. C].  No histogram and no
+ * atomics; empty columns at the start, in the middle and at the end come out right.  nnz = 0 gives the all-zero colptr without
+ * a launch.
+ *   *first_violation (HOST)  the smallest k with key[k] <= key[k - 1], or -1
+ *   *violation_kind (HOST)   ICNV_CSC_SORTED; ICNV_CSC_DUPLICATE: the keys of k - 1 and k are equal, a (gene, cell) pair stored
+ *                            twice -- an error for the caller, since icnv_counts does not detect duplicates downstream;
+ *                            ICNV_CSC_DESCENT: unsorted input, to be sorted by the caller and handed in again.
+ * With a violation the call returns ICNV_OK and colptr_dev is left untouched.  ICNV_ERR_ARG: a null pointer, G or C outside
+ * 1 .. 2^31 - 1, nnz < 0, an entry whose row or column lies outside the matrix (checked on the device before anything else;
+ * colptr_dev untouched).  Synchronises.  Timer names: "csc_build_check", "csc_build_colptr". */
+#define ICNV_CSC_SORTED 0
+#define ICNV_CSC_DUPLICATE 1
+#define ICNV_CSC_DESCENT 2
+int icnv_csc_from_sorted_triplets_dev(const int32_t *row_dev, const int32_t *col_dev, int64_t nnz, int64_t G, int64_t C,
+                                      int64_t *colptr_dev, int64_t *first_violation, int32_t *violation_kind, void *stream);
+/* .order_reduce (R/inferCNV.R:352-428) and the cell filter (:236-288) on a CSC matrix: cnt (CSC form, DEVICE pointers, G x C),
+ * gene_map_dev [G] the new row of each gene or -1 to drop it, cells_dev [n_cells] the source columns, in any order, repeats
+ * allowed.  Output column j holds the entries of source column cells[j] whose gene is kept, IN SOURCE ORDER, with the rows
+ * mapped -- a stable compaction, so the rows of an output column are in whatever order gene_map leaves them, which icnv_counts
+ * allows ("any order inside a column").  Values are copied, stored zeros included.
+ * Two calls: with rowidx_out == NULL the call fills colptr_out [n_cells + 1] (DEVICE, int64: the exclusive scan of the kept
+ * entries per output column) and *nnz_out (HOST); with rowidx_out / vals_out (DEVICE, `capacity` elements each) it fills
+ * those as well.  Neither call keeps state: the second counts again.
+ * ICNV_ERR_ARG: a null pointer; a dense icnv_counts; G, C or n_cells outside 1 .. 2^31 - 1; n_genes_out outside 0 .. 2^31 - 1;
+ * an entry of cells outside 0 .. C - 1 or of gene_map outside -1 .. n_genes_out - 1 (checked on the device before anything is
+ * counted; the message names the first such entry); capacity smaller than the count.  On an error the outputs are untouched.
+ * A colptr of cnt that leaves 0 .. nnz, or a row index outside 0 .. G - 1, reads nothing out of bounds: such a range is
+ * clipped and such an entry dropped.  Synchronises.
+ * Method: one wavefront per output column walks the source column 64 entries at a time -- first counting the kept ones by
+ * ballot, then, after a two-level exclusive int64 scan of the counts (tiles of 2048 columns, their sums scanned by one
+ * workgroup; exact for every n_cells), storing lane l's entry behind those of the kept lanes below it.
+ * Timer names: "csc_select_count", "csc_select_fill". */
+int icnv_csc_select_dev(const icnv_counts *cnt, int64_t G, int64_t C, const int32_t *gene_map_dev, int64_t n_genes_out,
+                        const int32_t *cells_dev, int64_t n_cells, int64_t *colptr_out, int32_t *rowidx_out, int32_t *vals_out,
+                        int64_t capacity, int64_t *nnz_out, void *stream);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

@@ -204,39 +204,138 @@ def _matrix_on_device(raw_counts_matrix, delim, gene_names, cell_names, chunk_by
     return [str(g) for g in gene_names], [str(c) for c in cell_names], torch.from_numpy(np.ascontiguousarray(m.T)).cuda(), None
 
 
+def make_unique(names, sep="."):
+    """R's make.unique: the first occurrence of a name stays, every later one gets `sep` and the smallest number, counted up
+    from 1 per name, that gives a string neither among the input nor handed out before."""
+    taken, used, nxt, out = set(names), set(), {}, []
+    for n in names:
+        if n not in used:
+            used.add(n)
+            out.append(n)
+            continue
+        k = nxt.get(n, 1)
+        while f"{n}{sep}{k}" in taken:
+            k += 1
+        taken.add(f"{n}{sep}{k}")
+        nxt[n] = k + 1
+        out.append(f"{n}{sep}{k}")
+    return out
+
+
+def _name_list(src, column, what):
+    """Names given as a list, or as the path of a .tsv[.gz] whose `column`-th tab-separated field (1-based) holds them."""
+    if not isinstance(src, (str, os.PathLike)):
+        return [str(v) for v in src]
+    out = []
+    with _open_text(src) as fh:
+        for no, line in enumerate(fh, 1):
+            line = line.rstrip("\n").rstrip("\r")
+            if not line:
+                continue
+            toks = line.split("\t")
+            if len(toks) < column:
+                raise ValueError(f"{what}: line {no} has {len(toks)} fields, column {column} is asked for")
+            out.append(toks[column - 1])
+    return out
+
+
+def _first_existing(directory, names):
+    for n in names:
+        if os.path.exists(os.path.join(directory, n)):
+            return os.path.join(directory, n)
+    raise ValueError(f"{directory}: none of {', '.join(names)} is there")
+
+
+def _mtx_source(raw_counts_matrix, gene_names, cell_names, gene_column):
+    """(matrix path, gene names, cell names) when the matrix is a MatrixMarket file or a directory in 10x layout, else None."""
+    if not isinstance(raw_counts_matrix, (str, os.PathLike)):
+        return None
+    path = os.fspath(raw_counts_matrix)
+    if os.path.isdir(path):                                              # what Seurat::Read10X reads
+        mtx = _first_existing(path, ("matrix.mtx.gz", "matrix.mtx"))
+        genes = _name_list(_first_existing(path, ("features.tsv.gz", "features.tsv", "genes.tsv")), gene_column, "features")
+        cells = _name_list(_first_existing(path, ("barcodes.tsv.gz", "barcodes.tsv")), 1, "barcodes")
+        return mtx, make_unique(genes), cells
+    if not (path.endswith(".mtx") or path.endswith(".mtx.gz")):
+        return None
+    if gene_names is None or cell_names is None:
+        raise ValueError("a .mtx matrix comes with gene_names and cell_names (lists, or paths of .tsv files)")
+    return path, _name_list(gene_names, gene_column, "gene_names"), _name_list(cell_names, 1, "cell_names")
+
+
 def CreateInfercnvObject(raw_counts_matrix, gene_order_file, annotations_file, ref_group_names, delim="\t", max_cells_per_group=None,
                          min_max_counts_per_cell=(100, float("inf")), chr_exclude=CHR_EXCLUDE, seed=0, gene_names=None,
-                         cell_names=None, return_device=False, chunk_bytes=None):
+                         cell_names=None, return_device=False, chunk_bytes=None, sparse=None, gene_column=2):
     """CreateInfercnvObject (R/inferCNV.R:133-337) with the reference's formals, plus `seed` (the down-sampling of
     max_cells_per_group; see the module's notes on the deviations), `gene_names` / `cell_names` (for a matrix given as a NumPy
-    array or a scipy sparse matrix, genes x cells) and `return_device`.
+    array, a scipy sparse matrix or a .mtx file, genes x cells), `return_device`, `sparse` and `gene_column`.
 
     raw_counts_matrix: a path (text, or .gz; .rds raises NotImplementedError), an array or a sparse matrix.  gene_order_file,
     annotations_file: paths, or small tables given as rows.  The matrix file is parsed on the device; a byte outside the
     grammar of include/icnv.h raises IcnvError with its line and field.
 
+    Sparse input (DESIGN K22).  raw_counts_matrix may also be a MatrixMarket coordinate file (.mtx, .mtx.gz; gene_names and
+    cell_names are then lists, or paths of .tsv[.gz] files whose `gene_column`-th, for cells first, column holds the names), or a
+    directory in 10x layout (matrix.mtx[.gz], features.tsv[.gz] or genes.tsv, barcodes.tsv[.gz]; the gene names are the
+    `gene_column`-th column made unique as R's make.unique does, which is what Seurat::Read10X hands the reference).
+      sparse = None   every input that worked before takes the route it took (a sparse object is densified by toarray());
+                      .mtx and directory input take the sparse route
+      sparse = True   a scipy sparse matrix (anything with tocsc) stays sparse too
+      sparse = False  .mtx input is expanded on the device (DeviceCounts.to_dense) and continues on the dense route
+    The sparse route: device.read_mtx or DeviceCounts.from_scipy, the name and annotation checks, .order_reduce, the column
+    sums over the kept genes (device.ingest_col_sums: integer sums, equal to the dense route's bit for bit), the cell filter,
+    device.csc_select.  expr_data and count_data are then the same scipy.sparse.csc_matrix (float64 data, as a dgCMatrix
+    holds; the entries of a column in the file's order); every other slot is what the dense route gives.  The counts must be
+    integers in 0 .. 2^31 - 1 (ValueError pointing to sparse=False otherwise).
+
     Returns the InfercnvObject: expr_data and count_data (the same genes x cells array, as in R), gene_order (chr, start, stop),
     gene_names, cell_names, the two 0-based index dicts, options (chr_exclude, max_cells_per_group, min_max_counts_per_cell,
     counts_md5 = None), validated.  return_device = True returns (object, x) with x the (cells, genes) CUDA float64 tensor of
-    the same values, for a caller that goes on with device.*."""
+    the same values -- on the sparse route the CSC DeviceCounts --, for a caller that goes on with device.*."""
     from . import device
     positions = read_gene_order(gene_order_file, chr_exclude)
     annotations = read_annotations(annotations_file, delim)
-    genes, cells, x, _ = _matrix_on_device(raw_counts_matrix, delim, gene_names, cell_names, chunk_bytes)
+    counts = x = None
+    mtx = _mtx_source(raw_counts_matrix, gene_names, cell_names, gene_column)
+    if mtx is not None:
+        genes, cells = mtx[1], mtx[2]
+        counts, _ = device.read_mtx(mtx[0], chunk_bytes=chunk_bytes)
+        if (counts.G, counts.C) != (len(genes), len(cells)):
+            raise ValueError(f"the matrix is {counts.G} x {counts.C}, but there are {len(genes)} gene names and {len(cells)} cell names")
+        if sparse is False:
+            counts, x = None, counts.to_dense()
+    elif sparse and hasattr(raw_counts_matrix, "tocsc"):
+        if gene_names is None or cell_names is None:
+            raise ValueError("a matrix given as an array comes with gene_names and cell_names")
+        genes, cells = [str(g) for g in gene_names], [str(c) for c in cell_names]
+        if tuple(raw_counts_matrix.shape) != (len(genes), len(cells)):
+            raise ValueError("the matrix must be genes x cells, with one name per row and per column")
+        counts = device.DeviceCounts.from_scipy(raw_counts_matrix)
+    elif sparse:
+        raise ValueError("sparse=True wants a .mtx file, a 10x directory or a scipy sparse matrix")
+    else:
+        genes, cells, x, _ = _matrix_on_device(raw_counts_matrix, delim, gene_names, cell_names, chunk_bytes)
     if _first_duplicate(genes) is not None:
         raise ValueError(f"{ERR_DUP_ROW_NAMES} ({_first_duplicate(genes)!r})")
     check_annotated_cells(cells, annotations)                      # before .order_reduce, as in R; select_cells refuses duplicates
     rows, chrs, start, stop = order_reduce(genes, positions)
     if rows is None:
         raise ValueError(ERR_NO_GENES)
-    x = device.gather_matrix(x, genes=rows)                              # kept genes in genomic order, every cell
-    cs = device.col_sums(x).cpu().numpy()
+    if counts is not None:
+        cs = device.ingest_col_sums(counts, rows).cpu().numpy()          # over the kept genes, every cell
+    else:
+        x = device.gather_matrix(x, genes=rows)                          # kept genes in genomic order, every cell
+        cs = device.col_sums(x).cpu().numpy()
     columns, _, ref, obs = select_cells(cells, cs, annotations, ref_group_names, min_max_counts_per_cell, max_cells_per_group, seed)
     if columns.size == 0:
         raise ValueError("no cell is left after the counts-per-cell filter and the annotations")
-    if columns.size != len(cells):
-        x = device.gather_matrix(x, cells=columns)
-    expr = x.cpu().numpy().T                                             # genes x cells, R's column-major storage
+    if counts is not None:
+        x = device.csc_select(counts, rows, columns)
+        expr = x.to_scipy()                                              # genes x cells, float64 data
+    else:
+        if columns.size != len(cells):
+            x = device.gather_matrix(x, cells=columns)
+        expr = x.cpu().numpy().T                                         # genes x cells, R's column-major storage
     obj = InfercnvObject(expr_data=expr, count_data=expr, gene_order=GeneOrder(chr=np.array(chrs), start=np.array(start), stop=np.array(stop)),
                          reference_grouped_cell_indices=ref, observation_grouped_cell_indices=obs,
                          options={"chr_exclude": list(chr_exclude) if chr_exclude is not None else None,

@@ -1502,6 +1502,48 @@ class DeviceCounts:
     def device(self):
         return next(t for t in self.t if t is not None).device
 
+    @property
+    def nnz(self):
+        """Stored entries of the CSC form (None for the dense form)."""
+        return None if self.t[0] is not None else int(self.t[3].numel())
+
+    @classmethod
+    def from_scipy(cls, m, device=None):
+        """Upload a scipy sparse matrix (genes x cells, anything with tocsc) as CSC in its canonical form: tocsc(),
+        sum_duplicates(), sort_indices().  The values must be integers in 0 .. 2^31 - 1, as ops.ingest_counts asks (ValueError)."""
+        m = m.tocsc().copy()
+        m.sum_duplicates()
+        m.sort_indices()
+        vals = np.ascontiguousarray(m.data)
+        if not np.array_equal(vals, np.rint(vals)) or (vals.size and (vals.min() < 0 or vals.max() > 0x7fffffff)):
+            raise ValueError("the sparse route wants integer counts in 0 .. 2^31 - 1; pass sparse=False for other data")
+        G, C = m.shape
+        if G < 1 or C < 1:
+            raise ValueError("the matrix must have at least one gene and one cell")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return cls(G, C, colptr=torch.from_numpy(np.ascontiguousarray(m.indptr, dtype=np.int64)).to(dev),
+                   rowidx=torch.from_numpy(np.ascontiguousarray(m.indices, dtype=np.int32)).to(dev),
+                   vals=torch.from_numpy(vals.astype(np.int32)).to(dev))
+
+    def to_scipy(self, dtype=np.float64):
+        """Download to a scipy.sparse.csc_matrix, genes x cells (float64 data by default, as a dgCMatrix holds).  The entries of
+        a column keep their stored order."""
+        from scipy.sparse import csc_matrix
+        if self.t[0] is not None:
+            return csc_matrix(self.t[0].cpu().numpy().T.astype(dtype))
+        _, colptr, rowidx, vals = self.t
+        return csc_matrix((vals.cpu().numpy().astype(dtype), rowidx.cpu().numpy(), colptr.cpu().numpy()), shape=(self.G, self.C))
+
+    def to_dense(self):
+        """The (C, G) CUDA float64 tensor of the counts, expanded on the device (icnv_ingest_apply_dev with normalise and log2
+        off)."""
+        L = _lib.load()
+        keep = torch.arange(self.G, dtype=torch.int32, device=self.device)
+        out = torch.empty((self.C, self.G), dtype=torch.float64, device=self.device)
+        check(L.icnv_ingest_apply_dev(ct.byref(self.c), self.G, self.C, _ptr(keep), self.G, None, 1.0, 0, 0, _ptr(out), _stream()))
+        torch.cuda.current_stream().synchronize()
+        return out
+
 
 def ingest_gene_stats(counts):
     """[G sums | G counts of cells with a positive count] as one float64 tensor (all-reduce it in a sharded run)."""
@@ -1555,6 +1597,266 @@ def ingest_counts(counts, min_mean_expr_cutoff=None, min_cells_per_gene=0, norma
                                    keep.ctypes.data_as(ct.POINTER(ct.c_int32)), ct.byref(n), _ptr(buf), ct.byref(used), _stream()))
     g_out = n.value
     return buf[: counts.C * g_out].view(counts.C, g_out), keep[:g_out].copy(), used.value
+
+
+# ------------------------------------------------------------------ sparse count matrices (DESIGN K22)
+READ_MTX_CHUNK = 64 << 20          # bytes of one chunk of read_mtx; ICNV_READ_MTX_CHUNK (developer switch) overrides it
+_MM_FIELDS = {"integer": _lib.MM_INTEGER, "real": _lib.MM_REAL, "pattern": _lib.MM_PATTERN}
+
+
+def _mtx_header(f):
+    """The banner, the % comment lines and the size line of a MatrixMarket file open for reading bytes: (field code, G, C,
+    nnz, lines read, bytes read).  Only `%%MatrixMarket matrix coordinate {integer|real|pattern} general` is accepted."""
+    line = f.readline()
+    n_lines, n_bytes = 1, len(line)
+    toks = line.decode("latin-1").split()
+    if not toks or toks[0].lower() != "%%matrixmarket":
+        raise ValueError("read_mtx: the banner line must start with %%MatrixMarket")
+    if len(toks) != 5:
+        raise ValueError(f"read_mtx: the banner has {len(toks)} fields, 5 are expected")
+    obj, fmt, field, symmetry = (t.lower() for t in toks[1:])
+    if obj != "matrix":
+        raise ValueError(f"read_mtx: banner object '{toks[1]}': only 'matrix' is read")
+    if fmt != "coordinate":
+        raise ValueError(f"read_mtx: banner format '{toks[2]}': only 'coordinate' is read")
+    if field not in _MM_FIELDS:
+        raise ValueError(f"read_mtx: banner field '{toks[3]}': only 'integer', 'real' and 'pattern' are read")
+    if symmetry != "general":
+        raise ValueError(f"read_mtx: banner symmetry '{toks[4]}': only 'general' is read")
+    while True:
+        line = f.readline()
+        if not line:
+            raise ValueError("read_mtx: the size line is missing")
+        n_lines, n_bytes = n_lines + 1, n_bytes + len(line)
+        if line.startswith(b"%") or not line.strip():
+            continue
+        toks = line.split()
+        if len(toks) != 3 or not all(t.isdigit() and len(t) <= 18 for t in toks):
+            raise ValueError(f"read_mtx: size line '{line.decode('latin-1').strip()}': three integers G C nnz are expected")
+        G, C, nnz = (int(t) for t in toks)
+        if not (1 <= G <= 0x7fffffff and 1 <= C <= 0x7fffffff):
+            raise ValueError("read_mtx: size line: G and C must be 1 .. 2147483647")
+        if nnz > G * C:
+            raise ValueError(f"read_mtx: size line: {nnz} entries do not fit a {G} x {C} matrix")
+        return _MM_FIELDS[field], G, C, nnz, n_lines, n_bytes
+
+
+def parse_triplets_into(text_dev, text_host, n_bytes, field, G, C, row, col, val, offset, line0=1):
+    """icnv_parse_triplets_dev: the first n_bytes of `text_dev` (contiguous CUDA uint8) and of `text_host` (uint8 numpy array
+    with the same bytes) are whole lines of the body of a coordinate file of a G x C matrix; entry k of them goes to slot
+    offset + k of row / col / val (CUDA int32 of one length).  Returns the entries found.  On an IcnvError the arrays are as they
+    were.  Synchronises the stream."""
+    L = _lib.load()
+    if not (isinstance(text_dev, torch.Tensor) and text_dev.is_cuda and text_dev.dtype == torch.uint8 and text_dev.dim() == 1
+            and text_dev.is_contiguous()):
+        raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
+    host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
+    if not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
+        raise TypeError("text_host must be a contiguous one-dimensional uint8 array")
+    n_bytes, offset = int(n_bytes), int(offset)
+    if n_bytes < 1 or n_bytes > text_dev.numel() or n_bytes > host.size:
+        raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
+    for t in (row, col, val):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+                and t.numel() == row.numel()):
+            raise TypeError("row, col and val must be contiguous CUDA int32 vectors of one length")
+    if offset < 0 or offset > row.numel():
+        raise ValueError("offset must be 0 .. the length of the arrays")
+    capacity = row.numel() - offset
+    at = [ct.c_void_p(t.data_ptr() + 4 * offset) if capacity else ct.c_void_p(0) for t in (row, col, val)]
+    n = ct.c_int64(0)
+    check(L.icnv_parse_triplets_dev(_ptr(text_dev), ct.c_void_p(host.ctypes.data), n_bytes, int(field), int(G), int(C), int(line0), at[0], at[1],
+                                    at[2], capacity, ct.byref(n), _stream()))
+    return int(n.value)
+
+
+def csc_from_sorted_triplets(row, col, G, C):
+    """icnv_csc_from_sorted_triplets_dev: (colptr, -1, CSC_SORTED) for triplets in strictly ascending (col, row) order -- row
+    and the values are then the CSC's arrays as they are --, or (None, k, CSC_DUPLICATE | CSC_DESCENT) with k the first entry
+    whose key does not exceed its predecessor's."""
+    L = _lib.load()
+    nnz = int(row.numel())
+    colptr = torch.empty(int(C) + 1, dtype=torch.int64, device=row.device)
+    first, kind = ct.c_int64(-1), ct.c_int32(0)
+    check(L.icnv_csc_from_sorted_triplets_dev(_ptr(row) if nnz else None, _ptr(col) if nnz else None, nnz, int(G), int(C), _ptr(colptr),
+                                              ct.byref(first), ct.byref(kind), _stream()))
+    return (colptr if kind.value == _lib.CSC_SORTED else None), int(first.value), int(kind.value)
+
+
+def _count_entries(path, skip_bytes):
+    """The lines after the first skip_bytes of the (decompressed) file that are not blank: the error path of read_mtx."""
+    import gzip
+    count = 0
+    with (gzip.open(path, "rb") if str(path).endswith(".gz") else open(path, "rb")) as f:
+        f.read(skip_bytes)
+        for line in f:
+            count += bool(line.strip(b" \t\r\n"))
+    return count
+
+
+def read_mtx(path, chunk_bytes=None):
+    """A MatrixMarket coordinate file (10x: matrix.mtx, or .gz) to a CSC DeviceCounts, parsed on the device
+    (icnv_parse_triplets_dev, icnv_csc_from_sorted_triplets_dev; DESIGN K22; the grammar and what is refused: include/icnv.h
+    "sparse count matrices").  Returns (DeviceCounts, stats).
+
+    The banner, the % comment lines and the size line `G C nnz` are read here; only `%%MatrixMarket matrix coordinate
+    {integer|real|pattern} general` is accepted (ValueError names the banner field otherwise).  The body is streamed in chunks
+    of whole lines through two pinned buffers and a device buffer while a thread reads ahead; .gz goes through Python's gzip.
+    The triplet arrays are allocated once from the size line, every chunk parses into its offset, and an entry count other than
+    the size line's is a ValueError with both numbers.  A refused byte raises IcnvError with the file line and the field.
+
+    A file in column-major order (what 10x and scipy.io.mmwrite of a CSC matrix write) needs no sort: its rows and values are
+    the CSC's arrays as parsed.  Any other order is sorted by the 64-bit key col * G + row with torch.sort and gathered --
+    PyTorch as plumbing on the cold path; there is no hand-written device sort --, stats["sorted_on_device"] = 1.  A (row,
+    column) pair stored twice raises ValueError("duplicate entry for row R, column C"), 1-based.
+
+    stats: bytes (of the body), chunks, entries, sorted_on_device, read_s / parse_s / stall_s / wall_s."""
+    import gzip
+    import queue
+    import threading
+    import time
+    path = os.fspath(path)
+    cap0 = max(64, int(chunk_bytes if chunk_bytes is not None else os.environ.get("ICNV_READ_MTX_CHUNK", READ_MTX_CHUNK)))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stats = {"bytes": 0, "chunks": 0, "entries": 0, "sorted_on_device": 0, "read_s": 0.0, "parse_s": 0.0, "stall_s": 0.0}
+    t_start = time.perf_counter()
+    f = gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")
+    try:
+        field, G, C, nnz, header_lines, header_bytes = _mtx_header(f)
+    except BaseException:
+        f.close()
+        raise
+    jobs, free, failure = queue.Queue(), [threading.Semaphore(1), threading.Semaphore(1)], []
+    stop = threading.Event()
+    pin = [_pinned(cap0), _pinned(cap0)]
+
+    def reader():
+        try:
+            slot, fill, eof = 0, 0, False
+            free[0].acquire()
+            while not eof and not stop.is_set():
+                t0 = time.perf_counter()
+                arr = pin[slot].numpy()
+                total = fill
+                while total < arr.size:
+                    got = f.readinto(memoryview(arr)[total:])
+                    if not got:
+                        eof = True
+                        break
+                    total += got
+                cut = total if eof else _last_newline(arr, total) + 1
+                stats["read_s"] += time.perf_counter() - t0
+                if cut == 0 and not eof:                          # one line is longer than the buffer: grow it and read on
+                    bigger = _pinned(2 * arr.size)
+                    bigger[:total].copy_(pin[slot][:total])
+                    pin[slot], fill = bigger, total
+                    continue
+                jobs.put((slot, pin[slot], cut))                  # only this thread writes a buffer, and only while it holds it
+                nxt = 1 - slot
+                free[nxt].acquire()                               # the chunk before this one has left that buffer
+                tail = total - cut
+                if pin[nxt].numel() <= tail:
+                    pin[nxt] = _pinned(2 * tail)
+                if tail:
+                    pin[nxt][:tail].copy_(pin[slot][cut:total])
+                slot, fill = nxt, tail
+        except Exception as exc:                                  # handed to the caller's thread below
+            failure.append(exc)
+        finally:
+            jobs.put(None)
+
+    row, col, val = (torch.empty(nnz, dtype=torch.int32, device=dev) for _ in range(3))
+    dbuf, offset, filled = None, 0, 0                              # bytes of the body before this chunk; entries so far
+    thread = threading.Thread(target=reader, daemon=True)
+    thread.start()
+    try:
+        job = jobs.get()
+        while job is not None:
+            slot, buf, n = job
+            if n > 0:
+                if dbuf is None or dbuf.numel() < n:
+                    dbuf = torch.empty(max(cap0, n), dtype=torch.uint8, device=dev)
+                t0 = time.perf_counter()
+                dbuf[:n].copy_(buf[:n], non_blocking=True)
+                host = buf.numpy()[:n]
+                try:
+                    filled += parse_triplets_into(dbuf, host, n, field, G, C, row, col, val, filled)
+                except _lib.IcnvError as exc:
+                    if exc.code != _lib.ERR_ARG or not ("capacity" in str(exc) or "line " in str(exc)):
+                        raise
+                    if "capacity" in str(exc):
+                        raise ValueError(f"read_mtx: the size line says {nnz} entries, the body has "
+                                         f"{_count_entries(path, header_bytes)}") from None
+                    line0 = 1 + _count_newlines(path, header_bytes + offset)      # the refusal again, with the file's line number
+                    parse_triplets_into(dbuf, host, n, field, G, C, row, col, val, filled, line0=line0)
+                    raise
+                stats["parse_s"] += time.perf_counter() - t0
+                stats["chunks"] += 1
+            offset += n
+            free[slot].release()
+            t0 = time.perf_counter()
+            job = jobs.get()
+            stats["stall_s"] += time.perf_counter() - t0
+    finally:
+        stop.set()
+        torch.cuda.synchronize()
+        for sem in free:
+            sem.release()
+        thread.join()
+        f.close()
+    if failure:
+        raise failure[0]
+    if filled != nnz:
+        raise ValueError(f"read_mtx: the size line says {nnz} entries, the body has {filled}")
+    stats["bytes"], stats["entries"] = offset, filled
+    colptr, first, kind = csc_from_sorted_triplets(row, col, G, C)
+    if kind == _lib.CSC_DESCENT:
+        key, perm = torch.sort(col.to(torch.int64) * G + row)
+        del key
+        row, col, val = row[perm], col[perm], val[perm]
+        del perm
+        stats["sorted_on_device"] = 1
+        colptr, first, kind = csc_from_sorted_triplets(row, col, G, C)
+        if kind == _lib.CSC_DESCENT:
+            raise RuntimeError("read_mtx: the sorted triplets are not in order (internal error)")
+    if kind == _lib.CSC_DUPLICATE:
+        raise ValueError(f"duplicate entry for row {int(row[first]) + 1}, column {int(col[first]) + 1}")
+    del col
+    counts = DeviceCounts(G, C, colptr=colptr, rowidx=row, vals=val)
+    torch.cuda.synchronize()
+    stats["wall_s"] = time.perf_counter() - t_start
+    return counts, stats
+
+
+def csc_select(counts, genes, cells):
+    """.order_reduce and the cell filter on a CSC DeviceCounts (icnv_csc_select_dev): the rows `genes` (0-based, in their new
+    order, no repeats) and the columns `cells` (0-based, any order, repeats allowed) as a new CSC DeviceCounts.  The entries
+    of an output column keep the order they have in the source column."""
+    L = _lib.load()
+    if counts.t[0] is not None:
+        raise ValueError("csc_select wants the counts in CSC form")
+    genes = np.asarray(genes, dtype=np.int64).ravel()
+    cells = np.ascontiguousarray(np.asarray(cells, dtype=np.int64).ravel())
+    if genes.size < 1 or genes.min() < 0 or genes.max() >= counts.G:
+        raise ValueError("genes must list at least one row of the matrix, and only rows of it")
+    if cells.size < 1 or cells.min() < 0 or cells.max() >= counts.C:
+        raise ValueError("cells must list at least one column of the matrix, and only columns of it")
+    gene_map = np.full(counts.G, -1, dtype=np.int32)
+    gene_map[genes] = np.arange(genes.size, dtype=np.int32)
+    if np.count_nonzero(gene_map >= 0) != genes.size:
+        raise ValueError("genes lists a row twice")
+    dev = counts.device
+    gm, cl = torch.from_numpy(gene_map).to(dev), torch.from_numpy(cells.astype(np.int32)).to(dev)
+    colptr = torch.empty(cells.size + 1, dtype=torch.int64, device=dev)
+    nnz = ct.c_int64(0)
+    check(L.icnv_csc_select_dev(ct.byref(counts.c), counts.G, counts.C, _ptr(gm), int(genes.size), _ptr(cl), int(cells.size), _ptr(colptr),
+                                None, None, 0, ct.byref(nnz), _stream()))
+    rowidx = torch.empty(nnz.value, dtype=torch.int32, device=dev)
+    vals = torch.empty(nnz.value, dtype=torch.int32, device=dev)
+    if nnz.value:
+        check(L.icnv_csc_select_dev(ct.byref(counts.c), counts.G, counts.C, _ptr(gm), int(genes.size), _ptr(cl), int(cells.size),
+                                    _ptr(colptr), _ptr(rowidx), _ptr(vals), nnz.value, ct.byref(nnz), _stream()))
+    return DeviceCounts(int(genes.size), int(cells.size), colptr=colptr, rowidx=rowidx, vals=vals)
 
 
 def cells_moments_partial(x, cell_idx, phase, mean=0.0):

@@ -70,7 +70,8 @@ def _keep_gene_rows(infercnv_obj, keep):
     """The per-gene slots of remove_genes (R/inferCNV.R:445-457) restricted to rows `keep`; expr.data is the caller's."""
     new = infercnv_obj.copy()
     if infercnv_obj.count_data is not None:
-        new.count_data = np.asarray(infercnv_obj.count_data)[keep]
+        cd = infercnv_obj.count_data                                   # a scipy sparse matrix (CreateInfercnvObject's sparse route) stays one
+        new.count_data = cd[keep] if hasattr(cd, "tocsc") else np.asarray(cd)[keep]
     go = infercnv_obj.gene_order
     new.gene_order = type(go)(np.asarray(go.chr)[keep], None if go.start is None else np.asarray(go.start)[keep],
                               None if go.stop is None else np.asarray(go.stop)[keep])
