@@ -220,6 +220,23 @@ def scale_infercnv_expr(infercnv_obj: InfercnvObject) -> InfercnvObject:
     return _with_expr(infercnv_obj, out, hs)
 
 
+def split_references(infercnv_obj: InfercnvObject, num_groups=2, hclust_method="complete") -> InfercnvObject:
+    """Step 6 of run() (num_ref_groups, off by default; R/inferCNV_ops.R:1917-1947): hclust(parallelDist(t(expr.data[, refs])))
+    of the reference cells in get_reference_grouped_cell_indices() order on the device (K9), cutree(k = num_groups), and the
+    groups "refgrp-1", ... in order of first appearance, each group's cells ascending (which(colnames %in% names))."""
+    from . import heatmap, tumor_subclusters
+    if not infercnv_obj.has_reference_cells():
+        raise ValueError("Error, no reference cells defined. Cannot split them into groups as requested")
+    ref = np.asarray(infercnv_obj.get_reference_grouped_cell_indices(), dtype=np.int64)
+    hc = tumor_subclusters.hclust(infercnv_obj, ref, hclust_method)
+    split_groups = heatmap.cutree_k(hc.merge, num_groups)
+    new = infercnv_obj.copy()
+    new.reference_grouped_cell_indices = {}
+    for counter, cut_group in enumerate(dict.fromkeys(split_groups.tolist()), start=1):
+        new.reference_grouped_cell_indices["refgrp-%d" % counter] = np.sort(ref[split_groups == cut_group]).astype(np.int32)
+    return new
+
+
 def _remove_tails(chr_idx, tail_length):
     """.remove_tails (R/inferCNV_ops.R:2370-2386): the first and last tail_length positions of a chromosome's gene index
     vector (0-based here); nothing when the tail or the chromosome is shorter than 3; a chromosome shorter than two

@@ -197,6 +197,27 @@ def hclust(infercnv_obj: InfercnvObject, cells, method: str = "ward.D2", genes=N
     return HClust(merge.cpu().numpy(), height.cpu().numpy(), order.cpu().numpy(), labels, method)
 
 
+def redo_hierarchical_clustering(infercnv_obj: InfercnvObject, hclust_method) -> InfercnvObject:
+    """.redo_hierarchical_clustering (R/inferCNV_ops.R:3231-3249; step 17 of run() after a random_trees partition): every
+    group's `hc` replaced by hclust(parallelDist(t(expr.data[, cells]))) of all its subclusters' cells sorted by index -- one
+    K9 batch over the groups."""
+    ts = infercnv_obj.tumor_subclusters
+    groups = {g: np.sort(np.concatenate([np.asarray(v, dtype=np.int64).ravel() for v in subs.values()]))
+              for g, subs in ts["subclusters"].items()}
+    for g, c in groups.items():
+        if c.size < 2:   # R's hclust stops: "must have n >= 2 objects to cluster"
+            raise ValueError(f"group {g!r} has {c.size} cell(s): must have n >= 2 objects to cluster")
+    genes = np.arange(np.asarray(infercnv_obj.expr_data).shape[0], dtype=np.int32)
+    res = device.hclust_cells(_to_device(infercnv_obj), [(genes, c.astype(np.int32)) for c in groups.values()], hclust_method)
+    cell_names = np.asarray(infercnv_obj.cells())
+    out = infercnv_obj.copy()
+    hc = dict(ts.get("hc") or {})
+    for (g, c), (merge, height, order) in zip(groups.items(), res):
+        hc[g] = HClust(merge.cpu().numpy(), height.cpu().numpy(), order.cpu().numpy(), cell_names[c], hclust_method)
+    out.tumor_subclusters = dict(ts, hc=hc)
+    return out
+
+
 # ------------------------------------------------------------------ random-trees subclustering (DESIGN K10)
 RANDOM_TREES_ITERATIONS = 100   # num_rand_iters (R/inferCNV_tumor_subclusters.random_smoothed_trees.R:254)
 
