@@ -1108,6 +1108,22 @@ void icnv_table_parse_stats_reset(void);
 int icnv_gather_matrix_dev(const double *in, int64_t ld_in, int64_t G_in, int64_t C_in, const int32_t *genes, int64_t n_genes,
                            const int32_t *cells, int64_t n_cells, double *out, int64_t ld_out, void *stream);
 
+/* ---- exact sum of a matrix (K23) -----------------------------------------------------------------------------------------------
+ * mean(infercnv_obj@expr.data), the first line of plot_per_group (R/infercnv_sampling.R:522) and plot_cnv's default x.center:
+ * the sum of the G * C values of a (C, G) matrix whose rows lie ld >= G apart (the padding is never read), as the exact real sum
+ * rounded to double once, to nearest with ties to even.  That is Python's math.fsum wherever math.fsum returns, and the same
+ * rule where it raises "intermediate overflow".  Any NaN gives NaN; +Inf and -Inf together give NaN; infinities of one sign give
+ * that infinity; a finite exact sum beyond the double range gives +-Inf; a zero sum is +0.0.  The result is the same on every
+ * run and for every launch shape.  DESIGN.md section 4 K23, restated in tests/sampling_restate.py.
+ * Method: every finite double is a multiple of 2^-1074; the kernel adds the significands into a fixed-point number of 68 digits
+ *   of 32 bits held in 64-bit limbs (a lane's window of four limbs in registers, a wave's limbs in LDS, one record per
+ *   workgroup), and the host adds the records, propagates the carry once and rounds.
+ * icnv_matrix_sum_dev: x is a DEVICE matrix; synchronises the stream and writes the sum into the HOST double *sum.
+ * icnv_matrix_sum: the same for a HOST matrix (recognised when resident, else uploaded).
+ * ICNV_ERR_ARG before any launch: a null matrix or result, dimensions outside 1 .. 2^31 - 1, ld < G.  Timer name: "matrix_sum". */
+int icnv_matrix_sum_dev(const double *x, int64_t ld, int64_t G, int64_t C, double *sum, void *stream);
+int icnv_matrix_sum(const double *x, int64_t ld, int64_t G, int64_t C, double *sum);
+
 /* ---- sparse count matrices (K22) ----------------------------------------------------------------------------------------------
  * The count matrix as it arrives at production size -- a MatrixMarket coordinate file (10x: matrix.mtx) or a sparse matrix in
  * memory -- becomes an icnv_counts in CSC form on the device and stays sparse through .order_reduce and the cell filter of

@@ -194,6 +194,8 @@ PROTOTYPES = {
     "icnv_table_parse_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_table_parse_stats_reset": (None, []),
     "icnv_gather_matrix_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _i64, _ip, _i64, _vp, _i64, _vp]),
+    "icnv_matrix_sum_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _dp, _vp]),
+    "icnv_matrix_sum": (ct.c_int, [_vp, _i64, _i64, _i64, _dp]),
     "icnv_parse_triplets_dev": (ct.c_int, [_vp, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64p, _vp]),
     "icnv_csc_from_sorted_triplets_dev": (ct.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64p, ct.POINTER(ct.c_int32), _vp]),
     "icnv_csc_select_dev": (ct.c_int, [ct.POINTER(Counts), _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64p, _vp]),

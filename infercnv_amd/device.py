@@ -355,6 +355,33 @@ def gather_matrix(x, genes=None, cells=None, out=None):
     return out
 
 
+# ------------------------------------------------------------------ exact sum of a matrix (DESIGN K23)
+def matrix_sum(x):
+    """The exact sum of a matrix, rounded to double once, to nearest with ties to even (icnv_matrix_sum_dev, DESIGN K23):
+    math.fsum(x) wherever math.fsum returns, and the same rule where it raises "intermediate overflow".  x: a (C, G) CUDA
+    float64 matrix with contiguous rows (a padded_matrix is fine: the padding is never read), or a 2-D float64 numpy array
+    with contiguous rows, which the library uploads (icnv_matrix_sum).  Any NaN gives NaN, infinities of both signs NaN,
+    of one sign that infinity; an exact sum beyond the double range +-Inf; a zero sum +0.0.  Synchronises the stream."""
+    L = _lib.load()
+    s = ct.c_double(0.0)
+    if isinstance(x, np.ndarray):
+        if not (x.dtype == np.float64 and x.ndim == 2 and x.size and (x.shape[1] <= 1 or x.strides[1] == 8)
+                and (x.shape[0] <= 1 or (x.strides[0] % 8 == 0 and x.strides[0] >= 8 * x.shape[1]))):
+            raise TypeError("expected a non-empty float64 numpy array of shape (cells, genes) with contiguous rows")
+        C, G = x.shape
+        ld = x.strides[0] // 8 if C > 1 else G
+        check(L.icnv_matrix_sum(ct.c_void_p(x.ctypes.data), int(ld), G, C, ct.byref(s)))
+    else:
+        C, G, ld = _check_matrix_ld(x)
+        check(L.icnv_matrix_sum_dev(_ptr(x), int(ld), G, C, ct.byref(s), _stream()))
+    return s.value
+
+
+def matrix_mean(x):
+    """mean(expr.data) as plot_per_group and plot_cnv's default x.center take it: matrix_sum(x) / (G * C)."""
+    return matrix_sum(x) / (x.shape[0] * x.shape[1])
+
+
 def _unquote(b):
     return b[1:-1] if len(b) >= 2 and b[:1] == b"\"" and b[-1:] == b"\"" else b
 

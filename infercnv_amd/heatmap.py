@@ -504,6 +504,16 @@ def plot_cnv(infercnv_obj: InfercnvObject, out_dir=".", title="inferCNV", obs_ti
     binding of them into one tree is not mirrored.  References as :1058-1090, first cell at the top.
 
     ref_contig, plot_chr_scale = True, write_phylo = True and output_format "pdf" raise NotImplementedError."""
+    return _plot_cnv(infercnv_obj, None, out_dir, title, obs_title, ref_title, cluster_by_groups, cluster_references, plot_chr_scale,
+                     chr_lengths, k_obs_groups, contig_cex, x_center, x_range, hclust_method, custom_color_pal, color_safe_pal,
+                     output_filename, output_format, png_res, dynamic_resize, ref_contig, write_expr_matrix, write_phylo, useRaster)
+
+
+def _plot_cnv(infercnv_obj, x_dev, out_dir, title, obs_title, ref_title, cluster_by_groups, cluster_references, plot_chr_scale,
+              chr_lengths, k_obs_groups, contig_cex, x_center, x_range, hclust_method, custom_color_pal, color_safe_pal,
+              output_filename, output_format, png_res, dynamic_resize, ref_contig, write_expr_matrix, write_phylo, useRaster):
+    """plot_cnv's body.  x_dev: the object's matrix as a contiguous (C, G) CUDA float64 tensor when the caller holds it on
+    the device already (plot_per_group's gathers; expr_data is then not read), or None: expr_data is uploaded."""
     if hclust_method not in device.HCLUST_METHODS:
         raise ValueError(f"Error, hclust_method: {hclust_method} is not supported")
     if output_format not in ("png", "pdf", None):
@@ -518,13 +528,15 @@ def plot_cnv(infercnv_obj: InfercnvObject, out_dir=".", title="inferCNV", obs_ti
         raise NotImplementedError("output_format 'pdf': only the PNG panels are produced")
     obj = infercnv_obj
     os.makedirs(out_dir, exist_ok=True)
-    expr = np.asarray(obj.expr_data, dtype=np.float64)
-    G, C = expr.shape
+    if x_dev is None:
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(obj.expr_data, dtype=np.float64).T)).cuda()
+    else:
+        x = x_dev
+    C, G = x.shape
     genes, cells = [str(g) for g in obj.genes()], [str(c) for c in obj.cells()]
     if x_center is None:
-        x_center = math.fsum(expr.ravel()) / expr.size     # (seconds per 10^8 values: large callers pass x_center)
+        x_center = device.matrix_mean(x)         # (K23: math.fsum's bits, without the host's seconds per 10^8 values)
     x_center = float(x_center)
-    x = torch.from_numpy(np.ascontiguousarray(expr.T)).cuda()
     out = lambda name: os.path.join(out_dir, name)
 
     if write_expr_matrix:                        # (the matrix as it came, before the clamp)

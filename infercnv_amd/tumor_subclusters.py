@@ -746,3 +746,118 @@ def _leiden_per_chr(infercnv_obj, x, kept, groups, k_nn, leiden_method, objectiv
             else:
                 out[c][name] = v
     return out
+
+
+# ------------------------------------------------------------------ trees of sampled groups (sample_object)
+def _merge_pair(a, b):
+    """One row of R's merge matrix from two node references: a singleton (negative) before a cluster (positive); two
+    singletons by leaf number, two clusters by row number."""
+    return sorted((int(a), int(b)), key=lambda v: (v > 0, abs(v)))
+
+
+def prune_hclust(tree: HClust, keep):
+    """The induced subtree of `tree` on the kept leaves: what sample_object needs from
+    as.hclust(drop.tip(as.phylo(hc), to_prune)) (R/infercnv_sampling.R:294).  There is no ape here: the result follows the
+    contract below, which is believed, not verified, to be what ape's round trip returns.
+
+    keep: a boolean mask over the leaves in label order, or the 0-based positions of the kept leaves (any order, no repeats).
+    A merge of the result exists where both sides of an original merge hold kept leaves, at that merge's height; the new rows
+    keep the original row order (heights stay non-decreasing) and R's conventions (singletons negative and before clusters,
+    two of a kind ascending).  labels: the kept labels in original label order; order: the original order filtered and
+    renumbered.  Fewer than two kept leaves: None (R's condition at :292).  Every leaf kept: an equal tree."""
+    merge = np.asarray(tree.merge)
+    n = merge.shape[0] + 1
+    keep = np.asarray(keep)
+    if keep.dtype == bool:
+        if keep.shape != (n,):
+            raise ValueError("a mask has one entry per leaf")
+        mask = keep
+    else:
+        idx = keep.astype(np.int64).ravel()
+        if idx.size and (idx.min() < 0 or idx.max() >= n or np.unique(idx).size != idx.size):
+            raise ValueError("keep: distinct 0-based leaf positions")
+        mask = np.zeros(n, dtype=bool)
+        mask[idx] = True
+    m = int(mask.sum())
+    if m < 2:
+        return None
+    new_leaf = np.cumsum(mask)                       # 1-based number of a kept leaf among the kept
+    rep = [None] * (n - 1)                           # per original row: the reference of its kept part in the new tree
+    ref = lambda v: (-int(new_leaf[-v - 1]) if mask[-v - 1] else None) if v < 0 else rep[v - 1]
+    rows, heights = [], []
+    for r in range(n - 1):
+        a, b = ref(int(merge[r, 0])), ref(int(merge[r, 1]))
+        if a is not None and b is not None:
+            rows.append(_merge_pair(a, b))
+            heights.append(tree.height[r])
+            rep[r] = len(rows)
+        else:
+            rep[r] = a if a is not None else b
+    order = np.asarray(tree.order, dtype=np.int64)
+    order = new_leaf[order - 1][mask[order - 1]]
+    return HClust(np.asarray(rows, dtype=np.int32).reshape(m - 1, 2), np.asarray(heights, dtype=np.float64),
+                  order.astype(np.asarray(tree.order).dtype), np.asarray(tree.labels)[mask], tree.method, tree.dist_method)
+
+
+def expand_hclust(tree: HClust, copies, labels=None) -> HClust:
+    """`tree` with leaf k replaced by copies[k] >= 1 leaves at distance 0 from each other: what sample_object needs from the
+    Newick gsub of R/infercnv_sampling.R:334-369 and as.hclust(read.tree(...)).  There is no ape here: the result follows the
+    contract below, which is believed, not verified, to be what ape's round trip returns.
+
+    A leaf with m >= 2 copies becomes a caterpillar of m - 1 merges at height 0.  All of those rows come first, leaf by leaf
+    in label order, then copy by copy; the original merges follow with their references remapped.  order: the original order
+    with each leaf expanded in place.  labels: `<label>_<j>`, j = 1 .. m, also `_1` for a single copy (:362-367), built from
+    `labels` (default: the tree's)."""
+    merge = np.asarray(tree.merge)
+    n = merge.shape[0] + 1
+    copies = np.asarray(copies, dtype=np.int64).ravel()
+    if copies.shape != (n,) or (copies < 1).any():
+        raise ValueError("copies: one count >= 1 per leaf")
+    base = np.asarray(tree.labels if labels is None else labels)
+    if base.shape[0] != n:
+        raise ValueError("labels: one per leaf")
+    first = np.concatenate([[0], np.cumsum(copies)[:-1]]) + 1     # 1-based number of a leaf's first copy
+    rows, leaf_ref = [], []
+    for k in range(n):
+        f, m = int(first[k]), int(copies[k])
+        if m == 1:
+            leaf_ref.append(-f)
+            continue
+        rows.append([-f, -(f + 1)])
+        for j in range(2, m):
+            rows.append([-(f + j), len(rows)])
+        leaf_ref.append(len(rows))
+    zero = len(rows)
+    for r in range(n - 1):
+        a, b = (leaf_ref[-int(v) - 1] if v < 0 else int(v) + zero for v in merge[r])
+        rows.append(_merge_pair(a, b))
+    height = np.concatenate([np.zeros(zero), np.asarray(tree.height, dtype=np.float64)])
+    order = np.concatenate([np.arange(first[k - 1], first[k - 1] + copies[k - 1]) for k in np.asarray(tree.order, dtype=np.int64)])
+    new_labels = np.array([f"{base[k]}_{j}" for k in range(n) for j in range(1, int(copies[k]) + 1)])
+    return HClust(np.asarray(rows, dtype=np.int32).reshape(-1, 2), height, order.astype(np.asarray(tree.order).dtype), new_labels,
+                  tree.method, tree.dist_method)
+
+
+def plot_subclusters(infercnv_obj: InfercnvObject, out_dir, output_filename="subcluster_as_annotations"):
+    """plot_subclusters (R/inferCNV_tumor_subclusters.R:336-361): the subclustering shown as annotation groups.  The
+    subclusters of every reference group become the reference groups; those of every observation group, then of
+    "all_observations", the observation groups (a repeated name replaces the earlier entry in place, as R's `[[<-` does);
+    tumor_subclusters is dropped; the object is drawn by plot_cnv(cluster_by_groups = TRUE, write_expr_matrix = FALSE) into
+    out_dir and returned.  An object without subclusters raises ValueError (R would draw a page without cells)."""
+    from .heatmap import plot_cnv
+    ts = infercnv_obj.tumor_subclusters
+    if not ts or not ts.get("subclusters"):
+        raise ValueError("plot_subclusters: the object has no tumor_subclusters$subclusters")
+    subs = ts["subclusters"]
+    out = infercnv_obj.copy()
+    out.reference_grouped_cell_indices = {}
+    for grp in infercnv_obj.reference_grouped_cell_indices:
+        for grp2, cells in (subs.get(grp) or {}).items():
+            out.reference_grouped_cell_indices[grp2] = np.asarray(cells)
+    out.observation_grouped_cell_indices = {}
+    for grp in list(infercnv_obj.observation_grouped_cell_indices) + ["all_observations"]:
+        for grp2, cells in (subs.get(grp) or {}).items():
+            out.observation_grouped_cell_indices[grp2] = np.asarray(cells)
+    out.tumor_subclusters = None
+    plot_cnv(out, cluster_by_groups=True, output_filename=output_filename, out_dir=out_dir, write_expr_matrix=False)
+    return out
