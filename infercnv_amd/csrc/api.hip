@@ -15,11 +15,6 @@
 
 #include "icnv_internal.h"
 #include "emission_table.h"
-#include "knn_internal.h"
-#include "hclust_internal.h"
-#include "random_trees_internal.h"
-#include "leiden_internal.h"
-#include "leiden_pca_internal.h"
 
 namespace icnv {
 
@@ -257,13 +252,6 @@ static int validate_groups(const int32_t *idx, const int32_t *off, int32_t n_grp
     return ICNV_OK;
 }
 
-template <typename T>
-static int upload(DevBuf &b, const T *host, size_t n, hipStream_t s) {
-    int rc = b.alloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (rc) return rc;
-    if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return ICNV_OK;
-}
 
 }  // namespace icnv
 
@@ -1742,1006 +1730,6 @@ int icnv_cell_distances(const double *expr, int64_t G, int64_t C, const int32_t 
     if ((rc = icnv_cell_distances_dev(in.dev, G, C, cell_idx, n, dout.as<double>(), nullptr))) return rc;
     ICNV_HIP(hipMemcpy(dist_out, dout.p, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost));
     return ICNV_OK;
-}
-
-// ---- exact kNN (K8): RANN::nn2(t(expr_data), k = k_nn) per problem (R/inferCNV_tumor_subclusters.R:726)
-namespace {
-std::atomic<int64_t> g_knn_host[6];   // calls, problems, query rows, row blocks, screened rows, forced-exhaustive rows
-std::mutex g_knn_mu;
-std::map<int, int64_t *> g_knn_dev;   // per device: KNN_STAT_DEVICE_N counters
-
-int knn_device_counters(int64_t **out) {
-    int dev = 0;
-    ICNV_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_knn_mu);
-    int64_t *&p = g_knn_dev[dev];
-    if (!p) {
-        ICNV_HIP(hipMalloc(&p, KNN_STAT_DEVICE_N * sizeof(int64_t)));
-        ICNV_HIP(hipMemset(p, 0, KNN_STAT_DEVICE_N * sizeof(int64_t)));
-    }
-    *out = p;
-    return ICNV_OK;
-}
-
-int64_t env_int(const char *name, int64_t dflt) {
-    const char *e = std::getenv(name);
-    return (e && *e) ? std::atoll(e) : dflt;
-}
-
-// every check before any device work: offsets, sizes, k, every gene and cell index
-int knn_validate(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off, const int32_t *cell_idx,
-                 const int32_t *cell_off, int32_t n_prob, int32_t k, const void *nn_idx, const void *nn_dist) {
-    if (!expr || !nn_idx || !nn_dist || !gene_idx || !gene_off || !cell_idx || !cell_off) ICNV_FAIL(ICNV_ERR_ARG, "knn: null argument");
-    if (G < 1 || G > 0x7fffffff || C < 1 || C > 0x7fffffff) ICNV_FAIL(ICNV_ERR_ARG, "knn: bad matrix dimensions");
-    if (n_prob < 1) ICNV_FAIL(ICNV_ERR_ARG, "knn: n_prob must be >= 1");
-    if (k < 1) ICNV_FAIL(ICNV_ERR_ARG, "knn: k must be >= 1");
-    if (gene_off[0] != 0 || cell_off[0] != 0) ICNV_FAIL(ICNV_ERR_ARG, "knn: offsets must start at 0");
-    for (int32_t p = 0; p < n_prob; ++p) {
-        if (gene_off[p + 1] <= gene_off[p]) ICNV_FAIL(ICNV_ERR_ARG, "knn: every problem needs at least one gene");
-        if (cell_off[p + 1] <= cell_off[p]) ICNV_FAIL(ICNV_ERR_ARG, "knn: every problem needs at least one cell");
-        if (k > cell_off[p + 1] - cell_off[p]) ICNV_FAIL(ICNV_ERR_ARG, "knn: k exceeds the cells of problem " + std::to_string(p));
-    }
-    if (k > KNN_MAX_K) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "knn: k > 128 is not supported");
-    for (int64_t i = 0; i < gene_off[n_prob]; ++i)
-        if (gene_idx[i] < 0 || gene_idx[i] >= G) ICNV_FAIL(ICNV_ERR_ARG, "knn: gene index out of range");
-    for (int64_t i = 0; i < cell_off[n_prob]; ++i)
-        if (cell_idx[i] < 0 || cell_idx[i] >= C) ICNV_FAIL(ICNV_ERR_ARG, "knn: cell index out of range");
-    return ICNV_OK;
-}
-
-struct KnnPlanBlock {
-    std::vector<int32_t> i32;   // piece_prob | piece_r0 | piece_nr
-    std::vector<int64_t> i64;   // tile_off (n + 1) | row_off (n + 1) | piece_scr (n)
-    int64_t n_tiles = 0, n_rows = 0, entries = 0;
-    int wm = 2;
-    DevBuf d_i32, d_i64;
-};
-}  // namespace
-
-int icnv_knn_dev(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off, const int32_t *cell_idx,
-                 const int32_t *cell_off, int32_t n_prob, int32_t k, int32_t *nn_idx, double *nn_dist, void *stream) {
-    int rc = knn_validate(expr, G, C, gene_idx, gene_off, cell_idx, cell_off, n_prob, k, nn_idx, nn_dist);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const bool all_exact = env_int("ICNV_KNN_EXHAUSTIVE", 0) != 0;
-    const int64_t budget = std::max<int64_t>(1, env_int("ICNV_KNN_SCRATCH_MB", 4096)) * ((int64_t)1 << 20) / 8;   // 8-byte screen entries
-    const int cap = (int)std::max<int64_t>(1, std::min<int64_t>(KNN_MAX_CAP, env_int("ICNV_KNN_CAP", KNN_DEFAULT_CAP)));
-    const int64_t max_block_rows = ((int64_t)256 << 20) / ((int64_t)cap * 4);   // candidate lists <= 256 MB
-
-    // problems: 64-bit offsets, padded row length, compact-matrix offsets
-    std::vector<int64_t> goff(n_prob + 1), coff(n_prob + 1), yoff(n_prob + 1);
-    std::vector<int32_t> ld(n_prob);
-    for (int32_t p = 0; p <= n_prob; ++p) { goff[p] = gene_off[p]; coff[p] = cell_off[p]; }
-    yoff[0] = 0;
-    for (int32_t p = 0; p < n_prob; ++p) {
-        const int64_t Gp = goff[p + 1] - goff[p];
-        ld[p] = (int32_t)(Gp + (Gp & 1));
-        yoff[p + 1] = yoff[p] + (coff[p + 1] - coff[p]) * ld[p];
-    }
-    const int64_t total_rows = coff[n_prob], total_genes = goff[n_prob];
-
-    // row blocks: pieces (problem, rows) whose screens together fit the budget (at least one row per block)
-    std::vector<std::unique_ptr<KnnPlanBlock>> blocks;
-    {
-        std::vector<int32_t> pp, pr0, pnr;
-        int64_t used = 0, rows = 0;
-        auto close = [&]() {
-            if (pp.empty()) return;
-            auto b = std::make_unique<KnnPlanBlock>();
-            const int n = (int)pp.size();
-            int64_t t128 = 0;
-            for (int i = 0; i < n; ++i) {
-                const int64_t np = coff[pp[i] + 1] - coff[pp[i]];
-                t128 += ((pnr[i] + 127) / 128) * ((np + 127) / 128);
-            }
-            b->wm = t128 >= 2 * (int64_t)num_cus() ? 4 : 2;
-            const int DT = 32 * b->wm;
-            b->i32.insert(b->i32.end(), pp.begin(), pp.end());
-            b->i32.insert(b->i32.end(), pr0.begin(), pr0.end());
-            b->i32.insert(b->i32.end(), pnr.begin(), pnr.end());
-            b->i64.assign(3 * (size_t)n + 2, 0);
-            int64_t *toff = b->i64.data(), *roff = toff + n + 1, *soff = roff + n + 1;
-            for (int i = 0; i < n; ++i) {
-                const int64_t np = coff[pp[i] + 1] - coff[pp[i]];
-                toff[i + 1] = toff[i] + ((pnr[i] + DT - 1) / DT) * ((np + DT - 1) / DT);
-                roff[i + 1] = roff[i] + pnr[i];
-                soff[i] = b->entries;
-                b->entries += (int64_t)pnr[i] * np;
-            }
-            b->n_tiles = toff[n];
-            b->n_rows = roff[n];
-            blocks.push_back(std::move(b));
-            pp.clear(); pr0.clear(); pnr.clear();
-            used = rows = 0;
-        };
-        for (int32_t p = 0; p < n_prob; ++p) {
-            const int64_t np = coff[p + 1] - coff[p];
-            int64_t r = 0;
-            while (r < np) {
-                int64_t nr = std::min({np - r, (budget - used) / np, max_block_rows - rows});
-                if (nr < 1) {
-                    if (!pp.empty()) { close(); continue; }
-                    nr = 1;
-                }
-                pp.push_back(p); pr0.push_back((int32_t)r); pnr.push_back((int32_t)nr);
-                used += nr * np; rows += nr; r += nr;
-            }
-        }
-        close();
-    }
-    for (auto &b : blocks)
-        if (b->n_tiles > 0x7fffffff || b->n_rows > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "knn: row block too large");
-    if (total_genes > ((int64_t)1 << 31) * 255 || total_rows > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "knn: batch too large");
-
-    int64_t *stats = nullptr;
-    if ((rc = knn_device_counters(&stats))) return rc;
-    DevBuf d_gidx, d_goff, d_cidx, d_coff, d_yoff, d_ld, d_shift, d_Y, d_norm, d_screen, d_cand, d_ncand;
-    int64_t max_entries = 0, max_rows = 0;
-    for (auto &b : blocks) { max_entries = std::max(max_entries, b->entries); max_rows = std::max(max_rows, b->n_rows); }
-    if ((rc = upload(d_gidx, gene_idx, (size_t)total_genes, s)) || (rc = upload(d_goff, goff.data(), goff.size(), s)) ||
-        (rc = upload(d_cidx, cell_idx, (size_t)total_rows, s)) || (rc = upload(d_coff, coff.data(), coff.size(), s)) ||
-        (rc = upload(d_yoff, yoff.data(), yoff.size(), s)) || (rc = upload(d_ld, ld.data(), ld.size(), s)) ||
-        (rc = d_norm.alloc((size_t)total_rows * sizeof(double))) || (rc = d_screen.alloc((size_t)max_entries * 8)) ||
-        (rc = d_cand.alloc((size_t)max_rows * cap * sizeof(int32_t))) || (rc = d_ncand.alloc((size_t)max_rows * sizeof(int32_t))))
-        return rc;
-    if (!all_exact && ((rc = d_shift.alloc((size_t)total_genes * sizeof(double))) || (rc = d_Y.alloc((size_t)yoff[n_prob] * sizeof(double)))))
-        return rc;
-    for (auto &b : blocks)
-        if ((rc = upload(b->d_i32, b->i32.data(), b->i32.size(), s)) || (rc = upload(b->d_i64, b->i64.data(), b->i64.size(), s))) return rc;
-
-    KnnArgs a;
-    a.x = expr; a.G = (int32_t)G;
-    a.gene_idx = d_gidx.as<int32_t>(); a.gene_off = d_goff.as<int64_t>();
-    a.cell_idx = d_cidx.as<int32_t>(); a.cell_off = d_coff.as<int64_t>();
-    a.n_prob = n_prob; a.k = k; a.total_genes = total_genes; a.total_rows = total_rows;
-    a.shift = d_shift.as<double>(); a.Y = d_Y.as<double>(); a.y_off = d_yoff.as<int64_t>(); a.ld = d_ld.as<int32_t>();
-    a.norm = d_norm.as<double>(); a.nn_idx = nn_idx; a.nn_dist = nn_dist; a.stats = stats;
-    if (!all_exact && (rc = launch_knn_prepare(a, s))) return rc;
-    for (auto &pb : blocks) {
-        KnnBlock b;
-        const int n = (int)(pb->i32.size() / 3);
-        b.n_pieces = n;
-        b.piece_prob = pb->d_i32.as<int32_t>(); b.piece_r0 = b.piece_prob + n; b.piece_nr = b.piece_r0 + n;
-        b.tile_off = pb->d_i64.as<int64_t>(); b.row_off = b.tile_off + n + 1; b.piece_scr = b.row_off + n + 1;
-        b.n_tiles = pb->n_tiles; b.n_rows = pb->n_rows;
-        b.screen = d_screen.as<uint32_t>(); b.cand = d_cand.as<int32_t>(); b.ncand = d_ncand.as<int32_t>();
-        b.cap = cap; b.all_exact = all_exact ? 1 : 0;
-        if ((rc = launch_knn_block(a, b, pb->wm, s))) return rc;
-    }
-    g_knn_host[0] += 1;
-    g_knn_host[1] += n_prob;
-    g_knn_host[2] += total_rows;
-    g_knn_host[3] += (int64_t)blocks.size();
-    g_knn_host[all_exact ? 5 : 4] += total_rows;
-    return ICNV_OK;
-}
-
-int icnv_knn(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off, const int32_t *cell_idx,
-             const int32_t *cell_off, int32_t n_prob, int32_t k, int32_t *nn_idx, double *nn_dist) {
-    int rc = knn_validate(expr, G, C, gene_idx, gene_off, cell_idx, cell_off, n_prob, k, nn_idx, nn_dist);
-    if (rc) return rc;
-    const size_t n_out = (size_t)cell_off[n_prob] * k;
-    MatrixLease in;
-    DevBuf d_idx, d_dist;
-    if ((rc = acquire_input(expr, G * C, nullptr, in)) || (rc = d_idx.alloc(n_out * sizeof(int32_t))) ||
-        (rc = d_dist.alloc(n_out * sizeof(double))))
-        return rc;
-    if ((rc = icnv_knn_dev(in.dev, G, C, gene_idx, gene_off, cell_idx, cell_off, n_prob, k, d_idx.as<int32_t>(), d_dist.as<double>(),
-                           nullptr)))
-        return rc;
-    ICNV_HIP(hipMemcpy(nn_idx, d_idx.p, n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
-    ICNV_HIP(hipMemcpy(nn_dist, d_dist.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
-    return ICNV_OK;
-}
-
-int icnv_knn_stats(int64_t *out, int32_t n) {
-    if (!out || n < 1) ICNV_FAIL(ICNV_ERR_ARG, "bad argument");
-    int64_t v[9] = {g_knn_host[0].load(), g_knn_host[1].load(), g_knn_host[2].load(), g_knn_host[3].load(), g_knn_host[4].load(), 0, 0,
-                    0, g_knn_host[5].load()};
-    std::lock_guard<std::mutex> lk(g_knn_mu);
-    if (!g_knn_dev.empty()) {
-        int cur = 0;
-        ICNV_HIP(hipGetDevice(&cur));
-        for (auto &kv : g_knn_dev) {
-            int64_t h[KNN_STAT_DEVICE_N];
-            ICNV_HIP(hipSetDevice(kv.first));
-            ICNV_HIP(hipDeviceSynchronize());
-            ICNV_HIP(hipMemcpy(h, kv.second, sizeof(h), hipMemcpyDeviceToHost));
-            v[5] += h[KNN_STAT_CANDIDATES];
-            v[6] += h[KNN_STAT_OVERFLOW_ROWS];
-            v[7] += h[KNN_STAT_EXACT_ROWS];
-        }
-        ICNV_HIP(hipSetDevice(cur));
-    }
-    for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
-    return ICNV_OK;
-}
-
-void icnv_knn_stats_reset(void) {
-    for (auto &c : g_knn_host) c.store(0);
-    std::lock_guard<std::mutex> lk(g_knn_mu);
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); return; }
-    for (auto &kv : g_knn_dev) {
-        if (hipSetDevice(kv.first) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemset(kv.second, 0, KNN_STAT_DEVICE_N * sizeof(int64_t)) != hipSuccess)
-            (void)hipGetLastError();
-    }
-    (void)hipSetDevice(cur);
-}
-
-// ---- hierarchical clustering (K9): fastcluster::hclust(as.dist(D), method) (R/inferCNV_tumor_subclusters.R:191, 582, 609,
-// R/inferCNV_ops.R:1930, 3242, R/inferCNV_heatmap.R:719, 755, 1062, 1079)
-namespace {
-std::atomic<int64_t> g_hc[6];   // calls, problems, LDS problems, HBM problems, chain steps, wall microseconds
-
-int hclust_method_check(int32_t method) {
-    if (method < ICNV_HCLUST_WARD_D || method > ICNV_HCLUST_MCQUITTY)
-        ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "hclust: unsupported method (centroid and median are not reducible)");
-    return ICNV_OK;
-}
-
-// R's hclust object from one problem's raw merges (chain order): stable sort by dissimilarity, union-find relabelling
-// (singletons -(i+1), clusters by sorted step, the smaller internal node first) and the left-first depth-first order
-void hclust_label(int n, const int32_t *rx, const int32_t *ry, const double *rh, bool root, int32_t *merge, double *height,
-                  int32_t *order) {
-    const int nm = n - 1;
-    std::vector<int> perm(nm), parent(2 * (size_t)n - 1);
-    std::iota(perm.begin(), perm.end(), 0);
-    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return rh[a] < rh[b]; });
-    std::iota(parent.begin(), parent.end(), 0);
-    auto find = [&](int i) {
-        int r = i;
-        while (parent[r] != r) r = parent[r];
-        while (parent[i] != r) { const int q = parent[i]; parent[i] = r; i = q; }
-        return r;
-    };
-    for (int i = 0; i < nm; ++i) {
-        const int q = perm[i];
-        int a = find(rx[q]), b = find(ry[q]);
-        parent[a] = parent[b] = n + i;
-        if (a > b) std::swap(a, b);
-        merge[i] = a < n ? -(a + 1) : a - n + 1;
-        merge[i + nm] = b < n ? -(b + 1) : b - n + 1;
-        height[i] = root ? std::sqrt(rh[q]) : rh[q];
-    }
-    std::vector<int> stack{nm};   // R labels: > 0 a merge row (1-based), < 0 a singleton
-    int o = 0;
-    while (!stack.empty()) {
-        const int v = stack.back();
-        stack.pop_back();
-        if (v < 0) { order[o++] = -v; continue; }
-        stack.push_back(merge[v - 1 + nm]);
-        stack.push_back(merge[v - 1]);
-    }
-}
-
-// The raw merges of a batch of problems, left on the device (K9's chain; K10 keeps only the maximum of most trees).
-struct HclustRaw {
-    DevBuf d_n, d_moff, d_mx, d_my, d_mh;   // per problem: cells, first raw merge; the raw merges in chain order
-    std::vector<int64_t> m_off;
-    int n_lds = 0, n_hbm = 0;
-    int64_t steps = 0;
-};
-
-// Every problem's n_p x n_p matrix is at D + d_off[p] (row-major, consecutive).  Checks it and clusters every problem;
-// problem p's raw merges start at m_off[p] = c_off[p] - p.  Synchronises s.
-int hclust_raw(double *D, const std::vector<int32_t> &n, const std::vector<int64_t> &c_off, int32_t method, hipStream_t s,
-               HclustRaw &out) {
-    const int P = (int)n.size();
-    std::vector<int64_t> d_off(P + 1), &m_off = out.m_off;
-    m_off.assign(P + 1, 0);
-    d_off[0] = 0;
-    for (int p = 0; p < P; ++p) d_off[p + 1] = d_off[p] + (int64_t)n[p] * n[p];
-    for (int p = 0; p <= P; ++p) m_off[p] = c_off[p] - p;
-    const int64_t total_cells = c_off[P], total_merges = m_off[P];
-    int rc;
-    DevBuf d_bad;
-    uint32_t bad = 0;
-    if ((rc = d_bad.alloc(sizeof(uint32_t)))) return rc;
-    ICNV_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
-    if ((rc = launch_hclust_prep(D, d_off[P], method == ICNV_HCLUST_WARD_D2, d_bad.as<uint32_t>(), s))) return rc;
-    ICNV_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    if (bad) ICNV_FAIL(ICNV_ERR_ARG, "hclust: NaN or infinite distance");
-
-    const bool force_hbm = env_int("ICNV_HCLUST_FORCE_HBM", 0) != 0;
-    std::vector<int32_t> run;   // LDS problems, then HBM problems
-    int max_lds = 0, max_hbm = 0;
-    for (int p = 0; p < P; ++p)
-        if (!force_hbm && n[p] <= HC_LDS_MAX_N) { run.push_back(p); max_lds = std::max(max_lds, n[p]); }
-    const int n_lds = (int)run.size();
-    for (int p = 0; p < P; ++p)
-        if (force_hbm || n[p] > HC_LDS_MAX_N) { run.push_back(p); max_hbm = std::max(max_hbm, n[p]); }
-    const int n_hbm = P - n_lds;
-
-    DevBuf d_doff, d_coff, d_run, d_steps, d_work;
-    if ((rc = upload(out.d_n, n.data(), n.size(), s)) || (rc = upload(d_doff, d_off.data(), d_off.size(), s)) ||
-        (rc = upload(out.d_moff, m_off.data(), m_off.size(), s)) || (rc = upload(d_coff, c_off.data(), c_off.size(), s)) ||
-        (rc = upload(d_run, run.data(), run.size(), s)) || (rc = out.d_mx.alloc((size_t)total_merges * sizeof(int32_t))) ||
-        (rc = out.d_my.alloc((size_t)total_merges * sizeof(int32_t))) || (rc = out.d_mh.alloc((size_t)total_merges * sizeof(double))) ||
-        (rc = d_steps.alloc((size_t)P * sizeof(int64_t))))
-        return rc;
-    if (n_hbm && (rc = d_work.alloc((size_t)total_cells * 2 * sizeof(int32_t)))) return rc;
-    HclustArgs a;
-    a.n = out.d_n.as<int32_t>(); a.d_off = d_doff.as<int64_t>(); a.D = D; a.m_off = out.d_moff.as<int64_t>();
-    a.mx = out.d_mx.as<int32_t>(); a.my = out.d_my.as<int32_t>(); a.mh = out.d_mh.as<double>();
-    a.c_off = d_coff.as<int64_t>(); a.work = d_work.as<int32_t>(); a.steps = d_steps.as<int64_t>(); a.method = method;
-    a.n_run = n_lds; a.run = d_run.as<int32_t>();
-    if ((rc = launch_hclust_lds(a, max_lds, s))) return rc;
-    a.n_run = n_hbm; a.run = d_run.as<int32_t>() + n_lds;
-    if ((rc = launch_hclust_hbm(a, max_hbm, s))) return rc;
-
-    std::vector<int64_t> steps(P);
-    ICNV_HIP(hipMemcpyAsync(steps.data(), d_steps.p, steps.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    out.steps = 0;
-    for (int p = 0; p < P; ++p) {
-        if (steps[p] < 0) ICNV_FAIL(ICNV_ERR_ARG, "hclust: a dissimilarity overflowed to a non-finite value");
-        out.steps += steps[p];
-    }
-    out.n_lds = n_lds;
-    out.n_hbm = n_hbm;
-    return ICNV_OK;
-}
-
-// hclust_raw, then R's objects written to the DEVICE outputs, problem p's at 2 (c_off[p] - p), c_off[p] - p and c_off[p].
-// Synchronises s.
-int hclust_run(double *D, const std::vector<int32_t> &n, const std::vector<int64_t> &c_off, int32_t method, int32_t *merge,
-               double *height, int32_t *order, hipStream_t s, std::chrono::steady_clock::time_point t0) {
-    const int P = (int)n.size();
-    HclustRaw raw;
-    int rc = hclust_raw(D, n, c_off, method, s, raw);
-    if (rc) return rc;
-    const std::vector<int64_t> &m_off = raw.m_off;
-    const int64_t total_cells = c_off[P], total_merges = m_off[P];
-    std::vector<int32_t> mx(total_merges), my(total_merges), hm(2 * total_merges), ho(total_cells);
-    std::vector<double> mh(total_merges), hh(total_merges);
-    ICNV_HIP(hipMemcpyAsync(mx.data(), raw.d_mx.p, mx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipMemcpyAsync(my.data(), raw.d_my.p, my.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipMemcpyAsync(mh.data(), raw.d_mh.p, mh.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    for (int p = 0; p < P; ++p) {
-        const int64_t m0 = m_off[p];
-        hclust_label(n[p], mx.data() + m0, my.data() + m0, mh.data() + m0, method == ICNV_HCLUST_WARD_D2, hm.data() + 2 * m0,
-                     hh.data() + m0, ho.data() + c_off[p]);
-    }
-    ICNV_HIP(hipMemcpyAsync(merge, hm.data(), hm.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    ICNV_HIP(hipMemcpyAsync(height, hh.data(), hh.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    ICNV_HIP(hipMemcpyAsync(order, ho.data(), ho.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    const int n_lds = raw.n_lds, n_hbm = raw.n_hbm;
-    const int64_t all_steps = raw.steps;
-    g_hc[0] += 1;
-    g_hc[1] += P;
-    g_hc[2] += n_lds;
-    g_hc[3] += n_hbm;
-    g_hc[4] += all_steps;
-    g_hc[5] += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-    return ICNV_OK;
-}
-
-int hclust_cells_validate(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off,
-                          const int32_t *cell_idx, const int32_t *cell_off, int32_t n_prob, int32_t method, const void *merge,
-                          const void *height, const void *order) {
-    if (!expr || !gene_idx || !gene_off || !cell_idx || !cell_off || !merge || !height || !order)
-        ICNV_FAIL(ICNV_ERR_ARG, "hclust: null argument");
-    if (G < 1 || G > 0x7fffffff || C < 1 || C > 0x7fffffff) ICNV_FAIL(ICNV_ERR_ARG, "hclust: bad matrix dimensions");
-    if (n_prob < 1) ICNV_FAIL(ICNV_ERR_ARG, "hclust: n_prob must be >= 1");
-    if (gene_off[0] != 0 || cell_off[0] != 0) ICNV_FAIL(ICNV_ERR_ARG, "hclust: offsets must start at 0");
-    for (int32_t p = 0; p < n_prob; ++p) {
-        if (gene_off[p + 1] <= gene_off[p]) ICNV_FAIL(ICNV_ERR_ARG, "hclust: every problem needs at least one gene");
-        const int64_t np = (int64_t)cell_off[p + 1] - cell_off[p];
-        if (np < 2) ICNV_FAIL(ICNV_ERR_ARG, "hclust: every problem needs at least two cells (problem " + std::to_string(p) + ")");
-        if (np > HC_HBM_MAX_N) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "hclust: more than 524288 cells in one problem");
-    }
-    for (int64_t i = 0; i < gene_off[n_prob]; ++i)
-        if (gene_idx[i] < 0 || gene_idx[i] >= G) ICNV_FAIL(ICNV_ERR_ARG, "hclust: gene index out of range");
-    for (int64_t i = 0; i < cell_off[n_prob]; ++i)
-        if (cell_idx[i] < 0 || cell_idx[i] >= C) ICNV_FAIL(ICNV_ERR_ARG, "hclust: cell index out of range");
-    return hclust_method_check(method);
-}
-}  // namespace
-
-int icnv_hclust_dev(const double *dist, int64_t ld, int32_t n, int32_t method, int32_t *merge, double *height, int32_t *order,
-                    void *stream) {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!dist || !merge || !height || !order) ICNV_FAIL(ICNV_ERR_ARG, "hclust: null argument");
-    if (n < 2) ICNV_FAIL(ICNV_ERR_ARG, "hclust: must have n >= 2 objects to cluster");
-    if (ld < n) ICNV_FAIL(ICNV_ERR_ARG, "hclust: ld must be >= n");
-    if (n > HC_HBM_MAX_N) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "hclust: more than 524288 objects");
-    int rc = hclust_method_check(method);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DevBuf ws;   // the chain updates its matrix in place: a private copy
-    if ((rc = ws.alloc((size_t)n * n * sizeof(double)))) return rc;
-    ICNV_HIP(hipMemcpy2DAsync(ws.p, (size_t)n * sizeof(double), dist, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), n,
-                              hipMemcpyDeviceToDevice, s));
-    return hclust_run(ws.as<double>(), {n}, {0, n}, method, merge, height, order, s, t0);
-}
-
-int icnv_hclust_cells_dev(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off,
-                          const int32_t *cell_idx, const int32_t *cell_off, int32_t n_prob, int32_t method, int32_t *merge,
-                          double *height, int32_t *order, void *stream) {
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = hclust_cells_validate(expr, G, C, gene_idx, gene_off, cell_idx, cell_off, n_prob, method, merge, height, order);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    // every problem's distances straight into the workspace, R's sequential dist over the problem's genes (distance_kernels.hip)
-    std::vector<int64_t> goff(n_prob + 1), coff(n_prob + 1), doff(n_prob + 1), toff;
-    std::vector<int32_t> n(n_prob);
-    for (int32_t p = 0; p <= n_prob; ++p) { goff[p] = gene_off[p]; coff[p] = cell_off[p]; }
-    doff[0] = 0;
-    for (int32_t p = 0; p < n_prob; ++p) {
-        n[p] = (int32_t)(coff[p + 1] - coff[p]);
-        doff[p + 1] = doff[p] + (int64_t)n[p] * n[p];
-    }
-    const int dt = exact_dist_plan(n.data(), n_prob, toff);
-    if (toff[n_prob] > 0x7fffffff || coff[n_prob] > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "hclust: batch too large");
-    DevBuf d_gidx, d_goff, d_cidx, d_coff, d_toff, d_n, d_doff, d_D;
-    if ((rc = upload(d_gidx, gene_idx, (size_t)goff[n_prob], s)) || (rc = upload(d_goff, goff.data(), goff.size(), s)) ||
-        (rc = upload(d_cidx, cell_idx, (size_t)coff[n_prob], s)) || (rc = upload(d_coff, coff.data(), coff.size(), s)) ||
-        (rc = upload(d_toff, toff.data(), toff.size(), s)) || (rc = upload(d_n, n.data(), n.size(), s)) ||
-        (rc = upload(d_doff, doff.data(), doff.size(), s)) || (rc = d_D.alloc((size_t)doff[n_prob] * sizeof(double))))
-        return rc;
-    DistArgs a{};
-    a.x = expr; a.ldx = G; a.G = (int32_t)G;
-    a.gene_idx = d_gidx.as<int32_t>(); a.gene_off = d_goff.as<int64_t>();
-    a.cell_idx = d_cidx.as<int32_t>(); a.cell_off = d_coff.as<int64_t>(); a.n = d_n.as<int32_t>();
-    a.n_prob = n_prob; a.tile_off = d_toff.as<int64_t>(); a.d_off = d_doff.as<int64_t>(); a.D = d_D.as<double>();
-    if ((rc = launch_exact_dist(a, dt, toff[n_prob], s))) return rc;
-    return hclust_run(d_D.as<double>(), n, coff, method, merge, height, order, s, t0);
-}
-
-int icnv_hclust_cells(const double *expr, int64_t G, int64_t C, const int32_t *gene_idx, const int32_t *gene_off,
-                      const int32_t *cell_idx, const int32_t *cell_off, int32_t n_prob, int32_t method, int32_t *merge,
-                      double *height, int32_t *order) {
-    int rc = hclust_cells_validate(expr, G, C, gene_idx, gene_off, cell_idx, cell_off, n_prob, method, merge, height, order);
-    if (rc) return rc;
-    const size_t cells = (size_t)cell_off[n_prob], merges = cells - (size_t)n_prob;
-    MatrixLease in;
-    DevBuf d_merge, d_height, d_order;
-    if ((rc = acquire_input(expr, G * C, nullptr, in)) || (rc = d_merge.alloc(2 * merges * sizeof(int32_t))) ||
-        (rc = d_height.alloc(merges * sizeof(double))) || (rc = d_order.alloc(cells * sizeof(int32_t))))
-        return rc;
-    if ((rc = icnv_hclust_cells_dev(in.dev, G, C, gene_idx, gene_off, cell_idx, cell_off, n_prob, method, d_merge.as<int32_t>(),
-                                    d_height.as<double>(), d_order.as<int32_t>(), nullptr)))
-        return rc;
-    ICNV_HIP(hipMemcpy(merge, d_merge.p, 2 * merges * sizeof(int32_t), hipMemcpyDeviceToHost));
-    ICNV_HIP(hipMemcpy(height, d_height.p, merges * sizeof(double), hipMemcpyDeviceToHost));
-    ICNV_HIP(hipMemcpy(order, d_order.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return ICNV_OK;
-}
-
-int icnv_hclust_stats(int64_t *out, int32_t n) {
-    if (!out || n < 1) ICNV_FAIL(ICNV_ERR_ARG, "bad argument");
-    for (int i = 0; i < n && i < 6; ++i) out[i] = g_hc[i].load();
-    return ICNV_OK;
-}
-
-void icnv_hclust_stats_reset(void) {
-    for (auto &c : g_hc) c.store(0);
-}
-
-// ---- random-trees subclustering (K10): .parameterize_random_cluster_heights_smoothed_trees
-// (R/inferCNV_tumor_subclusters.random_smoothed_trees.R:217-298) for every clade of a recursion level in one call
-namespace {
-std::atomic<int64_t> g_rt[6];   // calls, clades, permuted matrices, waves, chain steps, wall microseconds
-
-int rt_validate(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, const int32_t *cell_off, int32_t n_prob,
-                int32_t window) {
-    if (!expr || !cell_idx || !cell_off) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: null argument");
-    if (G < 1 || G > 0x7fffffff || C < 1 || C > 0x7fffffff) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: bad matrix dimensions");
-    if (n_prob < 1) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: n_prob must be >= 1");
-    if (window < 1) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: window must be >= 1");
-    if (cell_off[0] != 0) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: offsets must start at 0");
-    for (int32_t p = 0; p < n_prob; ++p) {
-        const int64_t np = (int64_t)cell_off[p + 1] - cell_off[p];
-        if (np < 2) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: every clade needs at least two cells (clade " + std::to_string(p) + ")");
-        if (np > HC_HBM_MAX_N) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "random_trees: more than 524288 cells in one clade");
-    }
-    for (int64_t i = 0; i < cell_off[n_prob]; ++i)
-        if (cell_idx[i] < 0 || cell_idx[i] >= C) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: cell index out of range");
-    return ICNV_OK;
-}
-
-// The clades' cell lists and tokens on the device, checked for non-finite values (ICNV_ERR_ARG) before anything else runs.
-struct RtClades {
-    DevBuf d_cidx, d_coff, d_tok;
-    std::vector<int64_t> coff;
-};
-
-int rt_upload_clades(const double *expr, int32_t G, const int32_t *cell_idx, const int32_t *cell_off, const uint64_t *token,
-                     int32_t n_prob, hipStream_t s, RtClades &cl) {
-    cl.coff.resize(n_prob + 1);
-    for (int32_t p = 0; p <= n_prob; ++p) cl.coff[p] = cell_off[p];
-    std::vector<uint64_t> tok(token, token + n_prob);
-    int rc;
-    DevBuf d_bad;
-    uint32_t bad = 0;
-    if ((rc = upload(cl.d_cidx, cell_idx, (size_t)cl.coff[n_prob], s)) || (rc = upload(cl.d_coff, cl.coff.data(), cl.coff.size(), s)) ||
-        (rc = upload(cl.d_tok, tok.data(), tok.size(), s)) || (rc = d_bad.alloc(sizeof(uint32_t))))
-        return rc;
-    ICNV_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
-    if ((rc = launch_rt_check(expr, G, cl.d_cidx.as<int32_t>(), cl.coff[n_prob], d_bad.as<uint32_t>(), s))) return rc;
-    ICNV_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    if (bad) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: NaN or infinite value among the clades' cells");
-    return ICNV_OK;
-}
-
-// Items (clade, iteration; -1 = the observed matrix) -> their rows after the stages: m gets the gathered (permuted) rows,
-// ld_m doubles apart; z (rows of G doubles) the smoothed and centred ones.
-int rt_stage(const double *expr, int32_t G, const RtClades &cl, uint64_t seed, int32_t window, const std::vector<int32_t> &clade,
-             const std::vector<int32_t> &iter, const std::vector<int64_t> &row, uint32_t stages, double *m, int64_t ld_m, double *z,
-             hipStream_t s) {
-    const int n_items = (int)clade.size();
-    const int64_t rows = row[n_items];
-    int rc;
-    DevBuf d_clade, d_iter, d_row;
-    if ((rc = upload(d_clade, clade.data(), clade.size(), s)) || (rc = upload(d_iter, iter.data(), iter.size(), s)) ||
-        (rc = upload(d_row, row.data(), row.size(), s)))
-        return rc;
-    RtItems a;
-    a.n_items = n_items; a.G = G; a.x = expr;
-    a.cell_idx = cl.d_cidx.as<int32_t>(); a.cell_off = cl.d_coff.as<int64_t>();
-    a.item_clade = d_clade.as<int32_t>(); a.item_iter = d_iter.as<int32_t>(); a.item_row = d_row.as<int64_t>();
-    a.token = cl.d_tok.as<uint64_t>(); a.seed = seed;
-    a.m = m; a.ld_m = ld_m; a.z = z; a.window = window;
-    if ((rc = launch_rt_permute(a, s))) return rc;
-    if (stages & ICNV_RT_SMOOTH) {
-        if ((rc = launch_rt_smooth(a, rows, s))) return rc;
-    } else {
-        ICNV_HIP(hipMemcpy2DAsync(z, (size_t)G * sizeof(double), m, (size_t)ld_m * sizeof(double), (size_t)G * sizeof(double),
-                                  (size_t)rows, hipMemcpyDeviceToDevice, s));
-    }
-    if (stages & ICNV_RT_CENTER) {   // step 11's own median centring (R/inferCNV_ops.R:2098)
-        LargeChainArgs c{};
-        c.out = z; c.G = G; c.n_rows = (int32_t)rows; c.mask = ICNV_ST_CENTER;
-        if ((rc = launch_chain_large_center(c, s))) return rc;
-    }
-    // the device buffers above are freed when this returns: the stream must be done with them
-    ICNV_HIP(hipStreamSynchronize(s));
-    return ICNV_OK;
-}
-}  // namespace
-
-int icnv_random_trees_dev(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, const int32_t *cell_off,
-                          const uint64_t *token, int32_t n_prob, int32_t window, int32_t n_iter, uint64_t seed, int32_t method,
-                          int32_t *merge, double *height, int32_t *order, double *rand_max_height, void *stream) {
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = rt_validate(expr, G, C, cell_idx, cell_off, n_prob, window);
-    if (rc) return rc;
-    if (!token || !merge || !height || !order || !rand_max_height) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: null argument");
-    if (n_iter < 1) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: n_iter must be >= 1");
-    if ((int64_t)n_prob * (n_iter + 1) > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "random_trees: too many matrices");
-    if ((rc = hclust_method_check(method))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    RtClades cl;
-    if ((rc = rt_upload_clades(expr, (int32_t)G, cell_idx, cell_off, token, n_prob, s, cl))) return rc;
-
-    // waves: the distance matrices of a wave within half the cap (at least one), its matrices built in sub-waves within the other
-    // half; every item is computed on its own, so no cap and no batch composition changes a bit
-    const int64_t cap = std::max<int64_t>(1, env_int("ICNV_RT_SCRATCH_MB", 8192)) * ((int64_t)1 << 20);
-    const int64_t ld = G + (G & 1);
-    auto d_bytes = [&](int64_t n) { return n * n * 8 + n * 24 + 64; };
-    auto m_bytes = [&](int64_t n) { return n * (ld + G) * 8 + G * 12 + n * 16 + 64; };
-    const int64_t total_cells = cl.coff[n_prob], total_merges = total_cells - n_prob;
-    std::vector<int32_t> hm(2 * total_merges), ho(total_cells);
-    std::vector<double> hh(total_merges);
-    const int64_t n_items = (int64_t)n_prob * (n_iter + 1);   // item q: clade q / (n_iter + 1), iteration q % (n_iter + 1) - 1
-    auto item_n = [&](int64_t q) { const int64_t p = q / (n_iter + 1); return cl.coff[p + 1] - cl.coff[p]; };
-    const bool root = method == ICNV_HCLUST_WARD_D2;
-    int64_t waves = 0, steps = 0;
-    for (int64_t q0 = 0; q0 < n_items;) {
-        int64_t q1 = q0, used = 0;
-        while (q1 < n_items && (q1 == q0 || (used + d_bytes(item_n(q1)) <= cap / 2 && q1 - q0 < 65535))) used += d_bytes(item_n(q1++));
-        const int nw = (int)(q1 - q0);
-        std::vector<int32_t> n(nw);
-        std::vector<int64_t> c_off(nw + 1), d_off(nw + 1);
-        c_off[0] = d_off[0] = 0;
-        for (int i = 0; i < nw; ++i) {
-            n[i] = (int32_t)item_n(q0 + i);
-            c_off[i + 1] = c_off[i] + n[i];
-            d_off[i + 1] = d_off[i] + (int64_t)n[i] * n[i];
-        }
-        DevBuf d_D;
-        if ((rc = d_D.alloc((size_t)d_off[nw] * sizeof(double)))) return rc;
-        for (int i0 = 0; i0 < nw;) {   // sub-waves: matrices -> R's sequential dist into D (distance_kernels.hip)
-            int i1 = i0;
-            int64_t mused = 0;
-            while (i1 < nw && (i1 == i0 || mused + m_bytes(n[i1]) <= cap / 2)) mused += m_bytes(n[i1++]);
-            const int ns = i1 - i0;
-            std::vector<int32_t> clade(ns), iter(ns), ids;
-            std::vector<int64_t> row(ns + 1), doff(ns + 1), toff;
-            row[0] = 0;
-            for (int i = 0; i < ns; ++i) {
-                const int64_t q = q0 + i0 + i;
-                clade[i] = (int32_t)(q / (n_iter + 1));
-                iter[i] = (int32_t)(q % (n_iter + 1)) - 1;
-                row[i + 1] = row[i] + n[i0 + i];
-                doff[i] = d_off[i0 + i] - d_off[i0];
-            }
-            const int64_t rows = row[ns];
-            if (rows > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "random_trees: sub-wave too large");
-            ids.resize(rows);
-            std::iota(ids.begin(), ids.end(), 0);
-            const int dt = exact_dist_plan(n.data() + i0, ns, toff);
-            if (toff[ns] > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "random_trees: sub-wave too large");
-            DevBuf d_m, d_z, d_ids, d_row, d_toff, d_n, d_doff;
-            if ((rc = d_m.alloc((size_t)rows * ld * sizeof(double))) || (rc = d_z.alloc((size_t)rows * G * sizeof(double))))
-                return rc;
-            if ((rc = rt_stage(expr, (int32_t)G, cl, seed, window, clade, iter, row, ICNV_RT_PERMUTE | ICNV_RT_SMOOTH | ICNV_RT_CENTER,
-                               d_m.as<double>(), ld, d_z.as<double>(), s)))
-                return rc;
-            if ((rc = upload(d_ids, ids.data(), ids.size(), s)) || (rc = upload(d_row, row.data(), row.size(), s)) ||
-                (rc = upload(d_toff, toff.data(), toff.size(), s)) || (rc = upload(d_n, n.data() + i0, (size_t)ns, s)) ||
-                (rc = upload(d_doff, doff.data(), doff.size(), s)))
-                return rc;
-            DistArgs da{};   // the staged cells: row r of the sub-wave at d_z + r G, every gene in order
-            da.x = d_z.as<double>(); da.ldx = G; da.G = (int32_t)G;
-            da.cell_idx = d_ids.as<int32_t>(); da.cell_off = d_row.as<int64_t>(); da.n = d_n.as<int32_t>();
-            da.n_prob = ns; da.tile_off = d_toff.as<int64_t>(); da.d_off = d_doff.as<int64_t>(); da.D = d_D.as<double>() + d_off[i0];
-            if ((rc = launch_exact_dist(da, dt, toff[ns], s))) return rc;
-            ICNV_HIP(hipStreamSynchronize(s));   // (the sub-wave's buffers go back to the pool here)
-            i0 = i1;
-        }
-        HclustRaw raw;
-        if ((rc = hclust_raw(d_D.as<double>(), n, c_off, method, s, raw))) return rc;
-        d_D.release();
-        // observed trees: labelled as R does (K9); permuted trees: only their maximum height, on the device
-        std::vector<int64_t> pm_off, p_out;
-        std::vector<int32_t> p_n;
-        std::vector<int> obs;
-        for (int i = 0; i < nw; ++i) {
-            const int64_t q = q0 + i;
-            const int64_t p = q / (n_iter + 1), r = q % (n_iter + 1) - 1;
-            if (r < 0) {
-                obs.push_back(i);
-            } else {
-                pm_off.push_back(raw.m_off[i]);
-                p_n.push_back(n[i]);
-                p_out.push_back(p * n_iter + r);
-            }
-        }
-        if (!p_n.empty()) {
-            DevBuf d_pm, d_pn, d_po;
-            if ((rc = upload(d_pm, pm_off.data(), pm_off.size(), s)) || (rc = upload(d_pn, p_n.data(), p_n.size(), s)) ||
-                (rc = upload(d_po, p_out.data(), p_out.size(), s)))
-                return rc;
-            if ((rc = launch_rt_max_height(raw.d_mh.as<double>(), d_pm.as<int64_t>(), d_pn.as<int32_t>(), d_po.as<int64_t>(),
-                                           (int32_t)p_n.size(), root, rand_max_height, s)))
-                return rc;
-            ICNV_HIP(hipStreamSynchronize(s));
-        }
-        if (!obs.empty()) {
-            std::vector<std::vector<int32_t>> mx(obs.size()), my(obs.size());
-            std::vector<std::vector<double>> mh(obs.size());
-            for (size_t k = 0; k < obs.size(); ++k) {
-                const int i = obs[k];
-                const size_t nm = (size_t)n[i] - 1;
-                mx[k].resize(nm); my[k].resize(nm); mh[k].resize(nm);
-                ICNV_HIP(hipMemcpyAsync(mx[k].data(), raw.d_mx.as<int32_t>() + raw.m_off[i], nm * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                ICNV_HIP(hipMemcpyAsync(my[k].data(), raw.d_my.as<int32_t>() + raw.m_off[i], nm * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                ICNV_HIP(hipMemcpyAsync(mh[k].data(), raw.d_mh.as<double>() + raw.m_off[i], nm * sizeof(double), hipMemcpyDeviceToHost, s));
-            }
-            ICNV_HIP(hipStreamSynchronize(s));
-            for (size_t k = 0; k < obs.size(); ++k) {
-                const int64_t p = (q0 + obs[k]) / (n_iter + 1), m0 = cl.coff[p] - p;
-                hclust_label(n[obs[k]], mx[k].data(), my[k].data(), mh[k].data(), root, hm.data() + 2 * m0, hh.data() + m0,
-                             ho.data() + cl.coff[p]);
-            }
-        }
-        steps += raw.steps;
-        ++waves;
-        q0 = q1;
-    }
-    ICNV_HIP(hipMemcpyAsync(merge, hm.data(), hm.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    ICNV_HIP(hipMemcpyAsync(height, hh.data(), hh.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    ICNV_HIP(hipMemcpyAsync(order, ho.data(), ho.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    g_rt[0] += 1;
-    g_rt[1] += n_prob;
-    g_rt[2] += (int64_t)n_prob * n_iter;
-    g_rt[3] += waves;
-    g_rt[4] += steps;
-    g_rt[5] += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-    return ICNV_OK;
-}
-
-int icnv_random_trees(const double *expr, int64_t G, int64_t C, const int32_t *cell_idx, const int32_t *cell_off,
-                      const uint64_t *token, int32_t n_prob, int32_t window, int32_t n_iter, uint64_t seed, int32_t method,
-                      int32_t *merge, double *height, int32_t *order, double *rand_max_height) {
-    int rc = rt_validate(expr, G, C, cell_idx, cell_off, n_prob, window);
-    if (rc) return rc;
-    if (!token || !merge || !height || !order || !rand_max_height) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: null argument");
-    if (n_iter < 1) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: n_iter must be >= 1");
-    if ((rc = hclust_method_check(method))) return rc;
-    const size_t cells = (size_t)cell_off[n_prob], merges = cells - (size_t)n_prob, nr = (size_t)n_prob * n_iter;
-    MatrixLease in;
-    DevBuf d_merge, d_height, d_order, d_rand;
-    if ((rc = acquire_input(expr, G * C, nullptr, in)) || (rc = d_merge.alloc(2 * merges * sizeof(int32_t))) ||
-        (rc = d_height.alloc(merges * sizeof(double))) || (rc = d_order.alloc(cells * sizeof(int32_t))) ||
-        (rc = d_rand.alloc(nr * sizeof(double))))
-        return rc;
-    if ((rc = icnv_random_trees_dev(in.dev, G, C, cell_idx, cell_off, token, n_prob, window, n_iter, seed, method,
-                                    d_merge.as<int32_t>(), d_height.as<double>(), d_order.as<int32_t>(), d_rand.as<double>(), nullptr)))
-        return rc;
-    ICNV_HIP(hipMemcpy(merge, d_merge.p, 2 * merges * sizeof(int32_t), hipMemcpyDeviceToHost));
-    ICNV_HIP(hipMemcpy(height, d_height.p, merges * sizeof(double), hipMemcpyDeviceToHost));
-    ICNV_HIP(hipMemcpy(order, d_order.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
-    ICNV_HIP(hipMemcpy(rand_max_height, d_rand.p, nr * sizeof(double), hipMemcpyDeviceToHost));
-    return ICNV_OK;
-}
-
-int icnv_random_trees_matrix_dev(const double *expr, int64_t G, int64_t C, const int32_t *cells, int32_t n, int32_t window,
-                                 uint64_t seed, uint64_t token, int32_t iter, uint32_t stages, double *out, void *stream) {
-    const int32_t off[2] = {0, n};
-    int rc = rt_validate(expr, G, C, cells, off, 1, window);
-    if (rc) return rc;
-    if (!out) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: null argument");
-    if (iter < -1) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: iter must be >= -1");
-    if (stages & ~(uint32_t)(ICNV_RT_PERMUTE | ICNV_RT_SMOOTH | ICNV_RT_CENTER)) ICNV_FAIL(ICNV_ERR_ARG, "random_trees: unknown stage bits");
-    hipStream_t s = (hipStream_t)stream;
-    RtClades cl;
-    if ((rc = rt_upload_clades(expr, (int32_t)G, cells, off, &token, 1, s, cl))) return rc;
-    const int64_t ld = G + (G & 1);
-    DevBuf d_m;
-    if ((rc = d_m.alloc((size_t)n * ld * sizeof(double)))) return rc;
-    const int32_t it = (stages & ICNV_RT_PERMUTE) ? iter : -1;
-    return rt_stage(expr, (int32_t)G, cl, seed, window, {0}, {it}, {0, n}, stages, d_m.as<double>(), ld, out, s);
-}
-
-int icnv_random_trees_stats(int64_t *out, int32_t n) {
-    if (!out || n < 1) ICNV_FAIL(ICNV_ERR_ARG, "bad argument");
-    for (int i = 0; i < n && i < 6; ++i) out[i] = g_rt[i].load();
-    return ICNV_OK;
-}
-
-void icnv_random_trees_stats_reset(void) {
-    for (auto &c : g_rt) c.store(0);
-}
-
-// ---- Leiden community detection (K11): cluster_leiden of .leiden_simple_snn (R/inferCNV_tumor_subclusters.R:726-741)
-namespace {
-std::atomic<int64_t> g_ld[7];   // calls, problems, levels, move visits, refinement visits, draws, wall microseconds
-
-// every host check before any device work (R/inferCNV_tumor_subclusters.R:726: nn2's k = k_nn <= ncol)
-int leiden_validate(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob) {
-    if (!nn_idx || !node_off) ICNV_FAIL(ICNV_ERR_ARG, "leiden: null argument");
-    if (n_prob < 1) ICNV_FAIL(ICNV_ERR_ARG, "leiden: n_prob must be >= 1");
-    if (k < 1) ICNV_FAIL(ICNV_ERR_ARG, "leiden: k must be >= 1");
-    if (node_off[0] != 0) ICNV_FAIL(ICNV_ERR_ARG, "leiden: offsets must start at 0");
-    for (int32_t p = 0; p < n_prob; ++p) {
-        if (node_off[p + 1] < node_off[p]) ICNV_FAIL(ICNV_ERR_ARG, "leiden: offsets must be monotone");
-        if (k > node_off[p + 1] - node_off[p]) ICNV_FAIL(ICNV_ERR_ARG, "leiden: k exceeds the nodes of problem " + std::to_string(p));
-    }
-    if (k > LEIDEN_MAX_K) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "leiden: k > 128 is not supported");
-    if ((int64_t)node_off[n_prob] * 2 * k > ((int64_t)1 << 31) - 1)
-        ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "leiden: batch too large (2 k sum n_p must stay below 2^31)");
-    return ICNV_OK;
-}
-
-int leiden_validate_run(int32_t n_prob, int32_t objective, const double *resolution, double beta, int32_t n_iterations,
-                        const void *membership, const void *n_clusters) {
-    if (!resolution || !membership || !n_clusters) ICNV_FAIL(ICNV_ERR_ARG, "leiden: null argument");
-    if (objective != ICNV_LEIDEN_CPM && objective != ICNV_LEIDEN_MODULARITY) ICNV_FAIL(ICNV_ERR_ARG, "leiden: unknown objective");
-    for (int32_t p = 0; p < n_prob; ++p)
-        if (!std::isfinite(resolution[p]) || resolution[p] < 0) ICNV_FAIL(ICNV_ERR_ARG, "leiden: resolution must be finite and >= 0");
-    if (!std::isfinite(beta) || !(beta > 0)) ICNV_FAIL(ICNV_ERR_ARG, "leiden: beta must be finite and > 0");
-    if (n_iterations < 1 || n_iterations > LEIDEN_MAX_ITERATIONS) ICNV_FAIL(ICNV_ERR_ARG, "leiden: n_iterations must be in [1, 1000]");
-    return ICNV_OK;
-}
-
-// the graphs of a batch on the device (after the device check of nn_idx): g's arrays live in the buffers
-struct LeidenGraphBufs {
-    DevBuf d_off, d_noff, d_col, d_strength, d_ssum, d_raw, d_raw_off, d_cnt, d_loop, d_bad;
-    std::vector<int64_t> noff;
-    LeidenGraph g{};
-};
-
-int leiden_build_graph(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, hipStream_t s, LeidenGraphBufs &b) {
-    int rc;
-    b.noff.assign(node_off, node_off + n_prob + 1);
-    const int64_t tn = b.noff[n_prob], E = 2 * (int64_t)k * tn, to = tn + n_prob;
-    if ((rc = upload(b.d_noff, b.noff.data(), b.noff.size(), s)) || (rc = b.d_off.alloc((size_t)to * 8)) ||
-        (rc = b.d_col.alloc((size_t)std::max<int64_t>(E, 1) * 4)) || (rc = b.d_strength.alloc((size_t)tn * 8)) ||
-        (rc = b.d_ssum.alloc((size_t)n_prob * 8)) || (rc = b.d_raw.alloc((size_t)std::max<int64_t>(E, 1) * 4)) ||
-        (rc = b.d_raw_off.alloc((size_t)to * 8)) || (rc = b.d_cnt.alloc((size_t)tn * 4)) || (rc = b.d_loop.alloc((size_t)tn * 4)) ||
-        (rc = b.d_bad.alloc(sizeof(uint32_t))))
-        return rc;
-    LeidenGraph &g = b.g;
-    g.nn = nn_idx; g.k = k; g.n_prob = n_prob; g.node_off = b.d_noff.as<int64_t>();
-    g.off = b.d_off.as<int64_t>(); g.col = b.d_col.as<int32_t>(); g.strength = b.d_strength.as<int64_t>();
-    g.strength_sum = b.d_ssum.as<int64_t>(); g.raw = b.d_raw.as<int32_t>(); g.raw_off = b.d_raw_off.as<int64_t>();
-    g.cnt = b.d_cnt.as<int32_t>(); g.loop = b.d_loop.as<int32_t>(); g.bad = b.d_bad.as<uint32_t>();
-    uint32_t bad = 0;
-    ICNV_HIP(hipMemsetAsync(b.d_bad.p, 0, sizeof(uint32_t), s));
-    if ((rc = launch_leiden_check(g, s))) return rc;
-    ICNV_HIP(hipMemcpyAsync(&bad, b.d_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    if (bad) ICNV_FAIL(ICNV_ERR_ARG, "leiden: nn_idx entry outside [0, n_p)");
-    return launch_leiden_graph(g, s);
-}
-}  // namespace
-
-int icnv_snn_graph_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, int64_t *row_off,
-                       int32_t *col, int64_t *strength, void *stream) {
-    int rc = leiden_validate(nn_idx, k, node_off, n_prob);
-    if (rc) return rc;
-    if (!row_off || !col || !strength) ICNV_FAIL(ICNV_ERR_ARG, "leiden: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    LeidenGraphBufs b;
-    if ((rc = leiden_build_graph(nn_idx, k, node_off, n_prob, s, b))) return rc;
-    const int64_t tn = b.noff[n_prob];
-    std::vector<int64_t> off(tn + n_prob), out(tn + 1);
-    ICNV_HIP(hipMemcpyAsync(off.data(), b.d_off.p, off.size() * 8, hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    int64_t base = 0;
-    for (int32_t p = 0; p < n_prob; ++p) {   // problem p's rows after the ones before it
-        const int64_t n0 = b.noff[p], n = b.noff[p + 1] - n0;
-        for (int64_t i = 0; i <= n; ++i) out[n0 + i] = base + off[n0 + p + i];
-        const int64_t nnz = off[n0 + p + n];
-        if (nnz) ICNV_HIP(hipMemcpyAsync(col + base, b.d_col.as<int32_t>() + 2 * (int64_t)k * n0, (size_t)nnz * 4, hipMemcpyDeviceToDevice, s));
-        base += nnz;
-    }
-    ICNV_HIP(hipMemcpyAsync(row_off, out.data(), out.size() * 8, hipMemcpyHostToDevice, s));
-    ICNV_HIP(hipMemcpyAsync(strength, b.d_strength.p, (size_t)tn * 8, hipMemcpyDeviceToDevice, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    return ICNV_OK;
-}
-
-// the Leiden run of a batch whose graphs are on the device: g (CSR, strengths), the problems' edge regions (edge_off null:
-// 2 k node_off[p], icnv_leiden_dev's), the level-0 edge weights (ew0 null: 1) and E, the entries of all regions together
-static int leiden_run(const LeidenGraph &g, const std::vector<int64_t> &noff, const int64_t *edge_off, const int64_t *ew0, int64_t E,
-                      int32_t n_prob, int32_t objective, const double *resolution, double beta, int32_t n_iterations, uint64_t seed,
-                      const uint64_t *token, int32_t *membership, int32_t *n_clusters, hipStream_t s,
-                      std::chrono::steady_clock::time_point t0) {
-    int rc;
-    const int64_t tn = noff[n_prob], to = tn + n_prob;
-    std::vector<int64_t> ssum(n_prob);
-    ICNV_HIP(hipMemcpyAsync(ssum.data(), g.strength_sum, ssum.size() * 8, hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    std::vector<double> r(n_prob);
-    for (int32_t p = 0; p < n_prob; ++p)   // R's wrapper: resolution_parameter / sum(strength) for modularity
-        r[p] = objective == ICNV_LEIDEN_MODULARITY ? resolution[p] / (double)ssum[p] : resolution[p];
-    std::vector<uint64_t> tok(n_prob, 0);
-    if (token) tok.assign(token, token + n_prob);
-    DevBuf d_r, d_tok, d_i64, d_offs, d_i32, d_cum, d_nbr, d_ew, d_memb, d_ncl, d_status, d_cnt;
-    if ((rc = upload(d_r, r.data(), r.size(), s)) || (rc = upload(d_tok, tok.data(), tok.size(), s)) ||
-        (rc = d_i64.alloc((size_t)LEIDEN_I64_ARRAYS * tn * 8)) || (rc = d_offs.alloc((size_t)2 * to * 8)) ||
-        (rc = d_i32.alloc((size_t)LEIDEN_I32_ARRAYS * to * 4)) || (rc = d_cum.alloc((size_t)tn * 8)) ||
-        (rc = d_nbr.alloc((size_t)std::max<int64_t>(2 * E, 1) * 4)) || (rc = d_ew.alloc((size_t)std::max<int64_t>(2 * E, 1) * 8)) ||
-        (rc = d_memb.alloc((size_t)tn * 4)) || (rc = d_ncl.alloc((size_t)n_prob * 4)) || (rc = d_status.alloc((size_t)n_prob * 4)) ||
-        (rc = d_cnt.alloc((size_t)n_prob * LEIDEN_CNT_N * 8)))
-        return rc;
-    LeidenArgs a;
-    a.g = g; a.edge_off = edge_off; a.ew0 = ew0; a.total_e = E; a.objective = objective; a.r = d_r.as<double>(); a.beta = beta; a.n_iterations = n_iterations; a.seed = seed;
-    a.token = d_tok.as<uint64_t>(); a.i64 = d_i64.as<int64_t>(); a.offs = d_offs.as<int64_t>(); a.i32 = d_i32.as<int32_t>();
-    a.cum = d_cum.as<double>(); a.nbr = d_nbr.as<int32_t>(); a.ew = d_ew.as<int64_t>(); a.total_n = tn;
-    a.membership = d_memb.as<int32_t>(); a.n_clusters = d_ncl.as<int32_t>(); a.status = d_status.as<int32_t>();
-    a.counters = d_cnt.as<int64_t>();
-    if ((rc = launch_leiden(a, s))) return rc;
-    std::vector<int32_t> status(n_prob), ncl(n_prob);
-    std::vector<int64_t> cnt((size_t)n_prob * LEIDEN_CNT_N);
-    ICNV_HIP(hipMemcpyAsync(status.data(), d_status.p, status.size() * 4, hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipMemcpyAsync(ncl.data(), d_ncl.p, ncl.size() * 4, hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipMemcpyAsync(cnt.data(), d_cnt.p, cnt.size() * 8, hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    for (int32_t p = 0; p < n_prob; ++p) {
-        if (status[p] == LEIDEN_MOVE_CAP)
-            ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "leiden: problem " + std::to_string(p) + " exceeded the queue pops of a move phase (256 n + 1024)");
-        if (status[p] == LEIDEN_LEVEL_CAP)
-            ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "leiden: problem " + std::to_string(p) + " exceeded 512 levels in one iteration");
-        if (status[p] != LEIDEN_OK) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "leiden: internal error in problem " + std::to_string(p));
-    }
-    ICNV_HIP(hipMemcpyAsync(membership, d_memb.p, (size_t)tn * 4, hipMemcpyDeviceToDevice, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    std::copy(ncl.begin(), ncl.end(), n_clusters);
-    g_ld[0] += 1;
-    g_ld[1] += n_prob;
-    for (int32_t p = 0; p < n_prob; ++p)
-        for (int c = 0; c < LEIDEN_CNT_N; ++c) g_ld[2 + c] += cnt[(size_t)p * LEIDEN_CNT_N + c];
-    g_ld[6] += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-    return ICNV_OK;
-}
-
-
-int icnv_leiden_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, int32_t objective,
-                    const double *resolution, double beta, int32_t n_iterations, uint64_t seed, const uint64_t *token,
-                    int32_t *membership, int32_t *n_clusters, void *stream) {
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = leiden_validate(nn_idx, k, node_off, n_prob);
-    if (rc || (rc = leiden_validate_run(n_prob, objective, resolution, beta, n_iterations, membership, n_clusters))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    LeidenGraphBufs b;
-    if ((rc = leiden_build_graph(nn_idx, k, node_off, n_prob, s, b))) return rc;
-    const int64_t tn = b.noff[n_prob];
-    return leiden_run(b.g, b.noff, nullptr, nullptr, 2 * (int64_t)k * tn, n_prob, objective, resolution, beta, n_iterations, seed, token,
-                      membership, n_clusters, s, t0);
-}
-
-int icnv_leiden_graph_dev(const int64_t *row_off, const int32_t *col, const int64_t *weight, const int32_t *loop, int64_t loop_weight,
-                          const int32_t *node_off, int32_t n_prob, int32_t objective, const double *resolution, double beta,
-                          int32_t n_iterations, uint64_t seed, const uint64_t *token, int32_t *membership, int32_t *n_clusters,
-                          void *stream) {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!row_off || !col || !weight || !loop || !node_off) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: null argument");
-    if (n_prob < 1) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: n_prob must be >= 1");
-    if (loop_weight < 1 || loop_weight > ((int64_t)1 << 53)) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: loop_weight must be in [1, 2^53]");
-    if (node_off[0] != 0) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: offsets must start at 0");
-    for (int32_t p = 0; p < n_prob; ++p)
-        if (node_off[p + 1] <= node_off[p]) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: problem " + std::to_string(p) + " has no node");
-    int rc = leiden_validate_run(n_prob, objective, resolution, beta, n_iterations, membership, n_clusters);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t tn = node_off[n_prob], to = tn + n_prob;
-    std::vector<int64_t> roff((size_t)tn + 1), noff(node_off, node_off + n_prob + 1), off((size_t)to), eoff((size_t)n_prob + 1);
-    ICNV_HIP(hipMemcpyAsync(roff.data(), row_off, roff.size() * 8, hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    if (roff[0] != 0) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: row_off must start at 0");
-    for (int64_t i = 0; i < tn; ++i)
-        if (roff[i + 1] < roff[i]) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: row_off must be monotone");
-    const int64_t E = roff[tn];
-    if (E > ((int64_t)1 << 31) - 1) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "leiden_graph: batch too large (the entries must stay below 2^31)");
-    for (int32_t p = 0; p < n_prob; ++p) {   // problem p's offsets within its own edge region, n_p + 1 of them
-        const int64_t n0 = noff[p], n = noff[p + 1] - n0;
-        eoff[p] = roff[n0];
-        for (int64_t i = 0; i <= n; ++i) off[n0 + p + i] = roff[n0 + i] - roff[n0];
-    }
-    eoff[n_prob] = E;
-    DevBuf d_noff, d_off, d_eoff, d_strength, d_ssum, d_bad;
-    if ((rc = upload(d_noff, noff.data(), noff.size(), s)) || (rc = upload(d_off, off.data(), off.size(), s)) ||
-        (rc = upload(d_eoff, eoff.data(), eoff.size(), s)) || (rc = d_strength.alloc((size_t)tn * 8)) ||
-        (rc = d_ssum.alloc((size_t)n_prob * 8)) || (rc = d_bad.alloc(sizeof(uint32_t))))
-        return rc;
-    LgCheck c{};
-    c.node_off = d_noff.as<int64_t>(); c.row_off = row_off; c.col = col; c.loop = loop; c.weight = weight; c.loop_weight = loop_weight;
-    c.n_prob = n_prob; c.off = d_off.as<int64_t>(); c.edge_off = d_eoff.as<int64_t>(); c.strength = d_strength.as<int64_t>();
-    c.strength_sum = d_ssum.as<int64_t>(); c.bad = d_bad.as<uint32_t>();
-    uint32_t bad = 0;
-    std::vector<int64_t> ssum(n_prob);
-    ICNV_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
-    if ((rc = launch_lg_check(c, s))) return rc;
-    ICNV_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipMemcpyAsync(ssum.data(), d_ssum.p, ssum.size() * 8, hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    if (bad) ICNV_FAIL(ICNV_ERR_ARG, "leiden_graph: a row is not ascending within [0, n_p) without its own node, a weight is < 1, or a loop flag is not 0 / 1");
-    for (int32_t p = 0; p < n_prob; ++p)   // the int64 -> double conversions of the gain must be exact
-        if (ssum[p] / 2 >= ((int64_t)1 << 53))
-            ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "leiden_graph: the total edge weight of problem " + std::to_string(p) + " reaches 2^53");
-    LeidenGraph g{};
-    g.k = 0; g.n_prob = n_prob; g.node_off = d_noff.as<int64_t>(); g.off = d_off.as<int64_t>(); g.col = const_cast<int32_t *>(col);
-    g.strength = d_strength.as<int64_t>(); g.strength_sum = d_ssum.as<int64_t>();
-    return leiden_run(g, noff, d_eoff.as<int64_t>(), weight, E, n_prob, objective, resolution, beta, n_iterations, seed, token, membership,
-                      n_clusters, s, t0);
-}
-
-int icnv_leiden(const int32_t *nn_idx, int32_t k, const int32_t *node_off, int32_t n_prob, int32_t objective,
-                const double *resolution, double beta, int32_t n_iterations, uint64_t seed, const uint64_t *token,
-                int32_t *membership, int32_t *n_clusters) {
-    int rc = leiden_validate(nn_idx, k, node_off, n_prob);
-    if (rc || (rc = leiden_validate_run(n_prob, objective, resolution, beta, n_iterations, membership, n_clusters))) return rc;
-    const size_t tn = (size_t)node_off[n_prob];
-    DevBuf d_nn, d_memb;
-    if ((rc = upload(d_nn, nn_idx, tn * k, nullptr)) || (rc = d_memb.alloc(tn * 4))) return rc;
-    std::vector<int32_t> ncl(n_prob);
-    if ((rc = icnv_leiden_dev(d_nn.as<int32_t>(), k, node_off, n_prob, objective, resolution, beta, n_iterations, seed, token,
-                              d_memb.as<int32_t>(), ncl.data(), nullptr)))
-        return rc;
-    ICNV_HIP(hipMemcpy(membership, d_memb.p, tn * 4, hipMemcpyDeviceToHost));
-    std::copy(ncl.begin(), ncl.end(), n_clusters);
-    return ICNV_OK;
-}
-
-int icnv_leiden_stats(int64_t *out, int32_t n) {
-    if (!out || n < 1) ICNV_FAIL(ICNV_ERR_ARG, "bad argument");
-    for (int i = 0; i < n && i < 7; ++i) out[i] = g_ld[i].load();
-    return ICNV_OK;
-}
-
-void icnv_leiden_stats_reset(void) {
-    for (auto &c : g_ld) c.store(0);
 }
 
 int icnv_viterbi_groups_dev(const double *expr, uint8_t *states, int64_t G, int64_t C, const int32_t *chr_start,

@@ -17,14 +17,6 @@ namespace {
 
 std::atomic<int64_t> g_bayes[8];   // sample calls, regions, cells, undecided cells, LDS regions, streamed regions, sample us, loglik us
 
-template <typename T>
-int up(DevBuf &b, const T *host, size_t n, hipStream_t s) {
-    int rc = b.alloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (rc) return rc;
-    if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return ICNV_OK;
-}
-
 int check_offsets(const char *who, const int64_t *cell_off, int32_t n_regions, int32_t K) {
     if (n_regions < 1) ICNV_FAIL(ICNV_ERR_ARG, std::string(who) + ": n_regions must be >= 1");
     if (K < 2) ICNV_FAIL(ICNV_ERR_ARG, std::string(who) + ": K must be >= 2");
@@ -93,8 +85,8 @@ int icnv_bayes_loglik_dev(const double *expr, int64_t G, int64_t C, int64_t ld, 
     std::vector<double> mt((size_t)2 * K);
     for (int32_t k = 0; k < K; ++k) { mt[k] = mu[k]; mt[K + k] = tau[k]; }
     DevBuf d_regs, d_tile, d_cidx, d_mt;
-    if ((rc = up(d_regs, regs.data(), regs.size(), s)) || (rc = up(d_tile, tile_off.data(), tile_off.size(), s)) ||
-        (rc = up(d_cidx, cell_idx, (size_t)cell_off[n_regions], s)) || (rc = up(d_mt, mt.data(), mt.size(), s)))
+    if ((rc = upload(d_regs, regs.data(), regs.size(), s)) || (rc = upload(d_tile, tile_off.data(), tile_off.size(), s)) ||
+        (rc = upload(d_cidx, cell_idx, (size_t)cell_off[n_regions], s)) || (rc = upload(d_mt, mt.data(), mt.size(), s)))
         return rc;
     BayesLoglik a{};
     a.x = expr; a.ld = ld; a.cell_idx = d_cidx.as<int32_t>(); a.regions = d_regs.as<BayesRegion>(); a.tile_off = d_tile.as<int64_t>();
@@ -138,7 +130,7 @@ int icnv_bayes_sample_dev(const double *L, const int64_t *cell_off, const uint64
     for (int32_t r = 0; r < n_regions; ++r)
         regs[r] = BayesRegion{cell_off[r], (int32_t)(cell_off[r + 1] - cell_off[r]), 0, 0, 0, token[r]};
     DevBuf d_regs, d_und, d_nund, d_nfix;
-    if ((rc = up(d_regs, regs.data(), regs.size(), s)) || (rc = d_und.alloc((size_t)std::max<int64_t>(rows, 1) * sizeof(int32_t))) ||
+    if ((rc = upload(d_regs, regs.data(), regs.size(), s)) || (rc = d_und.alloc((size_t)std::max<int64_t>(rows, 1) * sizeof(int32_t))) ||
         (rc = d_nund.alloc((size_t)n_regions * sizeof(int32_t))) || (rc = d_nfix.alloc((size_t)n_regions * BAYES_MAX_K * sizeof(int32_t))))
         return rc;
     if (rows) ICNV_HIP(hipMemsetAsync(freq, 0, (size_t)rows * K * sizeof(int32_t), s));
@@ -162,7 +154,7 @@ int icnv_bayes_sample_dev(const double *L, const int64_t *cell_off, const uint64
     for (int q = 0; q < 2; ++q) {
         if (list[q].empty()) continue;
         if ((int64_t)list[q].size() * K > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "bayes_sample: too many regions");
-        if ((rc = up(d_list[q], list[q].data(), list[q].size(), s))) return rc;
+        if ((rc = upload(d_list[q], list[q].data(), list[q].size(), s))) return rc;
         BayesSample a{};
         a.L = L; a.regions = d_regs.as<BayesRegion>(); a.list = d_list[q].as<int32_t>(); a.n_list = (int32_t)list[q].size(); a.K = K;
         a.n_discard = n_adapt + n_burn; a.n_keep = n_keep; a.seed = seed; a.und = d_und.as<int32_t>(); a.n_und = d_nund.as<int32_t>();
@@ -187,7 +179,7 @@ int icnv_bayes_sample(const double *L, const int64_t *cell_off, const uint64_t *
     const size_t rows = (size_t)cell_off[n_regions];
     const size_t n_sum = (size_t)n_regions * K * K, n_samp = n_sum * (size_t)n_keep;
     DevBuf d_L, d_sum, d_samp, d_freq;
-    if ((rc = up(d_L, L, rows * K, nullptr)) || (rc = d_sum.alloc(n_sum * sizeof(double))) ||
+    if ((rc = upload(d_L, L, rows * K, nullptr)) || (rc = d_sum.alloc(n_sum * sizeof(double))) ||
         (rc = d_freq.alloc(std::max<size_t>(rows * K, 1) * sizeof(int32_t))))
         return rc;
     if (theta_samples && (rc = d_samp.alloc(n_samp * sizeof(double)))) return rc;

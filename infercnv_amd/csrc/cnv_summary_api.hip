@@ -10,14 +10,6 @@ using namespace icnv;
 
 namespace {
 
-template <typename T>
-int up(DevBuf &b, const T *host, size_t n, hipStream_t s) {
-    int rc = b.alloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (rc) return rc;
-    if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return ICNV_OK;
-}
-
 int check_matrix(const char *who, const void *states, int64_t G, int64_t C, int64_t ld, const int32_t *chr_start, int32_t n_chr) {
     const std::string w(who);
     if (!states || !chr_start) ICNV_FAIL(ICNV_ERR_ARG, w + ": null argument");
@@ -52,7 +44,7 @@ int icnv_cnv_features_dev(const uint8_t *states, int64_t G, int64_t C, int64_t l
     if (C == 0) return ICNV_OK;
     hipStream_t s = (hipStream_t)stream;
     DevBuf d_cs, d_bad, d_rc;
-    if ((rc = up(d_cs, chr_start, (size_t)n_chr + 1, s)) || (rc = d_bad.alloc(sizeof(int32_t)))) return rc;
+    if ((rc = upload(d_cs, chr_start, (size_t)n_chr + 1, s)) || (rc = d_bad.alloc(sizeof(int32_t)))) return rc;
     if (!run_counts) {
         if ((rc = d_rc.alloc((size_t)C * 2 * sizeof(int32_t)))) return rc;
         run_counts = d_rc.as<int32_t>();
@@ -97,10 +89,10 @@ int icnv_cnv_runs_dev(const uint8_t *states, int64_t G, int64_t C, int64_t ld, c
     if (C == 0 || n_cols == 0) return ICNV_OK;
     hipStream_t s = (hipStream_t)stream;
     DevBuf d_cs, d_bad, d_rc, d_idx, d_off, d_tot;
-    if ((rc = up(d_cs, chr_start, (size_t)n_chr + 1, s)) || (rc = d_bad.alloc(sizeof(int32_t))) ||
+    if ((rc = upload(d_cs, chr_start, (size_t)n_chr + 1, s)) || (rc = d_bad.alloc(sizeof(int32_t))) ||
         (rc = d_off.alloc((size_t)n_cols * 2 * sizeof(int64_t))) || (rc = d_tot.alloc(2 * sizeof(int64_t))))
         return rc;
-    if (col_idx && (rc = up(d_idx, col_idx, (size_t)n_cols, s))) return rc;
+    if (col_idx && (rc = upload(d_idx, col_idx, (size_t)n_cols, s))) return rc;
     if (!run_counts) {
         if ((rc = d_rc.alloc((size_t)C * 2 * sizeof(int32_t)))) return rc;
         run_counts = d_rc.as<int32_t>();

@@ -18,14 +18,6 @@ namespace {
 
 std::atomic<int64_t> g_de[7];   // calls, comparisons, genes, LDS segments, HBM segments, waves, wall microseconds
 
-template <typename T>
-int up(DevBuf &b, const T *host, size_t n, hipStream_t s) {
-    int rc = b.alloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (rc) return rc;
-    if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return ICNV_OK;
-}
-
 // the exact two-sided p-values of every (n.x, n.y) <= 49: built once on the host, one device copy per device
 struct ExactDev { double *p = nullptr; int64_t *off = nullptr; };
 std::mutex g_exact_mu;
@@ -78,7 +70,7 @@ int sort_segments(double *keys, double *other, const DeSegs &g, hipStream_t s, d
     int rc;
     DevBuf d_seg, d_off;
     const int64_t chunks[2] = {0, (int64_t)g.count * (((int64_t)g.n + DE_CHUNK - 1) / DE_CHUNK)};
-    if ((rc = up(d_seg, &g, 1, s)) || (rc = up(d_off, chunks, 2, s))) return rc;
+    if ((rc = upload(d_seg, &g, 1, s)) || (rc = upload(d_off, chunks, 2, s))) return rc;
     if ((rc = launch_de_sort_chunks(keys, d_seg.as<DeSegs>(), d_off.as<int64_t>(), 1, chunks[1], s))) return rc;
     double *src = keys, *dst = other;
     for (int64_t run = DE_CHUNK; run < g.n; run *= 2) {
@@ -118,8 +110,8 @@ int icnv_de_tests_dev(const double *expr, int64_t G, int64_t C, int64_t ld, cons
         coff[q + 1] = coff[q] + nk[q];
     }
     DevBuf d_cidx, d_coff, d_cmp;
-    if ((rc = up(d_cidx, cidx.data(), cidx.size(), s)) || (rc = up(d_coff, coff.data(), coff.size(), s)) ||
-        (rc = up(d_cmp, cmp2.data(), cmp2.size(), s)))
+    if ((rc = upload(d_cidx, cidx.data(), cidx.size(), s)) || (rc = upload(d_coff, coff.data(), coff.size(), s)) ||
+        (rc = upload(d_cmp, cmp2.data(), cmp2.size(), s)))
         return rc;
 
     int64_t n_lds = 0, n_hbm = 0, waves = 0;
@@ -140,7 +132,7 @@ int icnv_de_tests_dev(const double *expr, int64_t G, int64_t C, int64_t ld, cons
         DevBuf d_a, d_b, d_err, d_n, d_which;
         if ((rc = d_a.alloc((size_t)std::max<int64_t>(coff[ng], 1) * gw_max * sizeof(double))) ||
             (rc = d_b.alloc((size_t)std::max<int64_t>(coff[ng], 1) * gw_max * sizeof(double))) || (rc = d_err.alloc(sizeof(uint64_t))) ||
-            (rc = up(d_n, nk.data(), nk.size(), s)))
+            (rc = upload(d_n, nk.data(), nk.size(), s)))
             return rc;
         ICNV_HIP(hipMemsetAsync(d_err.p, 0xff, sizeof(uint64_t), s));
         for (int32_t q = 0; q < ng; ++q) (nk[q] <= DE_CHUNK ? n_lds : n_hbm) += G;
@@ -158,8 +150,8 @@ int icnv_de_tests_dev(const double *expr, int64_t G, int64_t C, int64_t ld, cons
             if (tile_off[ng] > 0x7fffffff || chunk_off[ng] > 0x7fffffff || (coff[ng] * gw + 255) / 256 > 0x7fffffff)
                 ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "de_tests: wave too large (lower ICNV_DE_SCRATCH_MB)");
             DevBuf d_base, d_tile, d_chunk, d_segs;
-            if ((rc = up(d_base, seg_base.data(), seg_base.size(), s)) || (rc = up(d_tile, tile_off.data(), tile_off.size(), s)) ||
-                (rc = up(d_chunk, chunk_off.data(), chunk_off.size(), s)) || (rc = up(d_segs, segs.data(), segs.size(), s)))
+            if ((rc = upload(d_base, seg_base.data(), seg_base.size(), s)) || (rc = upload(d_tile, tile_off.data(), tile_off.size(), s)) ||
+                (rc = upload(d_chunk, chunk_off.data(), chunk_off.size(), s)) || (rc = upload(d_segs, segs.data(), segs.size(), s)))
                 return rc;
             DeGather ga{};
             ga.x = expr; ga.ld = ld; ga.cell_idx = d_cidx.as<int32_t>(); ga.cell_off = d_coff.as<int64_t>();
@@ -175,7 +167,7 @@ int icnv_de_tests_dev(const double *expr, int64_t G, int64_t C, int64_t ld, cons
                     which[q] ^= 1;
                 }
             }
-            if ((rc = up(d_which, which.data(), which.size(), s))) return rc;
+            if ((rc = upload(d_which, which.data(), which.size(), s))) return rc;
             DeWilcox wa{};
             wa.buf[0] = d_a.as<double>(); wa.buf[1] = d_b.as<double>();
             wa.seg_base = d_base.as<int64_t>(); wa.n = d_n.as<int32_t>(); wa.which = d_which.as<int8_t>(); wa.cmp = d_cmp.as<int32_t>();
@@ -258,7 +250,7 @@ int icnv_mask_non_de_dev(const double *expr, int64_t G, int64_t C, int64_t ld, c
     hipStream_t s = (hipStream_t)stream;
     int rc;
     DevBuf d_base, d_off, d_idx, d_part, d_mean;
-    if ((rc = up(d_base, base, (size_t)C, s)) || (rc = up(d_off, cc_off, (size_t)C + 1, s)) || (rc = up(d_idx, cc_idx, (size_t)cc_off[C], s)) ||
+    if ((rc = upload(d_base, base, (size_t)C, s)) || (rc = upload(d_off, cc_off, (size_t)C + 1, s)) || (rc = upload(d_idx, cc_idx, (size_t)cc_off[C], s)) ||
         (rc = d_mean.alloc(sizeof(double))))
         return rc;
     if (use_mean) {
@@ -289,7 +281,7 @@ int icnv_mask_non_de(const double *expr, int64_t G, int64_t C, const double *pad
     MatrixLease in;
     DevBuf d_padj, d_out;
     const size_t n = (size_t)G * C;
-    if ((rc = acquire_input(expr, G * C, nullptr, in)) || (rc = up(d_padj, padj, (size_t)n_cmp * G, nullptr)) ||
+    if ((rc = acquire_input(expr, G * C, nullptr, in)) || (rc = upload(d_padj, padj, (size_t)n_cmp * G, nullptr)) ||
         (rc = d_out.alloc(n * sizeof(double))))
         return rc;
     if ((rc = icnv_mask_non_de_dev(in.dev, G, C, G, d_padj.as<double>(), n_cmp, p_val_thresh, base, cc_off, cc_idx, n_normal, rule,

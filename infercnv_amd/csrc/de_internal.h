@@ -1,4 +1,4 @@
-// Shared between api.hip (validation, wave planning, exact tables, stats) and de_kernels.hip (K12, the per-gene rank-sum and
+// Shared between de_api.hip (validation, wave planning, exact tables, stats) and de_kernels.hip (K12, the per-gene rank-sum and
 // Welch tests of mask_non_DE_genes_basic).  DESIGN.md section 4 K12.
 #pragma once
 #include <hip/hip_runtime.h>

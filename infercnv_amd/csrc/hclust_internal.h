@@ -1,8 +1,12 @@
-// Shared between api.hip (validation, planning, R labelling, stats) and hclust_kernels.hip (K9, the nearest-neighbour
-// chain of hclust).  DESIGN.md section 4 K9.
+// Shared between hclust_api.hip (validation, planning, R labelling, stats), hclust_kernels.hip (K9, the nearest-neighbour
+// chain of hclust) and random_trees_api.hip (K10 clusters its trees with K9's host helpers).  DESIGN.md section 4 K9.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <vector>
+
+#include "icnv_internal.h"
 
 namespace icnv {
 
@@ -32,5 +36,19 @@ struct HclustArgs {           // one launch; every pointer is device memory
 int launch_hclust_prep(double *D, int64_t total, bool square, uint32_t *bad, hipStream_t s);
 int launch_hclust_lds(const HclustArgs &a, int max_n, hipStream_t s);
 int launch_hclust_hbm(const HclustArgs &a, int max_n, hipStream_t s);
+
+// ---- host helpers of hclust_api.hip that K10 (random_trees_api.hip) calls too ----
+// The raw merges of a batch of problems, left on the device (K9's chain; K10 keeps only the maximum of most trees).
+struct HclustRaw {
+    DevBuf d_n, d_moff, d_mx, d_my, d_mh;   // per problem: cells, first raw merge; the raw merges in chain order
+    std::vector<int64_t> m_off;
+    int n_lds = 0, n_hbm = 0;
+    int64_t steps = 0;
+};
+int hclust_method_check(int32_t method);
+void hclust_label(int n, const int32_t *rx, const int32_t *ry, const double *rh, bool root, int32_t *merge, double *height,
+                  int32_t *order);
+int hclust_raw(double *D, const std::vector<int32_t> &n, const std::vector<int64_t> &c_off, int32_t method, hipStream_t s,
+               HclustRaw &out);
 
 }  // namespace icnv

@@ -10,7 +10,7 @@
 //                       row mirrored into its column), the active bitmask in LDS
 //
 // Both chain kernels run the same nn_chain() with the same operation order and tie rule, so they agree bit for bit.
-// The raw merges (chain order) go back to api.hip, which sorts and labels them as R does.
+// The raw merges (chain order) go back to hclust_api.hip, which sorts and labels them as R does.
 // This file is compiled with -ffp-contract=off (Makefile): the Lance-Williams updates must not become FMAs.
 #include "icnv_internal.h"
 #include "hclust_internal.h"

@@ -64,14 +64,6 @@ struct HmRank {
     int64_t cnt;        // kept values with this prefix
 };
 
-template <typename T>
-int hm_up(DevBuf &b, const T *host, size_t n, hipStream_t s) {
-    int rc = b.alloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (rc) return rc;
-    ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return ICNV_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -213,7 +205,7 @@ int icnv_heatmap_bins_dev(const double *x, int64_t ld, int64_t G, int64_t C, con
         return rc;
     hipStream_t s = (hipStream_t)stream;
     DevBuf d_rows, d_br, d_out;
-    if ((rc = hm_up(d_rows, rows, (size_t)n_rows, s)) || (rc = hm_up(d_br, breaks, (size_t)nb, s)) ||
+    if ((rc = upload(d_rows, rows, (size_t)n_rows, s)) || (rc = upload(d_br, breaks, (size_t)nb, s)) ||
         (rc = d_out.alloc((HM_MAX_BREAKS + 1) * sizeof(uint64_t))))
         return rc;
     ICNV_HIP(hipMemsetAsync(d_out.p, 0, (HM_MAX_BREAKS + 1) * sizeof(uint64_t), s));
@@ -252,7 +244,7 @@ int icnv_heatmap_raster_dev(const double *x, int64_t ld, int64_t G, int64_t C, c
         return rc;
     hipStream_t s = (hipStream_t)stream;
     DevBuf d_rows, d_br, d_img, d_flag;   // rendered aside: a NaN found by the kernel must leave `image` as it was
-    if ((rc = hm_up(d_rows, order, (size_t)n, s)) || (rc = hm_up(d_br, breaks, (size_t)nb, s)) ||
+    if ((rc = upload(d_rows, order, (size_t)n, s)) || (rc = upload(d_br, breaks, (size_t)nb, s)) ||
         (rc = d_img.alloc((size_t)H * (size_t)W)) || (rc = d_flag.alloc(sizeof(uint32_t))))
         return rc;
     ICNV_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(uint32_t), s));

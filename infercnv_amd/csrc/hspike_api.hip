@@ -13,14 +13,6 @@ using namespace icnv;
 
 namespace {
 
-template <typename T>
-int up(DevBuf &b, const T *host, size_t n, hipStream_t s) {
-    int rc = b.alloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (rc) return rc;
-    if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return ICNV_OK;
-}
-
 int tables_validate(const void *expr, int64_t G, int64_t C, int64_t ld, const int32_t *cell_idx, const int32_t *cell_off,
                     int32_t n_grp, const void *m, const void *v, const void *nzero) {
     if (!expr || !cell_idx || !cell_off || !m || !v || !nzero) ICNV_FAIL(ICNV_ERR_ARG, "group_gene_tables: null argument");
@@ -68,8 +60,8 @@ int icnv_group_gene_tables_dev(const double *expr, int64_t G, int64_t C, int64_t
     const int64_t n_chunks = (int64_t)chunks.size(), tiles = (G + 255) / 256;
     if (tiles > 65535 || tiles * n_chunks > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "group_gene_tables: too many (gene tile, cell chunk) pairs");
     DevBuf d_idx, d_chunks, d_choff, d_coff, d_part, d_nz;
-    if ((rc = up(d_idx, cell_idx, (size_t)cell_off[n_grp], s)) || (rc = up(d_chunks, chunks.data(), chunks.size(), s)) ||
-        (rc = up(d_choff, chunk_off.data(), chunk_off.size(), s)) || (rc = up(d_coff, coff.data(), coff.size(), s)) ||
+    if ((rc = upload(d_idx, cell_idx, (size_t)cell_off[n_grp], s)) || (rc = upload(d_chunks, chunks.data(), chunks.size(), s)) ||
+        (rc = upload(d_choff, chunk_off.data(), chunk_off.size(), s)) || (rc = upload(d_coff, coff.data(), coff.size(), s)) ||
         (rc = d_part.alloc((size_t)n_chunks * 3 * G * sizeof(double))) || (rc = d_nz.alloc((size_t)n_chunks * G * sizeof(int32_t))))
         return rc;
     HsTables a{};
@@ -120,8 +112,8 @@ int icnv_hspike_simulate_dev(const double *means, int64_t n_genes, int32_t num_c
     }
     hipStream_t s = (hipStream_t)stream;
     DevBuf d_means, d_tok, d_vk, d_vc, d_pk, d_pc;
-    if ((rc = up(d_means, means, n_means, s)) || (rc = up(d_tok, tokens, (size_t)n_mat, s)) || (rc = up(d_vk, var_knots, (size_t)var_nk + 4, s)) ||
-        (rc = up(d_vc, var_coef, (size_t)var_nk, s)) || (rc = up(d_pk, p0_knots, (size_t)p0_nk + 4, s)) || (rc = up(d_pc, p0_coef, (size_t)p0_nk, s)))
+    if ((rc = upload(d_means, means, n_means, s)) || (rc = upload(d_tok, tokens, (size_t)n_mat, s)) || (rc = upload(d_vk, var_knots, (size_t)var_nk + 4, s)) ||
+        (rc = upload(d_vc, var_coef, (size_t)var_nk, s)) || (rc = upload(d_pk, p0_knots, (size_t)p0_nk + 4, s)) || (rc = upload(d_pc, p0_coef, (size_t)p0_nk, s)))
         return rc;
     HsSim a{};
     a.means = d_means.as<double>(); a.tokens = d_tok.as<uint64_t>(); a.n_genes = (int32_t)n_genes; a.num_cells = num_cells; a.n_mat = n_mat;

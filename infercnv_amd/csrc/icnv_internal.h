@@ -1,6 +1,8 @@
 // Internal declarations shared by the HIP translation units of libicnv_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdlib>
 #include <vector>
 #include <stdint.h>
 
@@ -42,6 +44,18 @@ struct DevBuf {  // RAII over the pool
     void release() { pool_free(p); p = nullptr; }
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
+// n elements of host memory into a pool buffer on `s` (never an empty allocation; nothing is copied when n == 0)
+template <typename T>
+inline int upload(DevBuf &b, const T *host, size_t n, hipStream_t s) {
+    int rc = b.alloc(std::max<size_t>(n, 1) * sizeof(T));
+    if (rc) return rc;
+    if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
+    return ICNV_OK;
+}
+inline int64_t env_int(const char *name, int64_t dflt) {   // an integer tuning knob of the environment (ICNV_*_SCRATCH_MB, ...)
+    const char *e = std::getenv(name);
+    return (e && *e) ? std::atoll(e) : dflt;
+}
 
 // Host-buffer path (host_path.hip): a device copy of a host matrix, either recognised as resident (icnv_residency) or
 // uploaded on `s`; and the registration of a freshly downloaded result.

@@ -1,4 +1,4 @@
-// Shared between api.hip (planning, validation, stats) and knn_kernels.hip (K8, the exact kNN).  DESIGN.md section 4 K8.
+// Shared between knn_api.hip (planning, validation, stats) and knn_kernels.hip (K8, the exact kNN).  DESIGN.md section 4 K8.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
-// Shared between api.hip (validation, scratch, stats) and leiden_kernels.hip (K11, the Leiden community detection of the
-// Leiden subclustering).  DESIGN.md section 4 K11.
+// Shared between leiden_api.hip (validation, scratch, stats) and leiden_kernels.hip (K11, the Leiden community detection of
+// the Leiden subclustering).  DESIGN.md section 4 K11.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -1,5 +1,5 @@
 // C ABI of K18 (include/icnv.h "PCA route of the Leiden subclustering"): validation, the problems' descriptors and the
-// scratch of the SNN graph.  Kernels: leiden_pca_kernels.hip.  icnv_leiden_graph_dev lives in api.hip with K11's run.
+// scratch of the SNN graph.  Kernels: leiden_pca_kernels.hip.  icnv_leiden_graph_dev lives in leiden_api.hip with K11's run.
 // DESIGN.md section 4 K18.
 #include <algorithm>
 #include <cmath>
@@ -15,14 +15,6 @@
 using namespace icnv;
 
 namespace {
-
-template <typename T>
-int up(DevBuf &b, const T *host, size_t n, hipStream_t s) {
-    int rc = b.alloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (rc) return rc;
-    if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return ICNV_OK;
-}
 
 int lists_validate(const char *who, const int32_t *idx, const int32_t *off, int32_t n_prob, int64_t limit, const char *what) {
     const std::string w = std::string(who) + ": ";
@@ -110,8 +102,8 @@ int icnv_lpca_vstd_dev(const double *expr, int64_t G, int64_t C, int64_t ld, con
         q.cell_off = cell_off[p]; q.gene_off = gene_off[p]; q.n = cell_off[p + 1] - cell_off[p]; q.n_gene = gene_off[p + 1] - gene_off[p];
         b.max_genes = std::max(b.max_genes, q.n_gene);
     }
-    if ((rc = up(b.d_prob, b.prob.data(), b.prob.size(), s)) || (rc = up(b.d_gene, gene_idx, (size_t)gene_off[n_prob], s)) ||
-        (rc = up(b.d_cell, cell_idx, (size_t)cell_off[n_prob], s)))
+    if ((rc = upload(b.d_prob, b.prob.data(), b.prob.size(), s)) || (rc = upload(b.d_gene, gene_idx, (size_t)gene_off[n_prob], s)) ||
+        (rc = upload(b.d_cell, cell_idx, (size_t)cell_off[n_prob], s)))
         return rc;
     LpArgs a{};
     a.x = expr; a.ld = ld; a.cell_idx = b.d_cell.as<int32_t>(); a.gene_idx = b.d_gene.as<int32_t>(); a.prob = b.d_prob.as<LpProb>();
@@ -140,8 +132,8 @@ int icnv_lpca_scale_dev(const double *expr, int64_t G, int64_t C, int64_t ld, co
         b.max_genes = std::max(b.max_genes, q.n_gene); b.max_ldz = std::max(b.max_ldz, q.ldz);
     }
     if ((b.max_ldz + 31) / 32 > 65535) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "lpca_scale: more than 2 097 120 cells in one problem");
-    if ((rc = up(b.d_prob, b.prob.data(), b.prob.size(), s)) || (rc = up(b.d_gene, gene_idx, (size_t)gene_off[n_prob], s)) ||
-        (rc = up(b.d_cell, cell_idx, (size_t)cell_off[n_prob], s)))
+    if ((rc = upload(b.d_prob, b.prob.data(), b.prob.size(), s)) || (rc = upload(b.d_gene, gene_idx, (size_t)gene_off[n_prob], s)) ||
+        (rc = upload(b.d_cell, cell_idx, (size_t)cell_off[n_prob], s)))
         return rc;
     LpArgs a{};
     a.x = expr; a.ld = ld; a.cell_idx = b.d_cell.as<int32_t>(); a.gene_idx = b.d_gene.as<int32_t>(); a.prob = b.d_prob.as<LpProb>();
@@ -160,7 +152,7 @@ int icnv_lpca_gram_dev(const double *Z, const int32_t *n_feat, const int32_t *n_
     if (nt * nt > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "lpca_gram: too many features");
     if ((rc = need_device())) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = up(b.d_prob, b.prob.data(), b.prob.size(), s))) return rc;
+    if ((rc = upload(b.d_prob, b.prob.data(), b.prob.size(), s))) return rc;
     LpArgs a{};
     a.prob = b.d_prob.as<LpProb>(); a.n_prob = n_prob; a.Z = const_cast<double *>(Z); a.M = M;
     if ((rc = launch_lpca_gram(a, b.max_genes, s))) return rc;
@@ -183,7 +175,7 @@ int icnv_lpca_project_dev(const double *Z, const double *V, const int32_t *n_fea
     }
     if ((rc = need_device())) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = up(b.d_prob, b.prob.data(), b.prob.size(), s))) return rc;
+    if ((rc = upload(b.d_prob, b.prob.data(), b.prob.size(), s))) return rc;
     ICNV_HIP(hipMemsetAsync(E, 0, (size_t)tn * e_ld * sizeof(double), s));   // the components a problem does not have
     LpArgs a{};
     a.prob = b.d_prob.as<LpProb>(); a.n_prob = n_prob; a.Z = const_cast<double *>(Z); a.V = V; a.E = E; a.e_ld = e_ld;
@@ -215,7 +207,7 @@ int icnv_snn_begin_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off
     std::unique_ptr<icnv_snn> h(new icnv_snn);
     std::vector<int64_t> noff(node_off, node_off + n_prob + 1);
     const size_t scr = (size_t)n_prob * snn_blocks(max_n) * max_n;
-    if ((rc = up(h->d_noff, noff.data(), noff.size(), s)) || (rc = h->d_tcnt.alloc((size_t)tn * 4)) ||
+    if ((rc = upload(h->d_noff, noff.data(), noff.size(), s)) || (rc = h->d_tcnt.alloc((size_t)tn * 4)) ||
         (rc = h->d_toff.alloc((size_t)(tn + n_prob) * 8)) || (rc = h->d_tlist.alloc((size_t)tn * k * 4)) ||
         (rc = h->d_mark.alloc(scr * 4)) || (rc = h->d_touched.alloc(scr * 4)) || (rc = h->d_rowcnt.alloc((size_t)(tn + 1) * 4)) ||
         (rc = h->d_rowoff.alloc((size_t)(tn + 1) * 8)) || (rc = h->d_loop.alloc((size_t)tn * 4)) || (rc = h->d_bad.alloc(sizeof(uint32_t))))

@@ -1,5 +1,5 @@
-// Shared between api.hip (validation, wave planning, stats) and random_trees_kernels.hip (K10, the permutation statistic of
-// the random-trees subclustering).  DESIGN.md section 4 K10.
+// Shared between random_trees_api.hip (validation, wave planning, stats) and random_trees_kernels.hip (K10, the permutation
+// statistic of the random-trees subclustering).  DESIGN.md section 4 K10.
 #pragma once
 #include <stdint.h>
 

@@ -17,14 +17,6 @@ namespace {
 
 std::atomic<int64_t> g_sw[6];   // calls, LDS tiles, spilled tiles, weighted calls, window rows (sum of len), wall microseconds
 
-template <typename T>
-int up(DevBuf &b, const T *host, size_t n, hipStream_t s) {
-    int rc = b.alloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (rc) return rc;
-    if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return ICNV_OK;
-}
-
 // every check of the contract that needs no device work; `rows` receives the sum of len
 int sw_validate(const double *in, int64_t ld_in, const double *out, int64_t ld_out, int64_t G, int64_t C, const int32_t *lo,
                 const int32_t *len, const int64_t *w_off, const double *w, const double *denom, int64_t &rows) {
@@ -94,10 +86,10 @@ int icnv_smooth_windows_dev(const double *expr_in, int64_t ld_in, double *expr_o
     const int32_t n_lds = (int32_t)tiles.size(), n_spill = (int32_t)spill.size();
     tiles.insert(tiles.end(), spill.begin(), spill.end());
     DevBuf d_lo, d_len, d_off, d_w, d_den, d_tiles, d_flag;
-    if ((rc = up(d_lo, lo, (size_t)G, s)) || (rc = up(d_len, len, (size_t)G, s)) || (rc = up(d_den, denom, (size_t)G, s)) ||
-        (rc = up(d_tiles, tiles.data(), tiles.size(), s)) || (rc = d_flag.alloc(sizeof(uint32_t))))
+    if ((rc = upload(d_lo, lo, (size_t)G, s)) || (rc = upload(d_len, len, (size_t)G, s)) || (rc = upload(d_den, denom, (size_t)G, s)) ||
+        (rc = upload(d_tiles, tiles.data(), tiles.size(), s)) || (rc = d_flag.alloc(sizeof(uint32_t))))
         return rc;
-    if (w && ((rc = up(d_off, w_off, (size_t)G + 1, s)) || (rc = up(d_w, w, (size_t)w_off[G], s)))) return rc;
+    if (w && ((rc = upload(d_off, w_off, (size_t)G + 1, s)) || (rc = upload(d_w, w, (size_t)w_off[G], s)))) return rc;
     ICNV_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(uint32_t), s));
     SwArgs a{};
     a.x = expr_in; a.out = expr_out; a.ldx = ld_in; a.ldo = ld_out; a.C = C;

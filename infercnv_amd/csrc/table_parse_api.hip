@@ -30,14 +30,6 @@ int tp_validate(const void *text_dev, const uint8_t *text_host, int64_t n_bytes,
     return ICNV_OK;
 }
 
-template <typename T>
-int tp_up(DevBuf &b, const T *host, size_t n, hipStream_t s) {
-    int rc = b.alloc((n ? n : 1) * sizeof(T));
-    if (rc) return rc;
-    if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return ICNV_OK;
-}
-
 int tp_refused(const uint8_t *text_host, int64_t n, uint64_t word, uint8_t sep, int64_t line0, int64_t n_cols) {
     ICNV_FAIL(ICNV_ERR_ARG, "parse_table: " + tp_describe(text_host, n, (int64_t)(word >> 8), (int)(word & 0xff), sep, line0, n_cols));
 }
@@ -122,7 +114,7 @@ int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int6
         }
         if (worst != TP_NO_ERROR) return tp_refused(text_host, n_bytes, worst, a.sep, line0, n_cols);
         DevBuf d_slot, d_bits;
-        if ((rc = tp_up(d_slot, slot.data(), n, s)) || (rc = tp_up(d_bits, bits.data(), n, s)) ||
+        if ((rc = upload(d_slot, slot.data(), n, s)) || (rc = upload(d_bits, bits.data(), n, s)) ||
             (rc = launch_tp_patch(a, d_slot.as<int64_t>(), d_bits.as<uint64_t>(), (int32_t)n, s)))
             return rc;
         n_host += (int64_t)n;
@@ -196,8 +188,8 @@ int icnv_gather_matrix_dev(const double *in, int64_t ld_in, int64_t G_in, int64_
     hipStream_t s = (hipStream_t)stream;
     DevBuf d_genes, d_cells;
     int rc;
-    if (genes && (rc = tp_up(d_genes, genes, (size_t)n_genes, s))) return rc;
-    if (cells && (rc = tp_up(d_cells, cells, (size_t)n_cells, s))) return rc;
+    if (genes && (rc = upload(d_genes, genes, (size_t)n_genes, s))) return rc;
+    if (cells && (rc = upload(d_cells, cells, (size_t)n_cells, s))) return rc;
     if ((rc = launch_gather_matrix(in, ld_in, genes ? d_genes.as<int32_t>() : nullptr, n_genes, cells ? d_cells.as<int32_t>() : nullptr, n_cells,
                                    out, ld_out, s)))
         return rc;

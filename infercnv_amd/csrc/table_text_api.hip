@@ -50,14 +50,6 @@ int tt_validate(const double *x, int64_t ld, int64_t G, int64_t C, int32_t orien
     return ICNV_OK;
 }
 
-template <typename T>
-int tt_up(DevBuf &b, const T *host, size_t n, hipStream_t s) {
-    int rc = b.alloc((n ? n : 1) * sizeof(T));
-    if (rc) return rc;
-    if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return ICNV_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -91,13 +83,13 @@ int icnv_format_table_dev(const double *x, int64_t ld, int64_t G, int64_t C, int
     DevBuf d_cells, d_rec, d_meta, d_flag, d_seg_sum, d_seg_off, d_row_bytes, d_row_off, d_lab_off, d_lab;
     const int32_t *cell_src = orientation == TT_GENE_ROWS ? cells : cells + row0;
     const size_t n_cell_up = orientation == TT_GENE_ROWS ? (size_t)n_cells : (size_t)R;
-    if ((rc = tt_up(d_cells, cell_src, n_cell_up, s)) || (rc = d_rec.alloc((size_t)n_elem * sizeof(uint64_t))) ||
+    if ((rc = upload(d_cells, cell_src, n_cell_up, s)) || (rc = d_rec.alloc((size_t)n_elem * sizeof(uint64_t))) ||
         (rc = d_meta.alloc((size_t)n_elem * sizeof(uint16_t))) ||
         (rc = d_flag.alloc((size_t)TT_FLAG_CAP * sizeof(TtFlagged) + sizeof(uint64_t))) ||
         (rc = d_seg_sum.alloc((size_t)(R * a.n_seg) * sizeof(uint32_t))) || (rc = d_seg_off.alloc((size_t)(R * a.n_seg) * sizeof(int64_t))) ||
         (rc = d_row_bytes.alloc((size_t)R * sizeof(int64_t))) || (rc = d_row_off.alloc((size_t)(R + 1) * sizeof(int64_t))))
         return rc;
-    if (label_off && ((rc = tt_up(d_lab_off, label_off, (size_t)R + 1, s)) || (rc = tt_up(d_lab, labels, (size_t)label_off[R], s)))) return rc;
+    if (label_off && ((rc = upload(d_lab_off, label_off, (size_t)R + 1, s)) || (rc = upload(d_lab, labels, (size_t)label_off[R], s)))) return rc;
     a.cells = d_cells.as<int32_t>();
     a.rec = d_rec.as<uint64_t>(); a.meta = d_meta.as<uint16_t>();
     a.flagged = d_flag.as<TtFlagged>();
@@ -130,7 +122,7 @@ int icnv_format_table_dev(const double *x, int64_t ld, int64_t G, int64_t C, int
             tt_host_record(fl[i].bits, rec[i], meta[i]);
         }
         DevBuf d_idx, d_nrec, d_nmeta;
-        if ((rc = tt_up(d_idx, idx.data(), n, s)) || (rc = tt_up(d_nrec, rec.data(), n, s)) || (rc = tt_up(d_nmeta, meta.data(), n, s)) ||
+        if ((rc = upload(d_idx, idx.data(), n, s)) || (rc = upload(d_nrec, rec.data(), n, s)) || (rc = upload(d_nmeta, meta.data(), n, s)) ||
             (rc = launch_tt_patch(a, d_idx.as<int64_t>(), d_nrec.as<uint64_t>(), d_nmeta.as<uint16_t>(), (int32_t)n, s)))
             return rc;
         n_host += (int64_t)n;
