@@ -1211,6 +1211,72 @@ int icnv_csc_select_dev(const icnv_counts *cnt, int64_t G, int64_t C, const int3
                         const int32_t *cells_dev, int64_t n_cells, int64_t *colptr_out, int32_t *rowidx_out, int32_t *vals_out,
                         int64_t capacity, int64_t *nnz_out, void *stream);
 
+/* ---- CNV region reports (K24) -----------------------------------------------------------------------------------------------
+ * The bodies of `<prefix>.pred_cnv_genes.dat` and `<prefix>.pred_cnv_regions.dat`, which generate_cnv_region_reports writes
+ * with write.table(quote = FALSE, sep = "\t") (R/inferCNV_HMM.R:790-869).  The byte-level yardstick is the host writer kept in
+ * infercnv_amd/cnv_regions.py; DESIGN.md section 4 K24, restated in tests/cnv_reports_restate.py.  The header lines stay with
+ * the caller.  Not yet bound in the R shim.
+ *
+ * A plan describes one file.  icnv_cnv_report_begin[_dev] takes
+ *   records    the six int32 arrays of icnv_cnv_runs_dev, records[f * capacity + r] for r < n_records: f = 0 list position,
+ *              1 chromosome index, 2 first gene, 3 last gene (inclusive), 4 state, 5 ordinal.  They are already filtered by
+ *              `neutral` and ordered by (list position, gene).  DEVICE in the _dev flavour, where the plan keeps the pointer:
+ *              the arrays stay valid and unchanged until icnv_cnv_report_end.  HOST otherwise (the plan uploads a copy).
+ *   three string tables, HOST, each as bytes plus int64 offsets [n + 1] (entry i is bytes[off[i] .. off[i + 1]), copied as
+ *              bytes; bytes may be null when every entry is empty): the cell-group names by list position, the chromosome names
+ *              by chromosome index, the gene names in the gathered gene order of chr_layout() -- the order the records count in.
+ *   gene_start, gene_end   HOST int64 [G], in the same gathered order.
+ *   totals     HOST, nullable, 3 entries: bytes of the whole body, lines of the whole body, bytes of the largest record.
+ * begin uploads the tables once, computes the byte offset of every record and keeps it on both sides; it synchronises.
+ * n_records = 0 gives a valid plan of an empty body.  icnv_cnv_report_end frees the plan (null is fine).
+ *
+ * ICNV_REPORT_GENES: one line for every gene g in gene_first .. gene_last of every record, in record order, then gene order:
+ *   <group>\t<chr>-region_<ordinal>\t<state>\t<gene name g>\t<chr>\t<start[g]>\t<end[g]>\n
+ * ICNV_REPORT_REGIONS: one line per record:
+ *   <group>\t<chr>-region_<ordinal>\t<state>\t<chr>\t<min start over the run>\t<max end over the run>\n
+ * Integers are plain decimal, `-` in front of a negative one, no padding.  State 255 -- the library's invalid state -- is
+ * written as -1, every other state byte as its decimal value.  There is no limit on the length of a name or of a line.
+ *
+ * icnv_cnv_report_format[_dev] formats the records rec0 .. into `out` (capacity bytes; DEVICE in the _dev flavour, any
+ * alignment) and stops before the first record that does not fit: *recs_done records (>= 1) take *n_bytes bytes, record
+ * rec0 + i of them at rec_offsets[i] .. rec_offsets[i + 1] (HOST, nullable, room for n_records - rec0 + 1 entries; entries
+ * 0 .. *recs_done are written).  A caller streams a file in chunks of whole records by calling again with rec0 + *recs_done.
+ * Offsets within the file are int64 throughout.
+ * ICNV_ERR_ARG, before any launch: a null plan pointer, records, offsets, positions, out, recs_done or n_bytes; an unknown
+ *   kind; capacity (of the records) < n_records; a table of no entry; offsets that do not start at 0 or descend, or bytes
+ *   missing for them; a record whose list position, chromosome or gene range leaves its table, with gene_first > gene_last,
+ *   or with a state outside 0 .. 255 (the device records are copied to the host for this check); rec0 outside
+ *   0 .. n_records - 1; a capacity below the first record.  ICNV_ERR_UNSUPPORTED: a capacity above 2^31 - 1.
+ *   On an error the outputs are left as they were; `out` is written only by a call that succeeds, and never outside
+ *   out[0 .. *n_bytes).  The calls synchronise the stream.
+ * Method: no pass over the lines.  P = int64 prefix sum over the genes of len(name) + digits(start) + digits(end); the fixed
+ *   part of a record's lines is F = len(group) + 2 len(chr) + 8 + digits(ordinal) + len(state text) + 7; a GENES record of n
+ *   genes takes n F + P[last + 1] - P[first] bytes and its line i starts at i F + P[first + i] - P[first]; a REGIONS record
+ *   takes F - 1 + digits(min) + digits(max) after a min / max reduction over its genes.  One scan gives the record offsets.
+ *   The emit pass gives each workgroup 16 KiB of the output: it finds the lines that overlap them from the offsets, assembles
+ *   the bytes in LDS and stores aligned 16-byte words (the ragged ends of the chunk byte by byte).
+ *   Timer names: "cnv_report_prefix", "cnv_report_lengths", "cnv_report_scan", "cnv_report_emit". */
+#define ICNV_REPORT_GENES 0
+#define ICNV_REPORT_REGIONS 1
+typedef struct icnv_cnv_report icnv_cnv_report_t;
+int icnv_cnv_report_begin_dev(icnv_cnv_report_t **plan, int32_t kind, const int32_t *records, int64_t capacity, int64_t n_records,
+                              const uint8_t *group_bytes, const int64_t *group_off, int64_t n_groups, const uint8_t *chr_bytes,
+                              const int64_t *chr_off, int64_t n_chr, const uint8_t *gene_bytes, const int64_t *gene_off,
+                              const int64_t *gene_start, const int64_t *gene_end, int64_t G, int64_t *totals, void *stream);
+int icnv_cnv_report_begin(icnv_cnv_report_t **plan, int32_t kind, const int32_t *records, int64_t capacity, int64_t n_records,
+                          const uint8_t *group_bytes, const int64_t *group_off, int64_t n_groups, const uint8_t *chr_bytes,
+                          const int64_t *chr_off, int64_t n_chr, const uint8_t *gene_bytes, const int64_t *gene_off,
+                          const int64_t *gene_start, const int64_t *gene_end, int64_t G, int64_t *totals);
+int icnv_cnv_report_format_dev(icnv_cnv_report_t *plan, int64_t rec0, uint8_t *out, int64_t capacity, int64_t *rec_offsets,
+                               int64_t *recs_done, int64_t *n_bytes, void *stream);
+int icnv_cnv_report_format(icnv_cnv_report_t *plan, int64_t rec0, uint8_t *out, int64_t capacity, int64_t *rec_offsets, int64_t *recs_done,
+                           int64_t *n_bytes);
+void icnv_cnv_report_end(icnv_cnv_report_t *plan);
+/* Counters since the last reset, n = int64 slots (<= 5 written); a refused call counts nowhere:
+ *   out[0] format calls   out[1] records written   out[2] lines written   out[3] bytes written   out[4] wall microseconds */
+int icnv_cnv_report_stats(int64_t *out, int32_t n);
+void icnv_cnv_report_stats_reset(void);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

@@ -33,6 +33,7 @@ DE_WILCOXON, DE_T = 1, 2               # ICNV_DE_* tests of icnv_de_tests_dev
 DE_MASK_ANY, DE_MASK_MOST, DE_MASK_ALL = 0, 1, 2   # ICNV_DE_MASK_* rules of icnv_mask_non_de_dev
 DE_JITTER_TOKEN = 0x6E6F6E44456A6974   # ICNV_DE_JITTER_TOKEN: the jitter stream's second key word
 TABLE_GENE_ROWS, TABLE_CELL_ROWS = 0, 1   # ICNV_TABLE_* orientations of icnv_format_table_dev
+REPORT_GENES, REPORT_REGIONS = 0, 1       # ICNV_REPORT_* kinds of icnv_cnv_report_begin_dev
 MM_INTEGER, MM_REAL, MM_PATTERN = 0, 1, 2      # ICNV_MM_* fields of icnv_parse_triplets_dev
 CSC_SORTED, CSC_DUPLICATE, CSC_DESCENT = 0, 1, 2   # ICNV_CSC_* results of icnv_csc_from_sorted_triplets_dev
 HSPIKE_GENES_TOKEN = 0x6873706B67656E65   # ICNV_HSPIKE_GENES_TOKEN: the stream of the hidden spike-in's genes_means_use_idx
@@ -189,6 +190,15 @@ PROTOTYPES = {
     "icnv_format_table": (ct.c_int, [_vp, _i64, _i64, _i32, _i64, _i64, _ip, _i64, _vp, _i64p, ct.c_char_p, _vp, _i64, _i64p, _i64p, _i64p]),
     "icnv_table_text_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_table_text_stats_reset": (None, []),
+    "icnv_cnv_report_begin_dev": (ct.c_int, [ct.POINTER(_vp), _i32, _vp, _i64, _i64, _vp, _i64p, _i64, _vp, _i64p, _i64, _vp, _i64p, _i64p, _i64p,
+                                             _i64, _i64p, _vp]),
+    "icnv_cnv_report_begin": (ct.c_int, [ct.POINTER(_vp), _i32, _vp, _i64, _i64, _vp, _i64p, _i64, _vp, _i64p, _i64, _vp, _i64p, _i64p, _i64p, _i64,
+                                         _i64p]),
+    "icnv_cnv_report_format_dev": (ct.c_int, [_vp, _i64, _vp, _i64, _i64p, _i64p, _i64p, _vp]),
+    "icnv_cnv_report_format": (ct.c_int, [_vp, _i64, _vp, _i64, _i64p, _i64p, _i64p]),
+    "icnv_cnv_report_end": (None, [_vp]),
+    "icnv_cnv_report_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_cnv_report_stats_reset": (None, []),
     "icnv_parse_table_dev": (ct.c_int, [_vp, _vp, _i64, ct.c_char_p, _i64, _i64, _vp, _i64, _i64, _i64, _i64p, _i64p, _vp]),
     "icnv_parse_table": (ct.c_int, [_vp, _i64, ct.c_char_p, _i64, _i64, _vp, _i64, _i64, _i64, _i64p, _i64p]),
     "icnv_table_parse_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),

@@ -1,19 +1,35 @@
-"""CNV region / consensus reporting (second "next" row): host-side mirror of
-get_predicted_CNV_regions, .define_cnv_gene_regions, .get_cnv_gene_region_bounds and
-generate_cnv_region_reports (R/inferCNV_HMM.R:706-869, 1005-1087).  The per-gene consensus over a
-group's cells (.get_state_consensus, :977-987) and the run-length segmentation run on the GPU (icnv_state_consensus,
-icnv_cnv_runs); the four report files are written on the host, in the reference's formats.
+"""CNV region / consensus reporting (second "next" row): mirror of get_predicted_CNV_regions,
+.define_cnv_gene_regions, .get_cnv_gene_region_bounds and generate_cnv_region_reports (R/inferCNV_HMM.R:706-869, 1005-1087).
+The per-gene consensus over a group's cells (.get_state_consensus, :977-987) and the run-length segmentation run on the GPU
+(icnv_state_consensus, icnv_cnv_runs).
+
+generate_cnv_region_reports writes its two large files, <prefix>.pred_cnv_regions.dat and .pred_cnv_genes.dat, on the GPU
+(DESIGN K24): the state matrix goes to the device once, the run records stay there, and the text of the files is formatted
+from them by icnv_cnv_report_format_dev and streamed to disk in chunks of whole records (text_stream.stream_chunks).  The
+two small files, .cell_groupings and .genes_used.dat, are joined on the host and written at once.  The function returns a
+lazy sequence: a cell group's dict is built from the run records when somebody asks for it.  The earlier host writer is kept
+as _generate_cnv_region_reports_host: it is the byte-level yardstick of the device writer, and it still runs when the gene
+positions are not integers that int64 holds (the device prints integers only).
 """
 from __future__ import annotations
 
 import ctypes as ct
+import locale
+import logging
+import operator
 import os
+import time
+from collections.abc import Sequence
 
 import numpy as np
 
 from . import _lib
 from ._lib import check, i32, pack_groups
 from .infercnv_object import InfercnvObject
+
+log = logging.getLogger("infercnv_amd")
+REPORT_CHUNK = 256 << 20           # bytes of one chunk of the report bodies; ICNV_CNV_REPORT_CHUNK (developer switch) overrides it
+LAST_REPORT_STATS = {}             # seconds and counts of the last generate_cnv_region_reports (scripts/bench_cnv_reports.py)
 
 
 def _states_u8(obj):
@@ -183,10 +199,11 @@ def _fmt(v):
     return str(v)
 
 
-def generate_cnv_region_reports(infercnv_obj: InfercnvObject, output_filename_prefix, out_dir, ignore_neutral_state=None,
-                                by="consensus"):
-    """R/inferCNV_HMM.R:790-869: writes <prefix>.cell_groupings, .pred_cnv_regions.dat, .pred_cnv_genes.dat and
-    .genes_used.dat (tab separated, header row, no quotes, no row names except for genes_used)."""
+def _generate_cnv_region_reports_host(infercnv_obj: InfercnvObject, output_filename_prefix, out_dir, ignore_neutral_state=None,
+                                      by="consensus"):
+    """R/inferCNV_HMM.R:790-869 line by line on the host: writes <prefix>.cell_groupings, .pred_cnv_regions.dat,
+    .pred_cnv_genes.dat and .genes_used.dat (tab separated, header row, no quotes, no row names except for genes_used).
+    The yardstick of generate_cnv_region_reports, and its writer for gene positions that are not int64 integers."""
     cnv_regions = get_predicted_CNV_regions(infercnv_obj, by)
     os.makedirs(out_dir, exist_ok=True)
     genes = infercnv_obj.genes()
@@ -220,6 +237,184 @@ def generate_cnv_region_reports(infercnv_obj: InfercnvObject, output_filename_pr
         for i in range(n):
             fh.write(f"{genes[i]}\t{np.asarray(go.chr)[i]}\t{_fmt(st[i])}\t{_fmt(sp[i])}\n")
     return cnv_regions
+
+
+# ------------------------------------------------------------------ the reports on the device (DESIGN K24)
+REGIONS_HEADER = "cell_group_name\tcnv_name\tstate\tchr\tstart\tend\n"
+GENES_HEADER = "cell_group_name\tgene_region_name\tstate\tgene\tchr\tstart\tend\n"
+
+
+def _int64_positions(a):
+    """`a` as an int64 array when every element is an integer that int64 holds -- the numbers the device writer prints exactly
+    as _fmt does -- else None (the host writer runs)."""
+    a = np.asarray(a)
+    if a.dtype.kind == "i" or (a.dtype.kind == "u" and (a.size == 0 or int(a.max()) <= np.iinfo(np.int64).max)):
+        return a.astype(np.int64)
+    if a.dtype.kind == "f" and bool(np.all(np.isfinite(a))) and bool(np.all(a == np.floor(a))) and bool(np.all(np.abs(a) < 2.0 ** 63)):
+        return a.astype(np.int64)
+    return None
+
+
+def _neutral_byte(ignore_neutral_state):
+    """The `neutral` byte of icnv_cnv_runs that leaves out what `state != ignore_neutral_state` leaves out of the host writer's
+    files: 0 keeps every run, 255 is the invalid state (reported as -1).  None: a value the byte cannot express (0)."""
+    if ignore_neutral_state is None:
+        return 0
+    v = float(ignore_neutral_state)
+    if v == -1.0:
+        return 255
+    if v == 0.0:
+        return None
+    return int(v) if v.is_integer() and 1.0 <= v <= 254.0 else 0      # no state equals any other value: nothing is left out
+
+
+def _report_tables(group_names, chr_names, gene_names, enc):
+    """The three string tables of icnv_cnv_report_begin_dev as (uint8 bytes, int64 offsets) pairs."""
+    from .device import pack_labels
+    return tuple(pack_labels([str(n).encode(enc) for n in names]) for names in (group_names, chr_names, gene_names))
+
+
+def _int_len(v):
+    """Bytes of the decimal text of every element of an int64 array (`-` included)."""
+    v = np.asarray(v, dtype=np.int64)
+    mag = np.where(v < 0, -(v + 1), v).astype(np.uint64) + (v < 0).astype(np.uint64)
+    return np.searchsorted(10 ** np.arange(1, 19, dtype=np.uint64), mag, side="right") + 1 + (v < 0)
+
+
+def report_lengths(kind, rec, tables, start, end):
+    """The closed form of DESIGN K24 in NumPy, as the kernels compute it: (bytes of every record, F of every record, P).
+    rec: the six record arrays (col, chr, gene_first, gene_last, state with 255 for the invalid state, ordinal); tables:
+    _report_tables(); start, end: int64 in the records' gene order.  kind "genes": a record of n genes takes
+    n F + P[last + 1] - P[first] bytes, its line i starts at i F + P[first + i] - P[first]; "regions": F - 1 + digits(min
+    start) + digits(max end)."""
+    col, chr_i, first, last, state, ordinal = (np.asarray(r, dtype=np.int64) for r in rec)
+    (_, g_off), (_, c_off), (_, n_off) = tables
+    start, end = np.asarray(start, dtype=np.int64), np.asarray(end, dtype=np.int64)
+    P = np.concatenate([[0], np.cumsum(np.diff(n_off) + _int_len(start) + _int_len(end))]).astype(np.int64)
+    F = np.diff(g_off)[col] + 2 * np.diff(c_off)[chr_i] + 8 + _int_len(ordinal) + _int_len(np.where(state == 255, -1, state)) + 7
+    if kind == "genes":
+        return (last - first + 1) * F + P[last + 1] - P[first], F, P
+    lo, hi = _range_reduce(np.minimum, start, first, last), _range_reduce(np.maximum, end, first, last)
+    return F - 1 + _int_len(lo) + _int_len(hi), F, P
+
+
+class _RegionList(Sequence):
+    """What generate_cnv_region_reports returns: element i equals get_predicted_CNV_regions(...)[i] and is built from the run
+    records (every run, the neutral ones included) when it is asked for."""
+
+    def __init__(self, groups, cells, rec, chr_names, perm, start, stop):
+        self._groups, self._cells, self._chr_names, self._perm, self._start, self._stop = groups, cells, chr_names, perm, start, stop
+        self._col, self._chr, self._first, self._last, state, self._ordinal = (np.asarray(r).astype(np.int64) for r in rec)
+        self._state = np.where(state == 255, -1, state)
+        self._bounds = np.searchsorted(self._col, np.arange(len(groups) + 1))
+
+    def __len__(self):
+        return len(self._groups)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[k] for k in range(*i.indices(len(self)))]
+        i = operator.index(i)
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError("cell group index out of range")
+        name, idx = self._groups[i]
+        regions = []
+        for r in range(self._bounds[i], self._bounds[i + 1]):
+            rows = np.arange(self._first[r], self._last[r] + 1)
+            if self._perm is not None:
+                rows = self._perm[rows]
+            chr_name = self._chr_names[self._chr[r]]
+            regions.append((f"{chr_name}-region_{self._ordinal[r]}", {"state": float(self._state[r]), "gene": rows, "chr": chr_name,
+                                                                     "start": self._start[rows], "end": self._stop[rows]}))
+        ranges = [(rn, r["state"], r["chr"], r["start"].min(), r["end"].max()) for rn, r in regions]   # :1071-1087
+        return {"cell_group_name": name, "cells": self._cells[idx], "gene_regions": regions, "cnv_ranges": ranges}
+
+
+def generate_cnv_region_reports(infercnv_obj: InfercnvObject, output_filename_prefix, out_dir, ignore_neutral_state=None,
+                                by="consensus"):
+    """R/inferCNV_HMM.R:790-869: writes <prefix>.cell_groupings, .pred_cnv_regions.dat, .pred_cnv_genes.dat and
+    .genes_used.dat (tab separated, header row, no quotes, no row names except for genes_used), byte for byte the files of
+    _generate_cnv_region_reports_host.  The states go to the device once; group modes take the groups' consensus columns
+    (device.state_consensus), by = "cell" the cells' own columns in report order with every byte outside 1 .. 6 as the invalid
+    state; device.cnv_runs gives the run records and device.CnvReportPlan the text of the two .dat bodies, streamed in chunks
+    of whole records (DESIGN K24).  Returns a read-only sequence with one entry per cell group, equal to
+    get_predicted_CNV_regions(infercnv_obj, by) element by element; an entry is built when it is indexed."""
+    go = infercnv_obj.gene_order
+    n = np.asarray(go.chr).size
+    start = np.asarray(go.start) if go.start is not None else np.arange(n)
+    stop = np.asarray(go.stop) if go.stop is not None else np.arange(n)
+    start64, stop64, neutral = _int64_positions(start), _int64_positions(stop), _neutral_byte(ignore_neutral_state)
+    if start64 is None or stop64 is None or neutral is None:
+        log.info("generate_cnv_region_reports: gene positions that are not int64 integers, or ignore_neutral_state = 0: "
+                 "the host writer runs")
+        return _generate_cnv_region_reports_host(infercnv_obj, output_filename_prefix, out_dir, ignore_neutral_state, by)
+    import torch
+    from . import device
+    from .text_stream import stream_chunks
+    t0 = time.perf_counter()
+    enc = locale.getpreferredencoding(False)
+    groups = _cell_groups(infercnv_obj, by)
+    by_cell = by == "cell" and infercnv_obj.tumor_subclusters is not None
+    perm, chr_start = infercnv_obj.chr_layout()
+    chrs, genes, cells = np.asarray(go.chr), infercnv_obj.genes(), infercnv_obj.cells()
+    st = _states_u8(infercnv_obj)
+    g_chrs, g_genes, g_start, g_stop = chrs, genes, start64, stop64
+    if perm is not None:                                   # the kernels see contiguous chromosomes only
+        st, g_chrs, g_genes, g_start, g_stop = np.asfortranarray(st[perm]), chrs[perm], np.asarray(genes)[perm], start64[perm], stop64[perm]
+    chr_names = g_chrs[chr_start[:-1]]
+    if by_cell:
+        # what the consensus over one cell gave before: a byte outside 1 .. 6 is the invalid state (reported as -1)
+        st = np.asfortranarray(np.where((st >= 1) & (st <= 6), st, 255).astype(np.uint8))
+    stats = {"device_writer": True, "by": by}
+    G, C = st.shape
+    rec = rec_all = torch.zeros((6, 0), dtype=torch.int32, device="cuda")
+    if C and groups:
+        dev_states = torch.from_numpy(st.T).cuda()         # (C, G) rows = the columns of the (G, C) column-major matrix
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        if by_cell:
+            mat, col_idx = dev_states, np.concatenate([g for _, g in groups]).astype(np.int32)
+        else:
+            mat, col_idx = device.state_consensus(dev_states, [g for _, g in groups]), None
+        rec, _ = device.cnv_runs(mat, chr_start, neutral=neutral, K=0, col_idx=col_idx)
+        rec_all = rec if neutral == 0 else device.cnv_runs(mat, chr_start, neutral=0, K=0, col_idx=col_idx)[0]
+        del dev_states, mat
+    else:
+        t1 = time.perf_counter()
+    rec_host = rec_all.cpu().numpy()
+    stats["convert_upload_s"], stats["runs_s"] = t1 - t0, time.perf_counter() - t1
+
+    os.makedirs(out_dir, exist_ok=True)
+    path = lambda suffix: os.path.join(out_dir, output_filename_prefix + suffix)
+    with open(path(".cell_groupings"), "w") as fh:
+        fh.write("cell_group_name\tcell\n" + "".join(f"{name}\t{c}\n" for name, idx in groups for c in cells[idx]))
+    tables = _report_tables([name for name, _ in groups] or [""], chr_names, g_genes, enc)
+    chunk = int(os.environ.get("ICNV_CNV_REPORT_CHUNK", REPORT_CHUNK))
+    for kind, suffix, header in (("regions", ".pred_cnv_regions.dat", REGIONS_HEADER), ("genes", ".pred_cnv_genes.dat", GENES_HEADER)):
+        t2 = time.perf_counter()
+        with open(path(suffix), "wb") as fh, device.CnvReportPlan(kind, rec, *tables, g_start, g_stop) as plan:
+            fh.write(header.encode(enc))
+            state = {"next": 0}
+
+            def fill(buf):
+                if state["next"] >= plan.n_records:
+                    return None
+                done, nbytes, _ = plan.format_into(buf, state["next"])
+                state["next"] += done
+                return nbytes
+
+            if plan.n_records:
+                stats[kind] = stream_chunks(fh, max(plan.max_record_bytes, min(chunk, plan.total_bytes)), rec.device, fill)
+            stats[kind + "_lines"], stats[kind + "_s"] = plan.total_lines, time.perf_counter() - t2
+    t3 = time.perf_counter()
+    with open(path(".genes_used.dat"), "w") as fh:        # write.table(gene_order, quote=FALSE, sep="\t"): row names kept
+        fh.write("chr\tstart\tstop\n" + "".join(f"{g}\t{c}\t{a}\t{b}\n" for g, c, a, b in zip(genes, chrs, start64.tolist(), stop64.tolist())))
+    stats["genes_used_s"], stats["total_s"] = time.perf_counter() - t3, time.perf_counter() - t0
+    LAST_REPORT_STATS.clear()
+    LAST_REPORT_STATS.update(stats)
+    return _RegionList(groups, cells, rec_host, chr_names, perm, start, stop)
 
 
 def adjust_genes_regions_report(mcmc_obj, input_filename_prefix, output_filename_prefix, out_dir):

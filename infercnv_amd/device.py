@@ -293,6 +293,116 @@ def table_text_stats(reset=False):
     return dict(zip(TABLE_TEXT_STATS, (int(v) for v in out)))
 
 
+# ------------------------------------------------------------------ CNV region reports (DESIGN K24)
+REPORT_KINDS = {"genes": _lib.REPORT_GENES, "regions": _lib.REPORT_REGIONS}   # ICNV_REPORT_* of include/icnv.h
+CNV_REPORT_STATS = ("calls", "records", "lines", "bytes", "us")
+
+
+def _packed(table, name):
+    b, off = table
+    if not (isinstance(b, np.ndarray) and b.dtype == np.uint8 and b.flags.c_contiguous and isinstance(off, np.ndarray)
+            and off.dtype == np.int64 and off.flags.c_contiguous and off.size >= 1 and b.size >= int(off[-1])):
+        raise TypeError(f"{name} must be pack_labels() output: (uint8 bytes, int64 offsets)")
+    return b, off
+
+
+class CnvReportPlan:
+    """One report file of generate_cnv_region_reports on the device (icnv_cnv_report_begin_dev .. _end, DESIGN K24).
+    kind: "genes" (<prefix>.pred_cnv_genes.dat, a line per gene of every record) or "regions" (.pred_cnv_regions.dat, a line
+    per record).  records: the int32 (6, n) CUDA tensor cnv_runs() returned (rows may lie further apart than n); groups,
+    chrs, genes: pack_labels() of the cell-group names by list position, the chromosome names by chromosome index and the gene
+    names in the gene order the records count in; start, end: int64 numpy arrays in that order.  The tables go to the device
+    once; total_bytes, total_lines and max_record_bytes describe the whole body.  format_into() writes chunks of whole
+    records; close() (or the with statement) frees the plan."""
+
+    def __init__(self, kind, records, groups, chrs, genes, start, end):
+        L = _lib.load()
+        code = REPORT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.dtype == torch.int32 and records.dim() == 2
+                and records.shape[0] == 6 and (records.shape[1] <= 1 or records.stride(1) == 1)):
+            raise TypeError("records must be the int32 (6, n) CUDA tensor of cnv_runs()")
+        n = int(records.shape[1])
+        stride = int(records.stride(0))
+        if stride < n:
+            raise TypeError("the rows of records overlap")
+        self._tables = [_packed(groups, "groups"), _packed(chrs, "chrs"), _packed(genes, "genes")]
+        G = self._tables[2][1].size - 1
+        self._pos = [np.ascontiguousarray(start, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)]
+        if self._pos[0].shape != (G,) or self._pos[1].shape != (G,):
+            raise ValueError("one start and one end per gene name")
+        self._records = records                     # the plan reads them until close()
+        self.n_records = n
+        self._h = ct.c_void_p()
+        totals = (ct.c_int64 * 3)()
+        i64p = ct.POINTER(ct.c_int64)
+        tab = [x for b, off in self._tables for x in (ct.c_void_p(b.ctypes.data), off.ctypes.data_as(i64p), off.size - 1)]
+        rc = L.icnv_cnv_report_begin_dev(ct.byref(self._h), code, _ptr(records), stride, n, *tab[:8], self._pos[0].ctypes.data_as(i64p),
+                                         self._pos[1].ctypes.data_as(i64p), G, totals, _stream())
+        if rc == _lib.ERR_ARG:
+            raise ValueError(L.icnv_last_error().decode("utf-8", "replace"))
+        check(rc)
+        self.total_bytes, self.total_lines, self.max_record_bytes = (int(v) for v in totals)
+
+    def format_into(self, out, rec0):
+        """icnv_cnv_report_format_dev: the records rec0 .. into `out`, a contiguous CUDA uint8 tensor whose size is the
+        capacity, as many whole records as it holds.  Returns (records done, bytes, int64 record offsets [done + 1]).
+        Synchronises the stream."""
+        L = _lib.load()
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous()):
+            raise TypeError("out must be a contiguous one-dimensional CUDA uint8 tensor")
+        rec0 = int(rec0)
+        offsets = np.zeros(max(self.n_records - rec0, 0) + 1, dtype=np.int64)
+        done, nbytes = ct.c_int64(0), ct.c_int64(0)
+        check(L.icnv_cnv_report_format_dev(self._h, rec0, _ptr(out), int(out.numel()), offsets.ctypes.data_as(ct.POINTER(ct.c_int64)),
+                                           ct.byref(done), ct.byref(nbytes), _stream()))
+        return int(done.value), int(nbytes.value), offsets[:int(done.value) + 1]
+
+    def close(self):
+        if self._h:
+            _lib.load().icnv_cnv_report_end(self._h)
+            self._h = ct.c_void_p()
+        self._records = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cnv_report(kind, records, groups, chrs, genes, start, end, capacity=None):
+    """The whole body of one report file as bytes (CnvReportPlan, chunk after chunk of `capacity` bytes): for tests and small
+    reports; generate_cnv_region_reports streams the chunks to the file instead."""
+    with CnvReportPlan(kind, records, groups, chrs, genes, start, end) as plan:
+        if plan.n_records == 0:
+            return b""
+        cap = max(int(capacity) if capacity is not None else plan.total_bytes, 1)
+        out = torch.empty(cap, dtype=torch.uint8, device=records.device)
+        parts, rec = [], 0
+        while rec < plan.n_records:
+            done, nbytes, _ = plan.format_into(out, rec)
+            parts.append(out[:nbytes].cpu().numpy().tobytes())
+            rec += done
+        return b"".join(parts)
+
+
+def cnv_report_stats(reset=False):
+    """icnv_cnv_report_stats as a dict (`calls`: format calls; `us`: their wall time in microseconds); reset=True zeroes the
+    counters."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(CNV_REPORT_STATS))()
+    check(L.icnv_cnv_report_stats(out, len(CNV_REPORT_STATS)))
+    if reset:
+        L.icnv_cnv_report_stats_reset()
+    return dict(zip(CNV_REPORT_STATS, (int(v) for v in out)))
+
+
 # ------------------------------------------------------------------ count matrices from text (DESIGN K21)
 TABLE_PARSE_STATS = ("calls", "rows", "fields", "host_parsed", "bytes", "collect_rounds", "us")
 READ_TABLE_CHUNK = 64 << 20        # bytes of one chunk of read_table; ICNV_READ_TABLE_CHUNK (developer switch) overrides it

@@ -19,10 +19,7 @@ import json
 import locale
 import math
 import os
-import queue
 import struct
-import threading
-import time
 import zlib
 
 import numpy as np
@@ -30,6 +27,7 @@ import torch
 
 from . import device
 from .infercnv_object import InfercnvObject
+from .text_stream import stream_chunks
 from .tumor_subclusters import HClust
 
 NB_BREAKS = 16
@@ -179,9 +177,10 @@ def write_matrix(path, x, cells, orientation, row_names=None, col_names=None, qu
     over all genes (the other members files).  row_names: one per line, or None.
 
     The header line is written here.  The body is streamed in chunks of whole rows through two device buffers and two pinned
-    host buffers: while the library formats chunk i + 1, chunk i is copied to the host on a second stream and a writer thread
-    hands chunk i - 1 to the file.  Returns a dict of counts and seconds (format_s: inside the library; copy_wait_s and
-    write_s: the writer thread waiting for a copy and inside f.write; stall_s: this thread waiting for a free buffer)."""
+    host buffers (text_stream.stream_chunks): while the library formats chunk i + 1, chunk i is copied to the host on a second
+    stream and a writer thread hands chunk i - 1 to the file.  Returns a dict of counts and seconds (format_s: inside the
+    library; copy_wait_s and write_s: the writer thread waiting for a copy and inside f.write; stall_s: this thread waiting
+    for a free buffer; wall_s: from the first chunk to the last write, the buffers' allocation left out)."""
     code = device.TABLE_ORIENTATIONS[orientation]
     C, G = x.shape
     cells = np.ascontiguousarray(cells, dtype=np.int32)
@@ -195,68 +194,19 @@ def write_matrix(path, x, cells, orientation, row_names=None, col_names=None, qu
         packed = device.pack_labels([fmt(str(r)).encode(enc) for r in row_names])
     worst = n_rows * n_fields * 23 + (int(packed[1][-1]) + n_rows if packed else 0)
     cap = max(1, min(int(os.environ.get("ICNV_TABLE_TEXT_CHUNK", TABLE_TEXT_CHUNK)), worst))
-    stats = {"bytes": 0, "chunks": 0, "format_s": 0.0, "copy_wait_s": 0.0, "write_s": 0.0, "stall_s": 0.0}
-    dev = [torch.empty(cap, dtype=torch.uint8, device=x.device) for _ in range(2)]
-    pin = [torch.empty(cap, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-    copy_stream = torch.cuda.Stream(device=x.device)
-    jobs, free, failure = queue.Queue(), [threading.Semaphore(1), threading.Semaphore(1)], []
-    t_start = time.perf_counter()
+    rows = {"next": 0}
+
+    def fill(buf):
+        if rows["next"] >= n_rows:
+            return None
+        done, nbytes, _ = device.format_table_into(x, buf, rows["next"], n_rows - rows["next"], cells, code, packed, sep)
+        rows["next"] += done
+        return nbytes
+
     with open(path, "wb") as f:
         if col_names is not None:
             f.write((sep.join(fmt(str(c)) for c in col_names) + "\n").encode(enc))
-
-        def writer():
-            while True:
-                job = jobs.get()
-                if job is None:
-                    return
-                slot, nbytes, event = job
-                try:
-                    if not failure:
-                        t0 = time.perf_counter()
-                        event.synchronize()
-                        t1 = time.perf_counter()
-                        f.write(memoryview(pin[slot].numpy())[:nbytes])
-                        stats["copy_wait_s"] += t1 - t0
-                        stats["write_s"] += time.perf_counter() - t1
-                except Exception as exc:          # handed to the caller's thread below
-                    failure.append(exc)
-                finally:
-                    free[slot].release()
-
-        thread = threading.Thread(target=writer, daemon=True)
-        thread.start()
-        try:
-            row, i = 0, 0
-            while row < n_rows and not failure:
-                slot = i % 2
-                t0 = time.perf_counter()
-                free[slot].acquire()               # chunk i - 2 has left this pair of buffers
-                t1 = time.perf_counter()
-                try:
-                    done, nbytes, _ = device.format_table_into(x, dev[slot], row, n_rows - row, cells, code, packed, sep)
-                except Exception:
-                    free[slot].release()
-                    raise
-                stats["stall_s"] += t1 - t0
-                stats["format_s"] += time.perf_counter() - t1
-                copy_stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(copy_stream):
-                    pin[slot][:nbytes].copy_(dev[slot][:nbytes], non_blocking=True)
-                    event = torch.cuda.Event()
-                    event.record(copy_stream)
-                jobs.put((slot, nbytes, event))
-                row += done
-                i += 1
-                stats["bytes"] += nbytes
-                stats["chunks"] += 1
-        finally:
-            jobs.put(None)
-            thread.join()
-        if failure:
-            raise failure[0]
-    stats["wall_s"] = time.perf_counter() - t_start
-    return stats
+        return stream_chunks(f, cap, x.device, fill)
 
 
 # ------------------------------------------------------------------ PNG
