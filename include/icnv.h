@@ -788,6 +788,11 @@ void icnv_de_stats_reset(void);
  *   A region without cells: NaN theta_sum and theta_samples, nothing else.
  *   A cell with exactly one L > 0 has the same eps whatever theta and u are; it is counted once and never visited.
  *   ICNV_BAYES_DECIDED=0 (environment) visits every cell instead: the output is identical.
+ *   Residency classes, by a region's undecided cells: more than 512 stream their L rows from memory, up to 512 keep them in
+ *   LDS (one workgroup per (region, chain)), and a region with cells of which at most 8 are undecided -- every region of a
+ *   per-cell report -- is sampled by an 8-lane group, eight (region, chain) pairs to a wavefront, in registers (K25).  Every
+ *   draw has its own counter, S and the kept-theta sums are sequential, freq is integer: the class does not show in the output.
+ *   ICNV_BAYES_PACKED=0 (environment, read per call) sends the third class down the LDS path.
  * Limits: 2 <= K <= 8 (more: ICNV_ERR_UNSUPPORTED), tau > 0, indices in range: ICNV_ERR_ARG before any launch.  Synchronises. */
 #define ICNV_BAYES_GAMMA_ATTEMPTS 64
 int icnv_bayes_loglik_dev(const double *expr, int64_t G, int64_t C, int64_t ld, const int32_t *gene_start, const int32_t *gene_count,
@@ -804,10 +809,22 @@ int icnv_bayes_sample_dev(const double *L, const int64_t *cell_off, const uint64
 int icnv_bayes_sample(const double *L, const int64_t *cell_off, const uint64_t *token, int32_t n_regions, int32_t K, int32_t n_adapt,
                       int32_t n_burn, int32_t n_keep, uint64_t seed, double *theta_sum, double *theta_samples, int32_t *freq);
 /* Counters since the last reset: out[0] sample calls, [1] regions, [2] (region, cell) rows, [3] undecided rows, [4] regions
- * sampled from LDS (<= 512 undecided cells), [5] regions streamed, [6] wall microseconds of the sample calls, [7] of the
- * likelihood calls. */
+ * with <= 512 undecided cells (the packed ones included), [5] regions streamed, [6] wall microseconds of the sample calls,
+ * [7] of the likelihood calls, [8] regions sampled by the packed kernel (cells, <= 8 of them undecided). */
 int icnv_bayes_stats(int64_t *out, int32_t n);
 void icnv_bayes_stats_reset(void);
+
+/* The rectangle rewrite of the Bayesian filter (removeCNV / reassignCNV, R/inferCNV_BayesNet.R:562-630, 491-540) for every
+ * region of a run in one launch (K25).  states: DEVICE uint8, element (gene g, cell c) at states[c * ld + g], ld >= G.  Region
+ * r is the genes gene_first[r] .. + gene_count[r] - 1 (gene_count >= 1) x the cells cell_idx[cell_off[r] .. cell_off[r + 1] - 1];
+ * every byte of the rectangle becomes value[r], and value[r] == 0 leaves it alone.  gene_first, gene_count (int32), cell_off
+ * (int64, n_regions + 1, from 0, monotone), cell_idx (int32, n_idx entries, cell_off[n_regions] <= n_idx) and value (uint8)
+ * are DEVICE arrays.  The rectangles of one call must be DISJOINT: overlap is not detected, and which value an overlapped
+ * byte keeps is not defined.  Every index is checked on the device before anything is written: ICNV_ERR_ARG leaves states
+ * untouched.  The check synchronises the stream; the fill itself is left running on it. */
+int icnv_state_fill_regions_dev(uint8_t *states, int64_t G, int64_t C, int64_t ld, int32_t n_regions, const int32_t *gene_first,
+                                const int32_t *gene_count, const int64_t *cell_off, const int32_t *cell_idx, int64_t n_idx,
+                                const uint8_t *value, void *stream);
 
 /* ---- per-cell CNV features and run-length segmentation (K14) -------------------------------------------------------------
  * The numbers behind add_to_seurat's map_metadata_from_infercnv.txt (.get_features, R/seurat_interaction.R:244-353) and the

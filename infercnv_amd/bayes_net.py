@@ -8,8 +8,10 @@ Plotting (postProbNormal, plotProbabilities, mcmcDiagnosticPlots) stays out.  In
 states keep R's numbering 1..K."""
 from __future__ import annotations
 
+import operator
 import os
-from dataclasses import dataclass, field
+from collections.abc import Sequence
+from dataclasses import dataclass, field, replace
 from typing import List, Optional
 
 import numpy as np
@@ -44,6 +46,205 @@ class MCMCInferCNV:
     cell_probabilities: List[np.ndarray] = field(default_factory=list)
     args: dict = field(default_factory=dict)
     x_dev: object = None                      # the (C, G) CUDA matrix the sampler reads
+    table: object = None                      # route="table": the RegionTable behind the four per-region sequences
+
+
+# ---- the table route (DESIGN K25) ---------------------------------------------------------------------------------------
+_FNV_OFFSET, _FNV_PRIME = 0xCBF29CE484222325, 0x100000001B3
+
+
+def region_tokens(chr_names, chr_i, ordinal):
+    """fnv1a64("<chr>-region_<ordinal>") of every region as a uint64 array: the prefix is hashed once per chromosome, the
+    ordinal's decimal digits (at most ten: ordinals below 10^10) take one step each over the whole array."""
+    chr_i, ordinal = np.asarray(chr_i, dtype=np.int64), np.asarray(ordinal, dtype=np.int64)
+    if ordinal.size and (int(ordinal.min()) < 0 or int(ordinal.max()) >= 10 ** 10):
+        raise ValueError("region ordinals must be in 0 .. 10^10 - 1")
+    prefix = np.array([fnv1a64(f"{c}-region_") for c in chr_names], dtype=np.uint64)
+    h = prefix[chr_i] if ordinal.size else np.zeros(0, dtype=np.uint64)
+    n_digits = np.searchsorted(10 ** np.arange(1, 10, dtype=np.int64), ordinal, side="right") + 1
+    prime = np.uint64(_FNV_PRIME)
+    with np.errstate(over="ignore"):
+        for step in range(int(n_digits.max()) if ordinal.size else 0):
+            live = n_digits > step
+            digit = (ordinal // 10 ** np.maximum(n_digits - 1 - step, 0)) % 10
+            h = np.where(live, (h ^ (digit + 48).astype(np.uint64)) * prime, h)
+    return h
+
+
+def _ranges(start, count):
+    """concatenate([arange(s, s + c) for s, c in zip(start, count)]) without the loop."""
+    start, count = np.asarray(start, dtype=np.int64), np.asarray(count, dtype=np.int64)
+    end = np.cumsum(count)
+    return np.arange(int(end[-1]) if end.size else 0, dtype=np.int64) + np.repeat(start - (end - count), count)
+
+
+@dataclass
+class RegionTable:
+    """The predicted CNV regions of a run as arrays, one entry per region in report order (cell group, then gene).  groups:
+    [(name, 0-based cell indices)] in report order; chr_names: chromosomes in order of first appearance; perm: the gene gather
+    of chr_layout(), or None; col: index into groups; chr: index into chr_names; gene_first / gene_count: the run in the
+    gathered gene order; row_first: its first row in the object's own gene order (the run is contiguous there too); state: the
+    HMM state, -1 for the invalid state; ordinal: the counter of the region's name "<chr>-region_<ordinal>"; token: fnv1a64 of
+    that name; cell_idx[cell_off[r] : cell_off[r + 1]]: the region's cells, ascending.  source: the table this one was
+    taken from by take() (the regions the step-17 reports hold), else None."""
+    groups: list
+    chr_names: np.ndarray
+    perm: Optional[np.ndarray]
+    col: np.ndarray
+    chr: np.ndarray
+    gene_first: np.ndarray
+    gene_count: np.ndarray
+    row_first: np.ndarray
+    state: np.ndarray
+    ordinal: np.ndarray
+    token: np.ndarray
+    cell_off: np.ndarray
+    cell_idx: np.ndarray
+    source: object = None
+
+    def __len__(self):
+        return int(self.col.size)
+
+    @staticmethod
+    def from_records(groups, chr_names, perm, rec):
+        """rec: the six int64 record arrays of device.cnv_runs (col, chr, gene_first, gene_last, state with 255 for the
+        invalid state, ordinal)."""
+        col, chr_i, first, last, state, ordinal = (np.asarray(r, dtype=np.int64) for r in rec)
+        count = last - first + 1
+        if perm is None:
+            row_first = first.copy()
+        else:                                   # a run must stay one run of rows in the object's own order
+            perm = np.asarray(perm, dtype=np.int64)
+            breaks = np.concatenate([[0], np.cumsum(np.diff(perm) != 1)])
+            bad = np.nonzero(breaks[last] != breaks[first])[0]
+            if bad.size:
+                name = f"{chr_names[chr_i[bad[0]]]}-region_{ordinal[bad[0]]}"
+                raise ValueError(f"region {name}: its genes must be one contiguous run of rows (order the object by chromosome)")
+            row_first = perm[first]
+        sizes = np.fromiter((len(g) for _, g in groups), dtype=np.int64, count=len(groups))
+        members = (np.concatenate([np.asarray(g, dtype=np.int64).ravel() for _, g in groups]) if len(groups)
+                   else np.zeros(0, dtype=np.int64))
+        owner = np.repeat(np.arange(len(groups), dtype=np.int64), sizes)
+        members = members[np.lexsort((members, owner))]          # every group's cells ascending
+        g_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        n_cells = sizes[col] if col.size else np.zeros(0, dtype=np.int64)
+        cell_off = np.concatenate([[0], np.cumsum(n_cells)]).astype(np.int64)
+        cell_idx = members[_ranges(g_off[col], n_cells)].astype(np.int32) if col.size else np.zeros(0, dtype=np.int32)
+        return RegionTable(groups=groups, chr_names=np.asarray(chr_names), perm=perm, col=col, chr=chr_i, gene_first=first,
+                           gene_count=count, row_first=row_first, state=np.where(state == 255, -1, state), ordinal=ordinal,
+                           token=region_tokens(chr_names, chr_i, ordinal), cell_off=cell_off, cell_idx=cell_idx)
+
+    @staticmethod
+    def from_states(infercnv_obj, HMM_states, by, normal):
+        """The regions inferCNVBayesNet samples: the runs of get_predicted_CNV_regions(states, by) whose state is not `normal`.
+        The states go to the device once as uint8 (as generate_cnv_region_reports sends them); group modes segment the groups'
+        consensus columns, by = "cell" the cells' own columns with every byte outside 1 .. 6 as the invalid state."""
+        import torch
+        groups = cnv_regions._cell_groups(infercnv_obj, by)
+        by_cell = by == "cell" and infercnv_obj.tumor_subclusters is not None
+        perm, chr_start = infercnv_obj.chr_layout()
+        chrs = np.asarray(infercnv_obj.gene_order.chr)
+        st = np.asarray(HMM_states)
+        st = np.asfortranarray(np.where(st < 0, 255, st).astype(np.uint8))
+        if perm is not None:                    # the kernels see contiguous chromosomes only
+            st, chrs = np.asfortranarray(st[perm]), chrs[perm]
+        if by_cell:
+            st = np.asfortranarray(np.where((st >= 1) & (st <= 6), st, 255).astype(np.uint8))
+        rec = np.zeros((6, 0), dtype=np.int64)
+        if st.shape[1] and groups:
+            dev_states = torch.from_numpy(st.T).cuda()
+            if by_cell:
+                mat, col_idx = dev_states, np.concatenate([g for _, g in groups]).astype(np.int32)
+            else:
+                mat, col_idx = device.state_consensus(dev_states, [g for _, g in groups]), None
+            rec = device.cnv_runs(mat, chr_start, neutral=int(normal), K=0, col_idx=col_idx)[0].cpu().numpy()
+        return RegionTable.from_records(groups, chrs[chr_start[:-1]], perm, rec)
+
+    def take(self, keep, state=None):
+        """The regions `keep` (a boolean mask or ascending indices), optionally with new states."""
+        idx = np.nonzero(keep)[0] if np.asarray(keep).dtype == bool else np.asarray(keep, dtype=np.int64)
+        n_cells = np.diff(self.cell_off)[idx]
+        cells = self.cell_idx[_ranges(self.cell_off[:-1][idx], n_cells)] if idx.size else self.cell_idx[:0]
+        return replace(self, col=self.col[idx], chr=self.chr[idx], gene_first=self.gene_first[idx], gene_count=self.gene_count[idx],
+                       row_first=self.row_first[idx], state=(self.state if state is None else np.asarray(state, dtype=np.int64))[idx],
+                       ordinal=self.ordinal[idx], token=self.token[idx],
+                       cell_off=np.concatenate([[0], np.cumsum(n_cells)]).astype(np.int64), cell_idx=cells,
+                       source=self if self.source is None else self.source)
+
+    def name(self, r):
+        return f"{self.chr_names[self.chr[r]]}-region_{self.ordinal[r]}"
+
+    def cell_gene(self, r):
+        rows = np.arange(self.gene_first[r], self.gene_first[r] + self.gene_count[r], dtype=np.int64)
+        if self.perm is not None:
+            rows = self.perm[rows]
+        return {"cnv_regions": self.name(r), "Genes": rows, "Cells": self.cell_idx[self.cell_off[r]:self.cell_off[r + 1]].astype(np.int64),
+                "State": int(self.state[r])}
+
+    def group_id(self, n_obs):
+        """Per cell below n_obs the 1-based number of its cell group among the groups that have a region (NA_INTEGER elsewhere)."""
+        has = np.zeros(len(self.groups), dtype=bool)
+        has[self.col] = True
+        number = np.cumsum(has)
+        out = np.full(n_obs, NA_INTEGER, dtype=np.int64)
+        which = np.nonzero(has)[0]
+        if which.size:
+            sizes = np.fromiter((len(self.groups[g][1]) for g in which), dtype=np.int64, count=which.size)
+            cells = np.concatenate([np.asarray(self.groups[g][1], dtype=np.int64).ravel() for g in which])
+            gid = np.repeat(number[which], sizes)
+            sel = cells < n_obs
+            out[cells[sel]] = gid[sel]          # groups in report order: where two share a cell the later one stays
+        return out
+
+
+class _LazySeq(Sequence):
+    """A read-only sequence whose element i is make(i), built when it is asked for (cnv_regions._RegionList is the precedent)."""
+
+    def __init__(self, n, make):
+        self._n, self._make = int(n), make
+
+    def __len__(self):
+        return self._n
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self._make(k) for k in range(*i.indices(self._n))]
+        i = operator.index(i)
+        if i < 0:
+            i += self._n
+        if not 0 <= i < self._n:
+            raise IndexError("region index out of range")
+        return self._make(i)
+
+
+def _attach_table(obj: "MCMCInferCNV", table: RegionTable):
+    obj.table = table
+    obj.cnv_regions = _LazySeq(len(table), table.name)
+    obj.cell_gene = _LazySeq(len(table), table.cell_gene)
+
+
+def run_mcmc_table(obj: "MCMCInferCNV") -> "MCMCInferCNV":
+    """run_mcmc on obj.table: the same two device calls, fed from the table's arrays."""
+    a, t = obj.args, obj.table
+    K = len(obj.mu)
+    R = len(t)
+    if R == 0:
+        obj.cnv_probabilities, obj.cell_probabilities, obj.cnv_means = _LazySeq(0, None), _LazySeq(0, None), np.zeros((K, 0))
+        return obj
+    _, L, off = device.bayes_loglik_arrays(obj.x_dev, t.row_first, t.gene_count, t.cell_idx, t.cell_off, obj.mu, obj.sig)
+    theta_sum, samples, freq = device.bayes_sample(L, off, t.token, a["n_adapt"], a["n_burn"], a["n_keep"], a["seed"],
+                                                   want_samples=a["keep_samples"])
+    theta_sum = theta_sum.cpu().numpy()
+    freq = freq.cpu().numpy()
+    n = float(K * a["n_keep"])
+    tot = np.zeros((R, K))
+    for ch in range(K):                        # the chain sums in chain order, one division
+        tot = tot + theta_sum[:, ch, :]
+    obj.cnv_means = (tot / n).T.copy()
+    samples = samples.cpu().numpy() if samples is not None else None
+    obj.cnv_probabilities = _LazySeq(R, (lambda r: samples[r].reshape(-1, K)) if samples is not None else (lambda r: None))
+    obj.cell_probabilities = _LazySeq(R, lambda r: (freq[off[r]:off[r + 1]].astype(np.float64) / n).T.copy())
+    return obj
 
 
 def mean_sd(infercnv_obj: InfercnvObject, HMM_type, i3_p_val=0.05):
@@ -93,41 +294,52 @@ def run_mcmc(obj: MCMCInferCNV) -> MCMCInferCNV:
 
 def inferCNVBayesNet(infercnv_obj: InfercnvObject, HMM_states, HMM_type="i6", by="subcluster", postMcmcMethod="removeCNV",
                      reassignCNVs=True, out_dir=None, seed=0, n_adapt=500, n_burn=200, n_keep=1000, keep_samples=False,
-                     i3_p_val=0.05, mu=None, sig=None, x=None) -> MCMCInferCNV:
+                     i3_p_val=0.05, mu=None, sig=None, x=None, *, route="dict") -> MCMCInferCNV:
     """inferCNVBayesNet (R/inferCNV_BayesNet.R:1237-1364).  infercnv_obj: the object the HMM ran on (its expr_data are the
     values the mixture model sees); HMM_states: the genes x cells state matrix of step 17 (1..K).  The regions are those of
     cnv_regions.get_predicted_CNV_regions(states, by) without the neutral state -- what initializeObject / getGenesCells
     (:245-338) read back from the step-17 report files.  mu / sig default to mean_sd(); x: the (C, G) CUDA matrix when it is
-    already on the device.  keep_samples: also keep every theta sample (K n_keep x K per region)."""
+    already on the device.  keep_samples: also keep every theta sample (K n_keep x K per region).
+    route: "dict" builds one Python object per region; "table" (DESIGN K25) keeps the regions as the arrays of a RegionTable
+    (obj.table) -- cnv_regions, cell_gene, cell_probabilities and cnv_probabilities are then read-only sequences whose
+    elements, equal to the dict route's, are built when they are indexed.  postMcmcMethod = "removeCells" needs the dict route."""
     import torch
     if HMM_type not in ("i6", "i3"):
         raise ValueError("HMM_type must be i6 or i3")
+    if route not in ("dict", "table"):
+        raise ValueError("route must be dict or table")
     normal = _normal_state(HMM_type)
-    states = np.asarray(HMM_states)
-    st_obj = infercnv_obj.copy()
-    st_obj.expr_data = states.astype(np.float64)
-    groups = cnv_regions.get_predicted_CNV_regions(st_obj, by)
-    cells_all = infercnv_obj.cells()
-    col_of = {str(c): i for i, c in enumerate(cells_all)}
+    if route == "table" and postMcmcMethod == "removeCells":
+        raise ValueError('postMcmcMethod = "removeCells" is not built on the table route: use route="dict"')
     obj = MCMCInferCNV(infercnv_obj=infercnv_obj)
     obj.args = {"HMM_type": HMM_type, "postMcmcMethod": postMcmcMethod, "reassignCNVs": bool(reassignCNVs), "out_dir": out_dir,
                 "BayesMaxPNormal": 0, "seed": int(seed), "n_adapt": int(n_adapt), "n_burn": int(n_burn), "n_keep": int(n_keep),
                 "keep_samples": bool(keep_samples), "by": by}
     n_obs = max((int(np.max(v)) + 1 for v in infercnv_obj.observation_grouped_cell_indices.values() if len(v)), default=0)
-    group_id = np.full(n_obs, NA_INTEGER, dtype=np.int64)
-    gid = 0
-    for grp in groups:
-        cols = np.sort(np.array([col_of[str(c)] for c in grp["cells"]], dtype=np.int64))
-        kept = [(rn, r) for rn, r in grp["gene_regions"] if r["state"] != normal]
-        if not kept:
-            continue
-        gid += 1                                # unique(pred_cnv_genes_df$cell_group_name): groups with a region, in file order
-        group_id[cols[cols < n_obs]] = gid
-        for rn, r in kept:
-            obj.cnv_regions.append(rn)
-            obj.cell_gene.append({"cnv_regions": rn, "Genes": np.asarray(r["gene"], dtype=np.int64), "Cells": cols.copy(),
-                                  "State": int(r["state"])})
-    obj.group_id = group_id
+    if route == "table":
+        _attach_table(obj, RegionTable.from_states(infercnv_obj, HMM_states, by, normal))
+        obj.group_id = obj.table.group_id(n_obs)
+    else:
+        states = np.asarray(HMM_states)
+        st_obj = infercnv_obj.copy()
+        st_obj.expr_data = states.astype(np.float64)
+        groups = cnv_regions.get_predicted_CNV_regions(st_obj, by)
+        cells_all = infercnv_obj.cells()
+        col_of = {str(c): i for i, c in enumerate(cells_all)}
+        group_id = np.full(n_obs, NA_INTEGER, dtype=np.int64)
+        gid = 0
+        for grp in groups:
+            cols = np.sort(np.array([col_of[str(c)] for c in grp["cells"]], dtype=np.int64))
+            kept = [(rn, r) for rn, r in grp["gene_regions"] if r["state"] != normal]
+            if not kept:
+                continue
+            gid += 1                            # unique(pred_cnv_genes_df$cell_group_name): groups with a region, in file order
+            group_id[cols[cols < n_obs]] = gid
+            for rn, r in kept:
+                obj.cnv_regions.append(rn)
+                obj.cell_gene.append({"cnv_regions": rn, "Genes": np.asarray(r["gene"], dtype=np.int64), "Cells": cols.copy(),
+                                      "State": int(r["state"])})
+        obj.group_id = group_id
     if mu is None or sig is None:
         mu, sig = mean_sd(infercnv_obj, HMM_type, i3_p_val)
     obj.mu, obj.sig = np.asarray(mu, dtype=np.float64), np.asarray(sig, dtype=np.float64)
@@ -135,7 +347,7 @@ def inferCNVBayesNet(infercnv_obj: InfercnvObject, HMM_states, HMM_type="i6", by
         raise ValueError("mu and sig must have one entry per state")
     obj.x_dev = x if x is not None else torch.from_numpy(
         np.ascontiguousarray(np.asarray(infercnv_obj.expr_data, dtype=np.float64).T)).cuda()
-    return run_mcmc(obj)
+    return run_mcmc_table(obj) if route == "table" else run_mcmc(obj)
 
 
 # ---- step 19 ----------------------------------------------------------------------------------------------------------
@@ -177,20 +389,84 @@ def _remove_cnv(obj: MCMCInferCNV, st: _States):
         return obj
     for i in remove:
         st.fill(obj.cell_gene[i]["Genes"], obj.cell_gene[i]["Cells"], normal)
-    keep = [i for i in range(len(obj.cell_gene)) if i not in set(remove.tolist())]
+    mask = np.ones(len(obj.cell_gene), dtype=bool)
+    mask[remove] = False
+    keep = np.nonzero(mask)[0].tolist()
     obj.cell_gene = [obj.cell_gene[i] for i in keep]
     obj.cnv_regions = [obj.cnv_regions[i] for i in keep]
     obj.cell_probabilities = [obj.cell_probabilities[i] for i in keep]
     obj.cnv_probabilities = [obj.cnv_probabilities[i] for i in keep]
     obj.cnv_means = obj.cnv_means[:, keep]
-    out_dir = obj.args.get("out_dir")
-    if out_dir is not None:
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, "CNV_State_Probabilities.dat"), "w") as fh:   # write.table(row.names = TRUE): no corner cell
-            fh.write("\t".join(cg["cnv_regions"] for cg in obj.cell_gene) + "\n")
-            for k in range(obj.cnv_means.shape[0]):
-                fh.write("\t".join([f"State:{k + 1}"] + [cnv_regions._fmt(float(v)) if v == v else "NaN" for v in obj.cnv_means[k]]) + "\n")
+    _write_state_probabilities(obj.args.get("out_dir"), [cg["cnv_regions"] for cg in obj.cell_gene], obj.cnv_means)
     return obj
+
+
+def _write_state_probabilities(out_dir, names, cnv_means):
+    if out_dir is None:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "CNV_State_Probabilities.dat"), "w") as fh:   # write.table(row.names = TRUE): no corner cell
+        fh.write("\t".join(names) + "\n")
+        for k in range(cnv_means.shape[0]):
+            fh.write("\t".join([f"State:{k + 1}"] + [cnv_regions._fmt(float(v)) if v == v else "NaN" for v in cnv_means[k]]) + "\n")
+
+
+def _filter_table(mcmc_obj: MCMCInferCNV, HMM_states, BayesMaxPNormal):
+    """filterHighPNormals on the table route: removeCNV's and reassignCNV's decisions as array expressions -- strictly above
+    the threshold, a NaN column stays and keeps its HMM state, the first maximum is the new state -- and ONE
+    device.fill_regions call for every rectangle: the normal state for the removed regions, the new state for the kept ones
+    when reassignCNVs is set, 0 (leave alone) otherwise."""
+    import copy
+    import torch
+    obj = copy.copy(mcmc_obj)
+    obj.args = dict(mcmc_obj.args, BayesMaxPNormal=BayesMaxPNormal)
+    t = mcmc_obj.table
+    on_device = isinstance(HMM_states, torch.Tensor)
+    if on_device and (not HMM_states.is_cuda or HMM_states.dim() != 2):
+        raise TypeError("HMM_states: a genes x cells array or a (cells, genes) CUDA tensor")
+    host = None if on_device else np.asarray(HMM_states)
+    method = obj.args.get("postMcmcMethod")
+    if method is None:
+        return obj, (HMM_states.clone() if on_device else np.array(host))
+    if method != "removeCNV":
+        raise ValueError('postMcmcMethod = "removeCells" is not built on the table route')
+    normal = _normal_state(obj.args["HMM_type"])
+    means = mcmc_obj.cnv_means
+    R = len(t)
+    remove = (means[normal - 1] > BayesMaxPNormal) if R else np.zeros(0, dtype=bool)   # NaN compares false: it stays
+    value = np.where(remove, normal, 0).astype(np.uint8)
+    state = t.state.copy()
+    if obj.args.get("reassignCNVs") and R:
+        moved = ~remove & ~np.isnan(means).any(axis=0)
+        best = np.argmax(means, axis=0) + 1                      # the first maximum
+        state[moved] = best[moved]
+        value[moved] = best[moved]
+    kept = np.nonzero(~remove)[0]
+    _attach_table(obj, t.take(kept, state))
+    obj.cnv_means = means[:, kept]
+    cell_p, cnv_p = mcmc_obj.cell_probabilities, mcmc_obj.cnv_probabilities
+    obj.cell_probabilities = _LazySeq(kept.size, lambda i: cell_p[int(kept[i])])
+    obj.cnv_probabilities = _LazySeq(kept.size, lambda i: cnv_p[int(kept[i])])
+    if remove.any():
+        _write_state_probabilities(obj.args.get("out_dir"), list(obj.cnv_regions), obj.cnv_means)
+
+    def fill(m):
+        if value.any():
+            device.fill_regions(m, t.row_first, t.gene_count, t.cell_off, t.cell_idx, value)
+        return m
+
+    if on_device and HMM_states.dtype == torch.uint8:
+        return obj, fill(HMM_states.clone(memory_format=torch.contiguous_format))
+    # any other element type: the rectangles are drawn on a zero uint8 matrix and laid over the input
+    C, G = HMM_states.shape if on_device else host.shape[::-1]
+    over = fill(torch.zeros((C, G), dtype=torch.uint8, device=HMM_states.device if on_device else "cuda"))
+    if on_device:
+        return obj, torch.where(over != 0, over.to(HMM_states.dtype), HMM_states)
+    over = over.cpu().numpy().T
+    out = np.array(host)
+    hit = over != 0
+    out[hit] = over[hit]
+    return obj, out
 
 
 def _remove_cells(obj: MCMCInferCNV, st: _States):
@@ -228,6 +504,8 @@ def filterHighPNormals(mcmc_obj: MCMCInferCNV, HMM_states, BayesMaxPNormal):
     (cells, genes) CUDA tensor, which stays on the device and is rewritten there; a new array / tensor of the same kind comes
     back.  The object passed in is not modified."""
     import copy
+    if mcmc_obj.table is not None:
+        return _filter_table(mcmc_obj, HMM_states, BayesMaxPNormal)
     obj = copy.copy(mcmc_obj)
     obj.cell_gene = [dict(cg) for cg in mcmc_obj.cell_gene]
     obj.cnv_regions = list(mcmc_obj.cnv_regions)

@@ -332,6 +332,28 @@ class _RegionList(Sequence):
         return {"cell_group_name": name, "cells": self._cells[idx], "gene_regions": regions, "cnv_ranges": ranges}
 
 
+def _stream_report(path, kind, header, rec, tables, g_start, g_stop, chunk):
+    """One report file: `header` (bytes), then the text of the records `rec` (int32 (6, n) CUDA tensor) from
+    device.CnvReportPlan, streamed in chunks of whole records.  Returns (stream_chunks' statistics or None, lines)."""
+    from . import device
+    from .text_stream import stream_chunks
+    with open(path, "wb") as fh, device.CnvReportPlan(kind, rec, *tables, g_start, g_stop) as plan:
+        fh.write(header)
+        state = {"next": 0}
+
+        def fill(buf):
+            if state["next"] >= plan.n_records:
+                return None
+            done, nbytes, _ = plan.format_into(buf, state["next"])
+            state["next"] += done
+            return nbytes
+
+        streamed = None
+        if plan.n_records:
+            streamed = stream_chunks(fh, max(plan.max_record_bytes, min(chunk, plan.total_bytes)), rec.device, fill)
+        return streamed, plan.total_lines
+
+
 def generate_cnv_region_reports(infercnv_obj: InfercnvObject, output_filename_prefix, out_dir, ignore_neutral_state=None,
                                 by="consensus"):
     """R/inferCNV_HMM.R:790-869: writes <prefix>.cell_groupings, .pred_cnv_regions.dat, .pred_cnv_genes.dat and
@@ -352,7 +374,6 @@ def generate_cnv_region_reports(infercnv_obj: InfercnvObject, output_filename_pr
         return _generate_cnv_region_reports_host(infercnv_obj, output_filename_prefix, out_dir, ignore_neutral_state, by)
     import torch
     from . import device
-    from .text_stream import stream_chunks
     t0 = time.perf_counter()
     enc = locale.getpreferredencoding(False)
     groups = _cell_groups(infercnv_obj, by)
@@ -394,20 +415,10 @@ def generate_cnv_region_reports(infercnv_obj: InfercnvObject, output_filename_pr
     chunk = int(os.environ.get("ICNV_CNV_REPORT_CHUNK", REPORT_CHUNK))
     for kind, suffix, header in (("regions", ".pred_cnv_regions.dat", REGIONS_HEADER), ("genes", ".pred_cnv_genes.dat", GENES_HEADER)):
         t2 = time.perf_counter()
-        with open(path(suffix), "wb") as fh, device.CnvReportPlan(kind, rec, *tables, g_start, g_stop) as plan:
-            fh.write(header.encode(enc))
-            state = {"next": 0}
-
-            def fill(buf):
-                if state["next"] >= plan.n_records:
-                    return None
-                done, nbytes, _ = plan.format_into(buf, state["next"])
-                state["next"] += done
-                return nbytes
-
-            if plan.n_records:
-                stats[kind] = stream_chunks(fh, max(plan.max_record_bytes, min(chunk, plan.total_bytes)), rec.device, fill)
-            stats[kind + "_lines"], stats[kind + "_s"] = plan.total_lines, time.perf_counter() - t2
+        streamed, stats[kind + "_lines"] = _stream_report(path(suffix), kind, header.encode(enc), rec, tables, g_start, g_stop, chunk)
+        if streamed is not None:
+            stats[kind] = streamed
+        stats[kind + "_s"] = time.perf_counter() - t2
     t3 = time.perf_counter()
     with open(path(".genes_used.dat"), "w") as fh:        # write.table(gene_order, quote=FALSE, sep="\t"): row names kept
         fh.write("chr\tstart\tstop\n" + "".join(f"{g}\t{c}\t{a}\t{b}\n" for g, c, a, b in zip(genes, chrs, start64.tolist(), stop64.tolist())))
@@ -417,11 +428,59 @@ def generate_cnv_region_reports(infercnv_obj: InfercnvObject, output_filename_pr
     return _RegionList(groups, cells, rec_host, chr_names, perm, start, stop)
 
 
+def _adjust_from_records(mcmc_obj, output_filename_prefix, out_dir):
+    """adjust_genes_regions_report from the run records of mcmc_obj.table (DESIGN K25).  The parser keeps a line of the
+    step-17 files when its region NAME is one the filter kept and gives it the state of the last kept region of that name:
+    this is the same rule on (chromosome, ordinal) keys over the table the filter started from, whether or not a name is
+    unique.  False -- nothing written -- when the gene positions are not int64 integers (the device prints integers only)."""
+    import torch
+    kept = mcmc_obj.table
+    full = kept.source if kept.source is not None else kept
+    obj = mcmc_obj.infercnv_obj
+    go = obj.gene_order
+    n = np.asarray(go.chr).size
+    start64 = _int64_positions(np.asarray(go.start) if go.start is not None else np.arange(n))
+    stop64 = _int64_positions(np.asarray(go.stop) if go.stop is not None else np.arange(n))
+    if start64 is None or stop64 is None:
+        log.info("adjust_genes_regions_report: gene positions that are not int64 integers: the step-17 files are parsed")
+        return False
+    enc = locale.getpreferredencoding(False)
+    genes = np.asarray(obj.genes())
+    if full.perm is not None:
+        genes, start64, stop64 = genes[full.perm], start64[full.perm], stop64[full.perm]
+    span = int(max(full.ordinal.max(initial=0), kept.ordinal.max(initial=0))) + 1
+    key_kept, key_full = kept.chr * span + kept.ordinal, full.chr * span + full.ordinal
+    names, last = np.unique(key_kept[::-1], return_index=True)          # the last kept region of every name
+    state_of = kept.state[::-1][last]
+    pos = np.minimum(np.searchsorted(names, key_full), max(names.size - 1, 0))
+    hit = (names[pos] == key_full) if names.size else np.zeros(key_full.size, dtype=bool)
+    state = state_of[pos[hit]]
+    rec = np.stack([full.col[hit], full.chr[hit], full.gene_first[hit], full.gene_first[hit] + full.gene_count[hit] - 1,
+                    np.where(state < 0, 255, state), full.ordinal[hit]]).astype(np.int32)
+    rec = torch.from_numpy(np.ascontiguousarray(rec)).cuda()
+    tables = _report_tables([name for name, _ in full.groups] or [""], full.chr_names, genes, enc)
+    chunk = int(os.environ.get("ICNV_CNV_REPORT_CHUNK", REPORT_CHUNK))
+    os.makedirs(out_dir, exist_ok=True)
+    for kind, suffix, header in (("genes", ".pred_cnv_genes.dat", GENES_HEADER), ("regions", ".pred_cnv_regions.dat", REGIONS_HEADER)):
+        _stream_report(os.path.join(out_dir, output_filename_prefix + suffix), kind, header.encode(enc), rec, tables, start64, stop64, chunk)
+    return True
+
+
 def adjust_genes_regions_report(mcmc_obj, input_filename_prefix, output_filename_prefix, out_dir):
     """adjust_genes_regions_report (R/inferCNV_HMM.R:891-963): the step-17 reports <input prefix>.pred_cnv_genes.dat and
     .pred_cnv_regions.dat restricted to the regions the Bayesian filter kept (mcmc_obj.cell_gene), their state column
     replaced by the region's state after the filter, written under the output prefix.  Every other field passes through
-    as text."""
+    as text.  When the object carries a RegionTable (bayes_net route="table", DESIGN K25) the two files are written from its
+    records instead of being parsed back from text -- the same bytes, provided the step-17 reports were written without the
+    normal state's regions (ignore_neutral_state = the normal state, as run() writes them); gene positions that are not
+    int64 integers take the parser."""
+    if getattr(mcmc_obj, "table", None) is not None:
+        for suffix in (".pred_cnv_genes.dat", ".pred_cnv_regions.dat"):      # R stops where an input file is missing
+            src = os.path.join(out_dir, input_filename_prefix + suffix)
+            if not os.path.exists(src):
+                raise FileNotFoundError(f"Cannot find and adjust the following file. {src}")
+        if _adjust_from_records(mcmc_obj, output_filename_prefix, out_dir):
+            return
     new_state = {str(cg["cnv_regions"]): cg["State"] for cg in mcmc_obj.cell_gene}
     for suffix, name_col in ((".pred_cnv_genes.dat", "gene_region_name"), (".pred_cnv_regions.dat", "cnv_name")):
         src = os.path.join(out_dir, input_filename_prefix + suffix)

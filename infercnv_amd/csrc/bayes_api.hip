@@ -1,5 +1,6 @@
 // C ABI of K13 (include/icnv.h "Bayesian filter of the predicted CNV regions"): validation, the 64-cell tiles of the likelihood
-// pass, the LDS-resident and the streaming class of the sampler, stats.  Kernels: bayes_kernels.hip.  DESIGN.md section 4 K13.
+// pass, the LDS-resident, the streaming and the packed class (K25) of the sampler, stats.  Kernels: bayes_kernels.hip.
+// DESIGN.md section 4 K13, K25.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -15,7 +16,7 @@ using namespace icnv;
 
 namespace {
 
-std::atomic<int64_t> g_bayes[8];   // sample calls, regions, cells, undecided cells, LDS regions, streamed regions, sample us, loglik us
+std::atomic<int64_t> g_bayes[9];   // sample calls, regions, cells, undecided cells, LDS regions, streamed regions, sample us, loglik us, packed regions
 
 int check_offsets(const char *who, const int64_t *cell_off, int32_t n_regions, int32_t K) {
     if (n_regions < 1) ICNV_FAIL(ICNV_ERR_ARG, std::string(who) + ": n_regions must be >= 1");
@@ -32,6 +33,11 @@ int check_offsets(const char *who, const int64_t *cell_off, int32_t n_regions, i
 
 bool skip_decided() {   // ICNV_BAYES_DECIDED=0: every cell is sampled in every iteration (the output is the same)
     const char *e = std::getenv("ICNV_BAYES_DECIDED");
+    return !(e && *e == '0');
+}
+
+bool packed_enabled() {   // ICNV_BAYES_PACKED=0: the regions of <= 8 undecided cells take the LDS path (the output is the same)
+    const char *e = std::getenv("ICNV_BAYES_PACKED");
     return !(e && *e == '0');
 }
 
@@ -141,17 +147,19 @@ int icnv_bayes_sample_dev(const double *L, const int64_t *cell_off, const uint64
     ICNV_HIP(hipMemcpyAsync(n_und.data(), d_nund.p, (size_t)n_regions * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     ICNV_HIP(hipStreamSynchronize(s));
 
-    // two classes: the regions whose undecided cells fit LDS, and the others
-    std::vector<int32_t> list[2];
+    // three classes: the regions whose undecided cells fit LDS, the others, and the regions of a handful of undecided cells
+    std::vector<int32_t> list[3];
     int32_t lds_cells = 0;
     int64_t und_total = 0;
+    const bool packed = packed_enabled();
     for (int32_t r = 0; r < n_regions; ++r) {
         und_total += n_und[r];
-        if (n_und[r] <= BAYES_LDS_CELLS) { list[0].push_back(r); lds_cells = std::max(lds_cells, n_und[r]); }
+        if (packed && regs[r].n_cells > 0 && n_und[r] <= BAYES_PACKED_CELLS) list[2].push_back(r);
+        else if (n_und[r] <= BAYES_LDS_CELLS) { list[0].push_back(r); lds_cells = std::max(lds_cells, n_und[r]); }
         else list[1].push_back(r);
     }
-    DevBuf d_list[2];
-    for (int q = 0; q < 2; ++q) {
+    DevBuf d_list[3];
+    for (int q = 0; q < 3; ++q) {
         if (list[q].empty()) continue;
         if ((int64_t)list[q].size() * K > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "bayes_sample: too many regions");
         if ((rc = upload(d_list[q], list[q].data(), list[q].size(), s))) return rc;
@@ -159,15 +167,16 @@ int icnv_bayes_sample_dev(const double *L, const int64_t *cell_off, const uint64
         a.L = L; a.regions = d_regs.as<BayesRegion>(); a.list = d_list[q].as<int32_t>(); a.n_list = (int32_t)list[q].size(); a.K = K;
         a.n_discard = n_adapt + n_burn; a.n_keep = n_keep; a.seed = seed; a.und = d_und.as<int32_t>(); a.n_und = d_nund.as<int32_t>();
         a.nfix = d_nfix.as<int32_t>(); a.theta_sum = theta_sum; a.theta_samples = theta_samples; a.freq = freq;
-        if ((rc = launch_bayes_sample(a, q == 0 ? lds_cells : 0, s))) return rc;
+        if ((rc = q == 2 ? launch_bayes_sample_packed(a, s) : launch_bayes_sample(a, q == 0 ? lds_cells : 0, s))) return rc;
     }
     ICNV_HIP(hipStreamSynchronize(s));
     g_bayes[0] += 1;
     g_bayes[1] += n_regions;
     g_bayes[2] += rows;
     g_bayes[3] += und_total;
-    g_bayes[4] += (int64_t)list[0].size();
+    g_bayes[4] += (int64_t)list[0].size() + (int64_t)list[2].size();
     g_bayes[5] += (int64_t)list[1].size();
+    g_bayes[8] += (int64_t)list[2].size();
     g_bayes[6] += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     return ICNV_OK;
 }
@@ -194,7 +203,7 @@ int icnv_bayes_sample(const double *L, const int64_t *cell_off, const uint64_t *
 
 int icnv_bayes_stats(int64_t *out, int32_t n) {
     if (!out || n < 1) ICNV_FAIL(ICNV_ERR_ARG, "bad argument");
-    for (int i = 0; i < n && i < 8; ++i) out[i] = g_bayes[i].load();
+    for (int i = 0; i < n && i < 9; ++i) out[i] = g_bayes[i].load();
     return ICNV_OK;
 }
 

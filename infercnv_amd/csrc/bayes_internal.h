@@ -8,6 +8,7 @@ namespace icnv {
 
 constexpr int BAYES_MAX_K = 8;          // states of the mixture (i6: 6, i3: 3); more: ICNV_ERR_UNSUPPORTED
 constexpr int BAYES_LDS_CELLS = 512;    // undecided cells of a region whose L rows and counts stay in LDS; more stream from L2 / HBM
+constexpr int BAYES_PACKED_CELLS = 8;   // at most as many undecided cells (and n_cells > 0): an 8-lane group samples a (region, chain)
 constexpr int BAYES_THREADS = 256;
 
 struct BayesRegion {
@@ -50,5 +51,7 @@ int launch_bayes_prep(const double *L, const BayesRegion *regions, int32_t n_reg
                       int32_t *und, int32_t *n_und, int32_t *nfix, int32_t *freq, hipStream_t s);
 // lds_cells: 0 = stream L, else the largest n_und of the list (<= BAYES_LDS_CELLS)
 int launch_bayes_sample(const BayesSample &a, int32_t lds_cells, hipStream_t s);
+// every region of the list has n_cells > 0 and n_und <= BAYES_PACKED_CELLS
+int launch_bayes_sample_packed(const BayesSample &a, hipStream_t s);
 
 }  // namespace icnv

@@ -10,6 +10,8 @@
 //                         undecided cells go over the lanes, the only cross-lane work is the K-bin count (LDS atomics on
 //                         integers).  L rows, the cell list and the kept-state counts of a region with <= BAYES_LDS_CELLS
 //                         undecided cells stay in LDS; larger regions stream them from L2 / HBM.
+//   bayes_sample_packed_kernel   regions with <= BAYES_PACKED_CELLS undecided cells (K25, the per-cell reports): an 8-lane
+//                         group per (region, chain), eight of them in a wavefront, registers and shuffles only.
 // Every draw has its own Philox counter, so nothing depends on which lane or in which order it is taken.
 // Every value is an individually rounded IEEE-754 double operation in the documented order: -ffp-contract=off.
 #include "icnv_internal.h"
@@ -135,6 +137,30 @@ __device__ inline double bayes_gamma(double shape, uint64_t seed, uint64_t token
     return d;
 }
 
+// eps of one cell: the first k with cum[k] > u cum[K-1], else the last k with w[k] > 0, else the last with L[k] > 0, else 0
+__device__ inline int bayes_select(const double (&theta)[BAYES_MAX_K], const double *row, int K, double u) {
+    double cums[BAYES_MAX_K];
+    double cum = 0.0;
+    int last_w = -1, last_l = -1;
+#pragma unroll
+    for (int k = 0; k < BAYES_MAX_K; ++k) {
+        if (k < K) {
+            const double l = row[k];
+            const double w = theta[k] * l;
+            cum = cum + w;
+            if (w > 0.0) last_w = k;
+            if (l > 0.0) last_l = k;
+        }
+        cums[k] = cum;
+    }
+    const double thr = u * cum;
+    int sel = -1;
+#pragma unroll
+    for (int k = BAYES_MAX_K - 1; k >= 0; --k) if (k < K && cums[k] > thr) sel = k;
+    if (sel < 0) sel = last_w >= 0 ? last_w : (last_l >= 0 ? last_l : 0);
+    return sel;
+}
+
 template <bool LDS>
 __global__ void __launch_bounds__(BAYES_THREADS) bayes_sample_kernel(BayesSample a, int lds_cells) {
     extern __shared__ double dyn[];
@@ -197,25 +223,7 @@ __global__ void __launch_bounds__(BAYES_THREADS) bayes_sample_kernel(BayesSample
             const double *row = LDS ? sL + (size_t)j * K : Lg + (int64_t)i * K;
             RtPhilox ph(a.seed, reg.token, (uint64_t)i, (uint64_t)t, (uint64_t)ch << 40);
             const double u = ph.random();
-            double cums[BAYES_MAX_K];
-            double cum = 0.0;
-            int last_w = -1, last_l = -1;
-#pragma unroll
-            for (int k = 0; k < BAYES_MAX_K; ++k) {
-                if (k < K) {
-                    const double l = row[k];
-                    const double w = theta[k] * l;
-                    cum = cum + w;
-                    if (w > 0.0) last_w = k;
-                    if (l > 0.0) last_l = k;
-                }
-                cums[k] = cum;
-            }
-            const double thr = u * cum;
-            int sel = -1;
-#pragma unroll
-            for (int k = BAYES_MAX_K - 1; k >= 0; --k) if (k < K && cums[k] > thr) sel = k;
-            if (sel < 0) sel = last_w >= 0 ? last_w : (last_l >= 0 ? last_l : 0);
+            const int sel = bayes_select(theta, row, K, u);
 #pragma unroll
             for (int k = 0; k < BAYES_MAX_K; ++k) cnt[k] += sel == k;
             if (keep) {
@@ -233,6 +241,73 @@ __global__ void __launch_bounds__(BAYES_THREADS) bayes_sample_kernel(BayesSample
             const int j = q / K, k = q - j * K;
             if (sF[q]) atomicAdd(&freq[(int64_t)sI[j] * K + k], sF[q]);
         }
+    }
+}
+
+// Regions with at most BAYES_PACKED_CELLS undecided cells (K25): an 8-lane group serves one (region, chain), a wavefront eight
+// of them.  Lane k < K of the group draws gamma k and keeps n[k] and its kept-theta sum; lane j < n_und keeps undecided cell
+// j's L row and kept-state counts in registers.  The gammas go round the group by shuffles, n[k] is nfix[k] plus the group's
+// part of a ballot: no LDS, no barrier, no atomic in the loop.  Every value is the one bayes_sample_kernel computes.
+__global__ void __launch_bounds__(BAYES_THREADS) bayes_sample_packed_kernel(BayesSample a) {
+    const int K = a.K;
+    const int64_t pair = (int64_t)blockIdx.x * (BAYES_THREADS / BAYES_PACKED_CELLS) + threadIdx.x / BAYES_PACKED_CELLS;
+    if (pair >= (int64_t)a.n_list * K) return;            // whole groups leave; the groups of a wavefront never read each other
+    const int r = a.list[pair / K], ch = (int)(pair % K);
+    const BayesRegion reg = a.regions[r];
+    const int lane = threadIdx.x & (BAYES_PACKED_CELLS - 1);
+    const int shift = (threadIdx.x & 63) & ~(BAYES_PACKED_CELLS - 1);   // the group's first lane in its wavefront
+    const int nu = min(a.n_und[r], BAYES_PACKED_CELLS);
+    const bool has_cell = lane < nu;
+    const int i = has_cell ? a.und[reg.row0 + lane] : 0;
+    double row[BAYES_MAX_K];
+#pragma unroll
+    for (int k = 0; k < BAYES_MAX_K; ++k) row[k] = (has_cell && k < K) ? a.L[(reg.row0 + i) * K + k] : 0.0;
+    const int nfix = lane < K ? a.nfix[r * BAYES_MAX_K + lane] : 0;
+    int n = (lane < K && lane == ch) ? reg.n_cells : 0;   // the chain starts from eps == ch
+    int fr[BAYES_MAX_K];
+#pragma unroll
+    for (int k = 0; k < BAYES_MAX_K; ++k) fr[k] = 0;
+    double *samp = a.theta_samples ? a.theta_samples + ((int64_t)r * K + ch) * (int64_t)a.n_keep * K : nullptr;
+    double tsum = 0.0;
+    const int64_t T = (int64_t)a.n_discard + a.n_keep;
+    for (int64_t t = 0; t < T; ++t) {
+        double g = 0.0;
+        if (lane < K) g = bayes_gamma(1.0 + (double)n, a.seed, reg.token, lane, t, ch);
+        double gk[BAYES_MAX_K];
+        double S = 0.0;
+#pragma unroll
+        for (int k = 0; k < BAYES_MAX_K; ++k) {
+            gk[k] = __shfl(g, k, BAYES_PACKED_CELLS);
+            if (k < K) S = S + gk[k];
+        }
+        double theta[BAYES_MAX_K];
+#pragma unroll
+        for (int k = 0; k < BAYES_MAX_K; ++k) theta[k] = k < K ? gk[k] / S : 0.0;
+        const bool keep = t >= a.n_discard;
+        if (keep && lane < K) {
+            const double th = g / S;
+            tsum = tsum + th;
+            if (samp) samp[(t - a.n_discard) * K + lane] = th;
+        }
+        int sel = -1;
+        if (has_cell) {
+            RtPhilox ph(a.seed, reg.token, (uint64_t)i, (uint64_t)t, (uint64_t)ch << 40);
+            const double u = ph.random();
+            sel = bayes_select(theta, row, K, u);
+        }
+        n = nfix;
+#pragma unroll
+        for (int k = 0; k < BAYES_MAX_K; ++k) {
+            const unsigned long long m = __ballot(sel == k);
+            if (lane == k) n += __popcll((m >> shift) & ((1ull << BAYES_PACKED_CELLS) - 1ull));
+            fr[k] += (keep && sel == k) ? 1 : 0;
+        }
+    }
+    if (lane < K) a.theta_sum[((int64_t)r * K + ch) * K + lane] = tsum;
+    if (has_cell) {
+#pragma unroll
+        for (int k = 0; k < BAYES_MAX_K; ++k)
+            if (k < K && fr[k]) atomicAdd(&a.freq[(reg.row0 + i) * K + k], fr[k]);   // the region's K chains meet here
     }
 }
 
@@ -268,6 +343,17 @@ int launch_bayes_sample(const BayesSample &a, int32_t lds_cells, hipStream_t s) 
     } else {
         hipLaunchKernelGGL(bayes_sample_kernel<false>, grid, dim3(BAYES_THREADS), 0, s, a, 0);
     }
+    BAYES_LAUNCH_CHECK();
+    return ICNV_OK;
+}
+
+int launch_bayes_sample_packed(const BayesSample &a, hipStream_t s) {
+    static_assert(BAYES_PACKED_CELLS == BAYES_MAX_K && 64 % BAYES_PACKED_CELLS == 0, "a group's lanes hold the K gammas and the cells");
+    if (a.n_list <= 0) return ICNV_OK;
+    KernelTimer kt("bayes_sample_packed", s);
+    const int64_t per_block = BAYES_THREADS / BAYES_PACKED_CELLS;
+    const int64_t blocks = ((int64_t)a.n_list * a.K + per_block - 1) / per_block;
+    hipLaunchKernelGGL(bayes_sample_packed_kernel, dim3((unsigned)blocks), dim3(BAYES_THREADS), 0, s, a);
     BAYES_LAUNCH_CHECK();
     return ICNV_OK;
 }

@@ -1481,6 +1481,32 @@ def bayes_loglik(x, regions, mu, tau):
     return ll, Lk, off
 
 
+def bayes_loglik_arrays(x, gene_start, gene_count, cell_idx, cell_off, mu, tau):
+    """bayes_loglik for regions that already are arrays (the table route of bayes_net, DESIGN K25): gene_start, gene_count
+    (one per region), cell_idx (the concatenated cell columns) and cell_off (int64, regions + 1) go to the same C entry
+    without a Python object per region.  Returns (ll, L, cell_off as the int64 array the sampler takes)."""
+    L_ = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    K = len(mu)
+    g0, g0p = i32(gene_start)
+    ng, ngp = i32(gene_count)
+    off = np.ascontiguousarray(cell_off, dtype=np.int64)
+    if g0.ndim != 1 or ng.shape != g0.shape or off.shape != (g0.size + 1,):
+        raise ValueError("one gene_start and gene_count per region, and regions + 1 offsets")
+    cidx = np.ascontiguousarray(cell_idx, dtype=np.int32).ravel()
+    if off.size and int(off[-1]) != cidx.size:
+        raise ValueError("cell_off does not match cell_idx")
+    cidx, cp = i32(cidx if cidx.size else np.zeros(1, dtype=np.int32))
+    m, mp = f64(mu)
+    t, tp = f64(tau)
+    rows = int(off[-1])
+    ll = torch.empty((rows, K), dtype=torch.float64, device=x.device)
+    Lk = torch.empty_like(ll)
+    check(L_.icnv_bayes_loglik_dev(_ptr(x), G, C, ld, g0p, ngp, cp, off.ctypes.data_as(ct.POINTER(ct.c_int64)), g0.size, K, mp, tp,
+                                   _ptr(ll), _ptr(Lk), _stream()))
+    return ll, Lk, off
+
+
 def bayes_sample(L, cell_off, tokens, n_adapt=500, n_burn=200, n_keep=1000, seed=0, want_samples=False):
     """The Gibbs sampler of every region's mixture model in one call (icnv_bayes_sample_dev, DESIGN K13): K chains per region,
     n_adapt + n_burn discarded and n_keep kept iterations.  L, cell_off: as bayes_loglik returns them; tokens: one uint64
@@ -1507,7 +1533,7 @@ def bayes_sample(L, cell_off, tokens, n_adapt=500, n_burn=200, n_keep=1000, seed
     return theta_sum, samples, freq
 
 
-BAYES_STATS = ("calls", "regions", "rows", "undecided_rows", "regions_lds", "regions_streamed", "us", "loglik_us")
+BAYES_STATS = ("calls", "regions", "rows", "undecided_rows", "regions_lds", "regions_streamed", "us", "loglik_us", "regions_packed")
 
 
 def bayes_stats(reset=False):
@@ -1518,6 +1544,36 @@ def bayes_stats(reset=False):
     if reset:
         L.icnv_bayes_stats_reset()
     return dict(zip(BAYES_STATS, (int(v) for v in out)))
+
+
+def fill_regions(states, gene_first, gene_count, cell_off, cell_idx, value):
+    """The rectangle rewrite of the Bayesian filter in one launch (icnv_state_fill_regions_dev, DESIGN K25), IN PLACE: states
+    (C, G) uint8 CUDA tensor, rows `ld` apart; region r = the genes gene_first[r] .. + gene_count[r] - 1 of the cells
+    cell_idx[cell_off[r] : cell_off[r + 1]] becomes value[r], 0 leaves it alone.  The region arrays are CUDA tensors (int32,
+    int32, int64, int32, uint8) or anything numpy converts, which is uploaded.  The rectangles must be disjoint.  ValueError
+    (states untouched) when an index is out of range."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(states, torch.uint8)
+
+    def dev(a, dtype):
+        if isinstance(a, torch.Tensor):
+            if not (a.is_cuda and a.dtype == dtype and a.dim() == 1 and a.is_contiguous()):
+                raise TypeError(f"region arrays must be contiguous one-dimensional CUDA tensors ({dtype})")
+            return a
+        np_dtype = {torch.int32: np.int32, torch.int64: np.int64, torch.uint8: np.uint8}[dtype]
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype).ravel()).to(states.device)
+
+    g0, ng, off = dev(gene_first, torch.int32), dev(gene_count, torch.int32), dev(cell_off, torch.int64)
+    idx, val = dev(cell_idx, torch.int32), dev(value, torch.uint8)
+    n = int(g0.numel())
+    if ng.numel() != n or val.numel() != n or off.numel() != n + 1:
+        raise ValueError("one gene_first, gene_count and value per region, and regions + 1 offsets")
+    rc = L.icnv_state_fill_regions_dev(_ptr(states), G, C, ld, n, _ptr(g0), _ptr(ng), _ptr(off), _ptr(idx) if idx.numel() else None,
+                                       int(idx.numel()), _ptr(val), _stream())
+    if rc == _lib.ERR_ARG:
+        raise ValueError(L.icnv_last_error().decode("utf-8", "replace"))
+    check(rc)
+    return states
 
 
 def state_consensus(states, groups, overwrite=False):

@@ -530,7 +530,8 @@ def run(infercnv_obj: InfercnvObject,
         log.info("STEP %02d: Run Bayesian Network Model on HMM predicted CNVs", step)
         mcmc_obj = bayes_net.inferCNVBayesNet(obj, hmm_obj.expr_data, HMM_type=HMM_type, by=HMM_report_by,
                                               postMcmcMethod="removeCNV", reassignCNVs=reassignCNVs,
-                                              out_dir=os.path.join(out_dir, tokens["bayes_dir"]), seed=seed)
+                                              out_dir=os.path.join(out_dir, tokens["bayes_dir"]), seed=seed,
+                                              route="table" if HMM_report_by == "cell" else "dict")
         done(step, "Run Bayesian Network Model on HMM predicted CNVs", mcmc_obj)
 
     if up_to_step == step:
