@@ -1228,6 +1228,57 @@ int icnv_csc_select_dev(const icnv_counts *cnt, int64_t G, int64_t C, const int3
                         const int32_t *cells_dev, int64_t n_cells, int64_t *colptr_out, int32_t *rowidx_out, int32_t *vals_out,
                         int64_t capacity, int64_t *nnz_out, void *stream);
 
+/* ---- reading a selection of columns (K26) -------------------------------------------------------------------------------------
+ * The two chunk parsers above for a caller that wants some of the file's columns only: a rank of the cell-sharded route that
+ * reads its own cells, or an annotation file that names a subset.  DESIGN.md section 4 K26, restated in
+ * tests/read_select_restate.py.  Device entries only; not bound in the R shim.
+ *
+ * The column map, in both entries: col_map_dev [n_cols] (DEVICE, int32) gives the output column of every numeric file column
+ * (dense) or matrix column (triplets), or -1 to skip it; n_cols_out is 1 .. n_cols.  The map is checked on the device before
+ * any other pass: every entry must lie in -1 .. n_cols_out - 1 and every output column must be hit exactly once.  Otherwise
+ * the call returns ICNV_ERR_ARG and the message names the first offending entry: the first entry out of range; else the first
+ * entry that names an output column a second time; else the first output column that no entry hits.  Timer name:
+ * "col_map_check".
+ *
+ * icnv_parse_table_cols_dev: icnv_parse_table_dev with the map.  Row i of the chunk, file column c with col_map[c] = k >= 0
+ * goes to out[k * ld + row0 + i]; `out` has n_cols_out columns.  n_cols stays the FILE's column count.
+ *   What sees the whole chunk: the structure pass, the rows' starts and the rows' checks.  A ragged row (counted against
+ *   n_cols + 1), a bad label or a bad separator is refused exactly as icnv_parse_table_dev refuses it, with the same message,
+ *   line and field number, whatever is selected.
+ *   What sees the selected columns only: everything else.  FIELDS OF SKIPPED COLUMNS ARE NOT EXAMINED: no lane converts them,
+ *   they never reach the host's strtod, they do not count in icnv_table_parse_stats slots 2 and 3 (slot 2 grows by rows *
+ *   n_cols_out), and a byte outside the number grammar in a skipped column is NOT reported by this call.  Over a deal in which
+ *   every column has exactly one owner, every field of the file is still examined once.
+ *   A refusal in a selected column reads exactly as the plain entry's: the file's line and the file's field number (not the
+ *   output column), under the prefix "parse_table: ".
+ *   The staged positions and values, the uncertified-field rounds and the transpose are n_cols_out wide: no device allocation
+ *   of the call grows with n_cols * rows (there is no list of all field starts; the per-segment counts grow with the bytes
+ *   / 4096, the rows' arrays with the rows, the map's inverse with n_cols_out).
+ *   Every other rule is icnv_parse_table_dev's: the grammar, the values (strtod, bit for bit), label_ranges, *n_rows, the
+ *   ICNV_ERR_ARG cases before any launch, and on any error out, label_ranges and *n_rows are left as they were.  The identity
+ *   map gives icnv_parse_table_dev's output bit for bit.  Synchronises.
+ *   Timer names: "table_parse_structure", "table_cols_index" (rows' starts, selected field starts), "table_cols_rows" (the
+ *   rows' checks), "table_cols_fields", "table_cols_collect", "table_parse_transpose". */
+int icnv_parse_table_cols_dev(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols,
+                              int64_t line0, double *out, int64_t ld, int64_t row0, int64_t max_rows, int64_t *label_ranges,
+                              int64_t *n_rows, const int32_t *col_map_dev, int64_t n_cols_out, void *stream);
+/* icnv_parse_triplets_cols_dev: icnv_parse_triplets_dev with the map.  EVERY entry of the chunk is parsed and validated in
+ * full, as there: its fields have to be read to learn its column, the value grammar is integer-only and there is no host
+ * fallback -- so a refusal anywhere, in a skipped column too, reads the same on every rank ("parse_triplets: line L, field
+ * K: ...").  Then the entries whose column maps to -1 are dropped and the kept ones are stored in FILE ORDER -- a stable
+ * compaction -- with the column replaced by col_map[col].
+ *   *n_entries (HOST)  the kept entries;  *n_seen (HOST)  the entries of the chunk (what icnv_parse_triplets_dev counts).
+ *   capacity bounds the KEPT entries: with more, ICNV_ERR_ARG "parse_triplets_cols: N entries are kept, capacity is M" and
+ *   nothing is written (the caller may grow its arrays to N and call again).  An output column need not receive an entry.
+ *   On any error the three arrays, *n_entries and *n_seen are left as they were.  Synchronises.
+ * Method: K22's structure, index and parse passes into staged arrays; then the kept entries of every tile of 2048 staged
+ *   entries are counted by ballot, the counts scanned by one workgroup, and entry k is stored behind the kept entries of the
+ *   tiles before its tile and of the steps, wavefronts and lanes before it inside the tile.  No atomics besides K22's error word; the result does not depend on the launch
+ *   shape.  Timer names: "triplets_structure", "triplets_index", "triplets_parse", "triplets_keep_count", "triplets_keep_fill". */
+int icnv_parse_triplets_cols_dev(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, int32_t field, int64_t n_rows,
+                                 int64_t n_cols, int64_t line0, int32_t *row_dev, int32_t *col_dev, int32_t *val_dev, int64_t capacity,
+                                 int64_t *n_entries, const int32_t *col_map_dev, int64_t n_cols_out, int64_t *n_seen, void *stream);
+
 /* ---- CNV region reports (K24) -----------------------------------------------------------------------------------------------
  * The bodies of `<prefix>.pred_cnv_genes.dat` and `<prefix>.pred_cnv_regions.dat`, which generate_cnv_region_reports writes
  * with write.table(quote = FALSE, sep = "\t") (R/inferCNV_HMM.R:790-869).  The byte-level yardstick is the host writer kept in

@@ -208,6 +208,8 @@ PROTOTYPES = {
     "icnv_matrix_sum_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _dp, _vp]),
     "icnv_matrix_sum": (ct.c_int, [_vp, _i64, _i64, _i64, _dp]),
     "icnv_parse_triplets_dev": (ct.c_int, [_vp, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64p, _vp]),
+    "icnv_parse_table_cols_dev": (ct.c_int, [_vp, _vp, _i64, ct.c_char_p, _i64, _i64, _vp, _i64, _i64, _i64, _i64p, _i64p, _vp, _i64, _vp]),
+    "icnv_parse_triplets_cols_dev": (ct.c_int, [_vp, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64p, _vp, _i64, _i64p, _vp]),
     "icnv_csc_from_sorted_triplets_dev": (ct.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64p, ct.POINTER(ct.c_int32), _vp]),
     "icnv_csc_select_dev": (ct.c_int, [ct.POINTER(Counts), _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64p, _vp]),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),

@@ -8,42 +8,6 @@
 
 using namespace icnv;
 
-namespace {
-
-// "line L, field K: <what>: '<bytes>'" for the error word of a refused chunk, read from the host copy of the text with the
-// grammar the kernel read it with.  SC_E_FIELDS and SC_E_COMMENT are reported at the line's first byte, K the line's number
-// of fields (1 for a comment) and the bytes the line's; the others at the field's first byte.
-std::string sc_describe(const uint8_t *text, int64_t n, uint64_t word, int field, int64_t G, int64_t C, int64_t line0) {
-    const int64_t offset = (int64_t)(word >> 8);
-    const int code = (int)(word & 0xff);
-    int64_t line = line0, start = 0;
-    for (int64_t i = 0; i < offset && i < n; ++i)
-        if (text[i] == '\n') { ++line; start = i + 1; }
-    int64_t k = 0, tokens = 0, b = offset, e = offset;
-    for (int64_t q = sc_skip_blanks(text, n, start); !tp_at_line_end(text, n, q);) {
-        const int64_t te = sc_token_end(text, n, q);
-        ++tokens;
-        if (q == offset) { k = tokens; e = te; }
-        q = sc_skip_blanks(text, n, te);
-    }
-    std::string what;
-    if (code == SC_E_FIELDS || code == SC_E_COMMENT) {
-        k = code == SC_E_COMMENT ? 1 : tokens;
-        b = start;
-        for (e = start; !tp_at_line_end(text, n, e);) ++e;
-        what = code == SC_E_COMMENT ? "a comment line inside the body"
-                                    : std::to_string(tokens) + " fields where " + std::to_string(field == SC_MM_PATTERN ? 2 : 3) + " are expected";
-    } else if (code == SC_E_INDEX) {
-        what = "not an index in 1 .. " + std::to_string(k == 1 ? G : C);
-    } else {
-        what = "not an integer count in 0 .. 2147483647";
-    }
-    const std::string bytes(reinterpret_cast<const char *>(text + b), (size_t)((e - b) < 60 ? (e - b) : 60));
-    return "line " + std::to_string(line) + ", field " + std::to_string(k) + ": " + what + ": '" + bytes + "'";
-}
-
-}  // namespace
-
 extern "C" {
 
 int icnv_parse_triplets_dev(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, int32_t field, int64_t n_rows, int64_t n_cols,

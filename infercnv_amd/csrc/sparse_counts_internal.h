@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string>
 
 #include "table_parse_num.h"
 
@@ -15,6 +16,8 @@ constexpr int SC_BYTES = 16;               // text positions of one lane of the 
 constexpr int SC_SEG = SC_NT * SC_BYTES;   // text positions of one workgroup: a segment
 constexpr int SC_SCAN_ITEMS = 8;           // counts of one lane of the selector's column scan
 constexpr int SC_SCAN_TILE = SC_NT * SC_SCAN_ITEMS;
+constexpr int SC_KEEP_STEPS = 8;           // steps of SC_NT staged entries one workgroup of the K26 compaction looks at
+constexpr int SC_KEEP_TILE = SC_NT * SC_KEEP_STEPS;
 constexpr uint64_t SC_NO_ERROR = ~0ull;
 constexpr unsigned long long SC_NO_VIOLATION = ~0ull;
 
@@ -127,6 +130,39 @@ TP_HD inline int sc_parse_line(const uint8_t *text, int64_t n, int64_t p, int fi
     return 0;
 }
 
+// (host) the text of a refusal of the triplet parsers
+// "line L, field K: <what>: '<bytes>'" for the error word of a refused chunk, read from the host copy of the text with the
+// grammar the kernel read it with.  SC_E_FIELDS and SC_E_COMMENT are reported at the line's first byte, K the line's number
+// of fields (1 for a comment) and the bytes the line's; the others at the field's first byte.
+inline std::string sc_describe(const uint8_t *text, int64_t n, uint64_t word, int field, int64_t G, int64_t C, int64_t line0) {
+    const int64_t offset = (int64_t)(word >> 8);
+    const int code = (int)(word & 0xff);
+    int64_t line = line0, start = 0;
+    for (int64_t i = 0; i < offset && i < n; ++i)
+        if (text[i] == '\n') { ++line; start = i + 1; }
+    int64_t k = 0, tokens = 0, b = offset, e = offset;
+    for (int64_t q = sc_skip_blanks(text, n, start); !tp_at_line_end(text, n, q);) {
+        const int64_t te = sc_token_end(text, n, q);
+        ++tokens;
+        if (q == offset) { k = tokens; e = te; }
+        q = sc_skip_blanks(text, n, te);
+    }
+    std::string what;
+    if (code == SC_E_FIELDS || code == SC_E_COMMENT) {
+        k = code == SC_E_COMMENT ? 1 : tokens;
+        b = start;
+        for (e = start; !tp_at_line_end(text, n, e);) ++e;
+        what = code == SC_E_COMMENT ? "a comment line inside the body"
+                                    : std::to_string(tokens) + " fields where " + std::to_string(field == SC_MM_PATTERN ? 2 : 3) + " are expected";
+    } else if (code == SC_E_INDEX) {
+        what = "not an index in 1 .. " + std::to_string(k == 1 ? G : C);
+    } else {
+        what = "not an integer count in 0 .. 2147483647";
+    }
+    const std::string bytes(reinterpret_cast<const char *>(text + b), (size_t)((e - b) < 60 ? (e - b) : 60));
+    return "line " + std::to_string(line) + ", field " + std::to_string(k) + ": " + what + ": '" + bytes + "'";
+}
+
 struct ScParseArgs {
     const uint8_t *text;                   // device, 16-byte aligned, n bytes
     int64_t n;                             // 1 .. 2^31 - 2
@@ -165,5 +201,18 @@ int launch_sc_build(const int32_t *row, const int32_t *col, int64_t nnz, int64_t
 int launch_sc_check_maps(const ScSelectArgs &a, hipStream_t s);
 int launch_sc_select_count(const ScSelectArgs &a, hipStream_t s);   // counts, colptr_out
 int launch_sc_select_fill(const ScSelectArgs &a, hipStream_t s);
+
+// K26, the column-selected triplet parser (triplets_cols_kernels.hip): the stable compaction of the staged entries
+struct ScKeepArgs {
+    const int32_t *row, *col, *val;        // [n_entries] staged by launch_sc_parse
+    int64_t n_entries;
+    const int32_t *col_map;                // [C] output column or -1
+    int64_t C;
+    uint32_t *block_count, *block_off;     // [tiles of SC_KEEP_TILE entries] kept entries, their exclusive scan
+    uint32_t *total;                       // [1]
+    int32_t *row_out, *col_out, *val_out;  // the caller's arrays
+};
+int launch_sc_keep_count(const ScKeepArgs &a, hipStream_t s);   // block_count, block_off, total
+int launch_sc_keep_fill(const ScKeepArgs &a, hipStream_t s);
 
 }  // namespace icnv

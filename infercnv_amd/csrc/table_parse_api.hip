@@ -36,6 +36,27 @@ int tp_refused(const uint8_t *text_host, int64_t n, uint64_t word, uint8_t sep, 
 
 }  // namespace
 
+// the same checks, refusal text and counters for the column-selected entry (table_cols_api.hip, K26)
+namespace icnv {
+
+int tp_check_args(const void *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0, const void *out,
+                  int64_t ld, int64_t row0, int64_t max_rows, const int64_t *label_ranges, const int64_t *n_rows) {
+    int rc;
+    if ((rc = tp_validate(text_dev, text_host, n_bytes, sep, n_cols, line0, out, ld, row0, max_rows, label_ranges, n_rows))) return rc;
+    if (reinterpret_cast<uintptr_t>(text_dev) & 15) ICNV_FAIL(ICNV_ERR_ARG, "parse_table: the device text must start on a 16-byte boundary");
+    return ICNV_OK;
+}
+
+int tp_refusal(const uint8_t *text_host, int64_t n, uint64_t word, uint8_t sep, int64_t line0, int64_t n_cols) {
+    return tp_refused(text_host, n, word, sep, line0, n_cols);
+}
+
+void tp_count_call(int64_t rows, int64_t fields, int64_t host_fields, int64_t bytes, int64_t rounds, int64_t us) {
+    g_tp[0] += 1; g_tp[1] += rows; g_tp[2] += fields; g_tp[3] += host_fields; g_tp[4] += bytes; g_tp[5] += rounds; g_tp[6] += us;
+}
+
+}  // namespace icnv
+
 extern "C" {
 
 int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0,

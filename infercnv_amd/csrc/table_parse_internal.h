@@ -47,12 +47,86 @@ struct TpArgs {
     int64_t ld, row0;
 };
 
+// ---- device helpers shared by table_parse_kernels.hip and table_cols_kernels.hip ----------------------------------------
+// Position p of the text (0 .. n; n is a position because a last line without '\n' may end in a separator) is
+//   a row start    when it begins a line (p == 0 or text[p - 1] == '\n') that is not blank (tp_at_line_end(p) is false);
+//   a field start  when it is a row start or text[p - 1] is the separator.
+// A lane looks at TP_BYTES positions from `base`: b[k] is the byte at base - 1 + k, '\n' on either side of the text, which
+// makes position 0 a line start and keeps every position beyond n from being anything.  Bit j of the masks is position base + j.
+__device__ inline void tp_masks(const TpArgs &a, int64_t base, uint32_t &rows, uint32_t &fields) {
+    uint8_t b[TP_BYTES + 2];
+    b[0] = (base > 0 && base - 1 < a.n) ? a.text[base - 1] : (uint8_t)'\n';
+    if (base + TP_BYTES <= a.n) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(a.text + base);
+        const uint32_t word[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < TP_BYTES; ++j) b[1 + j] = (uint8_t)(word[j >> 2] >> (8 * (j & 3)));
+    } else {
+#pragma unroll
+        for (int j = 0; j < TP_BYTES; ++j) b[1 + j] = base + j < a.n ? a.text[base + j] : (uint8_t)'\n';
+    }
+    b[TP_BYTES + 1] = base + TP_BYTES < a.n ? a.text[base + TP_BYTES] : (uint8_t)'\n';
+    rows = 0;
+    fields = 0;
+#pragma unroll
+    for (int j = 0; j < TP_BYTES; ++j) {
+        const int k = j + 1;
+        const bool line_start = b[k - 1] == '\n';
+        const bool line_end = b[k] == '\n' || (b[k] == '\r' && b[k + 1] == '\n');
+        const bool row = line_start && !line_end;
+        rows |= (uint32_t)row << j;
+        fields |= (uint32_t)(row || b[k - 1] == a.sep) << j;
+    }
+}
+
+__device__ inline uint32_t tp_packed_counts(uint32_t rows, uint32_t fields) { return ((uint32_t)__popc(rows) << 16) | (uint32_t)__popc(fields); }
+
+// Inclusive scan of one word per lane over the workgroup (s_scan: TP_NT words).
+__device__ inline uint32_t tp_block_scan(uint32_t v, uint32_t *s_scan) {
+    const int tid = threadIdx.x;
+    s_scan[tid] = v;
+    __syncthreads();
+    for (int d = 1; d < TP_NT; d <<= 1) {
+        const uint32_t add = tid >= d ? s_scan[tid - d] : 0u;
+        __syncthreads();
+        s_scan[tid] += add;
+        __syncthreads();
+    }
+    return s_scan[tid];
+}
+
+__device__ inline void tp_refuse(const TpArgs &a, int64_t offset, int code) {
+    atomicMin(a.error, ((unsigned long long)offset << 8) | (unsigned long long)code);
+}
+
+__device__ inline void tp_flag(const TpArgs &a, int64_t slot, int64_t pos) {
+    const uint32_t t = atomicAdd(a.n_flagged, 1u);
+    if (t < (uint32_t)TP_FLAG_CAP) a.flagged[t] = TpFlagged{slot, pos};
+}
+
 int launch_tp_structure(const TpArgs &a, hipStream_t s);     // seg_count, the scans, totals
 int launch_tp_index(const TpArgs &a, hipStream_t s);         // field_pos, field_row, row_pos, row_field0; then the rows' checks and label ranges
+int launch_tp_rows(const TpArgs &a, hipStream_t s);          // the rows' checks and label ranges alone (K26: needs row_pos, row_field0 only)
 int launch_tp_parse(const TpArgs &a, hipStream_t s);
 int launch_tp_collect(const TpArgs &a, hipStream_t s);
 int launch_tp_patch(const TpArgs &a, const int64_t *slot, const uint64_t *bits, int32_t n, hipStream_t s);
 int launch_tp_transpose(const TpArgs &a, hipStream_t s);
+// K26, the column-selected entry: its launches (table_cols_kernels.hip) and what it shares with table_parse_api.hip
+struct TcArgs {
+    TpArgs tp;                             // n_cols: the file's; vals: [n_rows * n_cols_out], row r, output column k at r * n_cols_out + k
+    const int32_t *col_map;                // [tp.n_cols] output column of a file column, or -1
+    int64_t n_cols_out;
+    uint32_t *sel_pos;                     // [n_rows * n_cols_out] first byte of the field staged at that slot; TC_ABSENT: a ragged row lacks it
+};
+constexpr uint32_t TC_ABSENT = 0xffffffffu;
+int launch_tc_index(const TcArgs &a, hipStream_t s);         // row_pos, row_field0; the rows' checks; sel_pos
+int launch_tc_parse(const TcArgs &a, hipStream_t s);
+int launch_tc_collect(const TcArgs &a, hipStream_t s);
+int tp_check_args(const void *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0, const void *out,
+                  int64_t ld, int64_t row0, int64_t max_rows, const int64_t *label_ranges, const int64_t *n_rows);
+int tp_refusal(const uint8_t *text_host, int64_t n, uint64_t word, uint8_t sep, int64_t line0, int64_t n_cols);   // sets the message, returns ICNV_ERR_ARG
+void tp_count_call(int64_t rows, int64_t fields, int64_t host_fields, int64_t bytes, int64_t rounds, int64_t us);   // icnv_table_parse_stats
+
 int launch_gather_matrix(const double *in, int64_t ld_in, const int32_t *genes, int64_t n_genes, const int32_t *cells, int64_t n_cells,
                          double *out, int64_t ld_out, hipStream_t s);
 

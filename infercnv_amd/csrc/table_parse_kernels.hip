@@ -10,54 +10,7 @@ namespace icnv {
 
 namespace {
 
-// ---- structure ------------------------------------------------------------------------------------------------------------
-// Position p of the text (0 .. n; n is a position because a last line without '\n' may end in a separator) is
-//   a row start    when it begins a line (p == 0 or text[p - 1] == '\n') that is not blank (tp_at_line_end(p) is false);
-//   a field start  when it is a row start or text[p - 1] is the separator.
-// A lane looks at TP_BYTES positions from `base`: b[k] is the byte at base - 1 + k, '\n' on either side of the text, which
-// makes position 0 a line start and keeps every position beyond n from being anything.  Bit j of the masks is position base + j.
-__device__ inline void tp_masks(const TpArgs &a, int64_t base, uint32_t &rows, uint32_t &fields) {
-    uint8_t b[TP_BYTES + 2];
-    b[0] = (base > 0 && base - 1 < a.n) ? a.text[base - 1] : (uint8_t)'\n';
-    if (base + TP_BYTES <= a.n) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(a.text + base);
-        const uint32_t word[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < TP_BYTES; ++j) b[1 + j] = (uint8_t)(word[j >> 2] >> (8 * (j & 3)));
-    } else {
-#pragma unroll
-        for (int j = 0; j < TP_BYTES; ++j) b[1 + j] = base + j < a.n ? a.text[base + j] : (uint8_t)'\n';
-    }
-    b[TP_BYTES + 1] = base + TP_BYTES < a.n ? a.text[base + TP_BYTES] : (uint8_t)'\n';
-    rows = 0;
-    fields = 0;
-#pragma unroll
-    for (int j = 0; j < TP_BYTES; ++j) {
-        const int k = j + 1;
-        const bool line_start = b[k - 1] == '\n';
-        const bool line_end = b[k] == '\n' || (b[k] == '\r' && b[k + 1] == '\n');
-        const bool row = line_start && !line_end;
-        rows |= (uint32_t)row << j;
-        fields |= (uint32_t)(row || b[k - 1] == a.sep) << j;
-    }
-}
-
-__device__ inline uint32_t tp_packed_counts(uint32_t rows, uint32_t fields) { return ((uint32_t)__popc(rows) << 16) | (uint32_t)__popc(fields); }
-
-// Inclusive scan of one word per lane over the workgroup (s_scan: TP_NT words).
-__device__ inline uint32_t tp_block_scan(uint32_t v, uint32_t *s_scan) {
-    const int tid = threadIdx.x;
-    s_scan[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < TP_NT; d <<= 1) {
-        const uint32_t add = tid >= d ? s_scan[tid - d] : 0u;
-        __syncthreads();
-        s_scan[tid] += add;
-        __syncthreads();
-    }
-    return s_scan[tid];
-}
-
+// ---- structure (tp_masks, tp_block_scan: table_parse_internal.h) ---------------------------------------------------------
 __global__ __launch_bounds__(TP_NT) void tp_count_kernel(TpArgs a) {
     __shared__ uint32_t s_part[TP_NT / 64];
     uint32_t rows, fields;
@@ -119,10 +72,6 @@ __global__ __launch_bounds__(TP_NT) void tp_index_kernel(TpArgs a) {
     }
 }
 
-__device__ inline void tp_refuse(const TpArgs &a, int64_t offset, int code) {
-    atomicMin(a.error, ((unsigned long long)offset << 8) | (unsigned long long)code);
-}
-
 // One lane per row: the field count, the label's range and its quotes.
 __global__ __launch_bounds__(TP_NT) void tp_rows_kernel(TpArgs a) {
     const int64_t r = (int64_t)blockIdx.x * TP_NT + threadIdx.x;
@@ -141,11 +90,6 @@ __global__ __launch_bounds__(TP_NT) void tp_rows_kernel(TpArgs a) {
 }
 
 // ---- parse ----------------------------------------------------------------------------------------------------------------
-__device__ inline void tp_flag(const TpArgs &a, int64_t slot, int64_t pos) {
-    const uint32_t t = atomicAdd(a.n_flagged, 1u);
-    if (t < (uint32_t)TP_FLAG_CAP) a.flagged[t] = TpFlagged{slot, pos};
-}
-
 // One lane per field start.  The label (field 0) and the fields of a ragged row beyond n_cols are left alone; the rows pass
 // refuses such a chunk.  The values are staged in file order: row r, column c at vals[r * n_cols + c].
 __global__ __launch_bounds__(TP_NT) void tp_parse_kernel(TpArgs a) {
@@ -242,6 +186,16 @@ int launch_tp_index(const TpArgs &a, hipStream_t s) {
     if ((rc = tp_grid(a.n_seg, grid))) return rc;
     hipLaunchKernelGGL(tp_index_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
     ICNV_HIP(hipGetLastError());
+    if ((rc = tp_grid((a.n_rows + TP_NT - 1) / TP_NT, grid))) return rc;
+    hipLaunchKernelGGL(tp_rows_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_tp_rows(const TpArgs &a, hipStream_t s) {
+    KernelTimer kt("table_cols_rows", s);
+    unsigned grid;
+    int rc;
     if ((rc = tp_grid((a.n_rows + TP_NT - 1) / TP_NT, grid))) return rc;
     hipLaunchKernelGGL(tp_rows_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
     ICNV_HIP(hipGetLastError());

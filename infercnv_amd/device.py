@@ -448,6 +448,64 @@ def parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, lin
     return int(n_rows.value), ranges[:int(n_rows.value)]
 
 
+def _selected_columns(cells, who):
+    """The `cells` argument of read_table / read_mtx as an int64 array: 0-based file columns, any order, no repeats."""
+    sel = np.asarray(cells)
+    if sel.ndim != 1 or sel.size == 0:
+        raise ValueError(f"{who}: cells must be a non-empty list of columns")
+    if not np.issubdtype(sel.dtype, np.integer):
+        raise ValueError(f"{who}: cells must be integers")
+    sel = sel.astype(np.int64)
+    if sel.min() < 0:
+        raise ValueError(f"{who}: cells entry {int(sel.min())} is negative")
+    uniq, counts = np.unique(sel, return_counts=True)
+    if uniq.size != sel.size:
+        raise ValueError(f"{who}: cells lists column {int(uniq[counts > 1][0])} more than once")
+    return sel
+
+
+def _column_map(sel, n_cols, who, dev):
+    """The device map of icnv_parse_*_cols_dev for the selection `sel` of a file with n_cols columns."""
+    if int(sel.max()) >= n_cols:
+        bad = int(sel[sel >= n_cols][0])
+        raise ValueError(f"{who}: cells entry {bad} is not a column of the file, which has {n_cols}")
+    col_map = np.full(n_cols, -1, dtype=np.int32)
+    col_map[sel] = np.arange(sel.size, dtype=np.int32)
+    return torch.from_numpy(col_map).to(dev)
+
+
+def parse_table_cols_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, col_map, line0=1):
+    """icnv_parse_table_cols_dev (DESIGN K26): parse_table_into for the columns a map selects.  col_map: a contiguous CUDA
+    int32 vector with one entry per numeric column of the FILE, the row of `out` (out.shape[0] = n_cols_out) that column goes
+    to, or -1.  The fields of skipped columns are not examined.  Returns (rows found, label ranges)."""
+    L = _lib.load()
+    if not (isinstance(text_dev, torch.Tensor) and text_dev.is_cuda and text_dev.dtype == torch.uint8 and text_dev.dim() == 1
+            and text_dev.is_contiguous()):
+        raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
+    host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
+    if not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
+        raise TypeError("text_host must be a contiguous one-dimensional uint8 array")
+    if not (isinstance(col_map, torch.Tensor) and col_map.is_cuda and col_map.dtype == torch.int32 and col_map.dim() == 1
+            and col_map.is_contiguous() and col_map.numel() >= 1):
+        raise TypeError("col_map must be a contiguous one-dimensional CUDA int32 tensor")
+    n_bytes = int(n_bytes)
+    if n_bytes < 1 or n_bytes > text_dev.numel() or n_bytes > host.size:
+        raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
+    n_out, _, ld = _check_matrix_ld(out)
+    row0, max_rows = int(row0), int(max_rows)
+    if row0 < 0 or max_rows < 1 or row0 + max_rows > out.shape[1]:
+        raise ValueError("rows row0 .. row0 + max_rows - 1 must be columns of out")
+    if n_out == 1:
+        ld = out.shape[1]
+    sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
+    ranges = np.zeros((max_rows, 2), dtype=np.int64)
+    n_rows = ct.c_int64(0)
+    check(L.icnv_parse_table_cols_dev(_ptr(text_dev), ct.c_void_p(host.ctypes.data), n_bytes, sep_b, int(col_map.numel()), int(line0), _ptr(out),
+                                      int(ld), row0, max_rows, ranges.ctypes.data_as(ct.POINTER(ct.c_int64)), ct.byref(n_rows), _ptr(col_map),
+                                      n_out, _stream()))
+    return int(n_rows.value), ranges[:int(n_rows.value)]
+
+
 def gather_matrix(x, genes=None, cells=None, out=None):
     """out[j, i] = x[cells[j], genes[i]] on the device (icnv_gather_matrix_dev): the kept, ordered genes and the kept cells of
     CreateInfercnvObject in one pass.  x: (C, G) CUDA float64 with contiguous rows; genes / cells: 0-based, any order, None for
@@ -526,7 +584,7 @@ def _count_newlines(path, n_bytes):
     return count
 
 
-def read_table(path, sep="\t", chunk_bytes=None):
+def read_table(path, sep="\t", chunk_bytes=None, cells=None):
     """read.table(path, sep = sep, header = TRUE, row.names = 1, check.names = FALSE) of a numeric table, parsed on the device
     (icnv_parse_table_dev, DESIGN K21; the grammar and what is refused: include/icnv.h "count matrices from text").
     Returns (row names, column names, x, stats): x is the (n_cols, n_rows) CUDA float64 tensor -- for a genes x cells file the
@@ -538,12 +596,19 @@ def read_table(path, sep="\t", chunk_bytes=None):
     device buffers: a thread reads chunk i + 1 from the file while chunk i is copied and parsed; a buffer grows when one line
     is longer than chunk_bytes.  A path that ends in .gz is decompressed by Python's gzip into the same pinned chunks
     (R/inferCNV.R:146-150 reads it through gzfile); .rds is not read (NotImplementedError).  A refused byte raises IcnvError
-    with the file line and the field."""
+    with the file line and the field.
+
+    cells (DESIGN K26): a list of 0-based numeric file columns, in any order, without repeats (ValueError before the file is
+    opened for an empty list, a repeat or a negative entry; once the header is read for an entry that is no column, with the
+    entry and the count).  Row k of x is then file column cells[k] -- x is (len(cells), n_rows), and so are the per-chunk
+    scratch and parts --, through icnv_parse_table_cols_dev: the fields of the other columns are not examined, so a byte
+    outside the grammar there is not reported.  All row names and ALL column names of the header still come back."""
     import gzip
     import queue
     import threading
     import time
     path = os.fspath(path)
+    sel = None if cells is None else _selected_columns(cells, "read_table")
     if path.endswith(".rds"):
         raise NotImplementedError("read_table: .rds input is not read; pass the matrix as an array")
     sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
@@ -618,6 +683,7 @@ def read_table(path, sep="\t", chunk_bytes=None):
         return n
 
     row_names, header_names, col_names, n_cols, parts, scratch = [], None, None, None, [], None
+    col_map = None                                                 # K26: the device map of the selection, once n_cols is known
     offset, ahead = 0, None                                        # bytes of the file before this chunk; (job, event) copied ahead
     thread = threading.Thread(target=reader, daemon=True)
     thread.start()
@@ -648,6 +714,8 @@ def read_table(path, sep="\t", chunk_bytes=None):
                         n_cols = len(col_names)
                         if n_cols < 1:
                             raise ValueError("read_table: the table has no numeric column")
+                        if sel is not None:
+                            col_map = _column_map(sel, n_cols, "read_table", dev)
                     p = e + 1
             nb = n - start
             if n_cols is not None and nb > 0:
@@ -655,7 +723,7 @@ def read_table(path, sep="\t", chunk_bytes=None):
                 ahead = None
                 max_rows = nb // (n_cols + 1) + 1                  # a row is at least its separators and its line end
                 if scratch is None or scratch.shape[1] < max_rows:
-                    scratch = torch.empty((n_cols, max_rows), dtype=torch.float64, device=dev)
+                    scratch = torch.empty((n_cols if sel is None else sel.size, max_rows), dtype=torch.float64, device=dev)
                 t0 = time.perf_counter()
                 try:                                               # the next chunk's copy runs beside this parse
                     peek = jobs.get_nowait()
@@ -667,17 +735,21 @@ def read_table(path, sep="\t", chunk_bytes=None):
                     pass
                 torch.cuda.current_stream().wait_event(event)
                 host = arr[start:n]
+
+                def parse(line0=1):
+                    if col_map is None:
+                        return parse_table_into(dbuf[slot], host, nb, sep_b, scratch, 0, max_rows, line0=line0)
+                    return parse_table_cols_into(dbuf[slot], host, nb, sep_b, scratch, 0, max_rows, col_map, line0=line0)
                 try:
-                    rows, ranges = parse_table_into(dbuf[slot], host, nb, sep_b, scratch, 0, max_rows)
+                    rows, ranges = parse()
                 except _lib.IcnvError as exc:
                     short = "max_rows" in str(exc)                 # more lines than full rows fit: some row is too short
                     if exc.code != _lib.ERR_ARG or not (short or "line " in str(exc)):
                         raise
                     if short:
                         max_rows = int(np.count_nonzero(host == 10)) + 1
-                        scratch = torch.empty((n_cols, max_rows), dtype=torch.float64, device=dev)
-                    line0 = 1 + _count_newlines(path, offset + start)     # the refusal again, with the file's line number
-                    parse_table_into(dbuf[slot], host, nb, sep_b, scratch, 0, max_rows, line0=line0)
+                        scratch = torch.empty((scratch.shape[0], max_rows), dtype=torch.float64, device=dev)
+                    parse(line0=1 + _count_newlines(path, offset + start))       # the refusal again, with the file's line number
                     raise
                 stats["parse_s"] += time.perf_counter() - t0
                 if rows:
@@ -1863,6 +1935,38 @@ def parse_triplets_into(text_dev, text_host, n_bytes, field, G, C, row, col, val
     return int(n.value)
 
 
+def parse_triplets_cols_into(text_dev, text_host, n_bytes, field, G, C, row, col, val, offset, col_map, n_cols_out, line0=1):
+    """icnv_parse_triplets_cols_dev (DESIGN K26): parse_triplets_into for the columns a map selects.  col_map: a contiguous CUDA
+    int32 vector of C entries, the new column (0 .. n_cols_out - 1) of each matrix column or -1.  Every entry of the chunk is validated; the kept ones
+    go, in file order and with their new column, to the slots from `offset` on.  Returns (kept, seen).  When the arrays are
+    too short for the kept entries the IcnvError's text holds their number ("N entries are kept")."""
+    L = _lib.load()
+    if not (isinstance(text_dev, torch.Tensor) and text_dev.is_cuda and text_dev.dtype == torch.uint8 and text_dev.dim() == 1
+            and text_dev.is_contiguous()):
+        raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
+    host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
+    if not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
+        raise TypeError("text_host must be a contiguous one-dimensional uint8 array")
+    if not (isinstance(col_map, torch.Tensor) and col_map.is_cuda and col_map.dtype == torch.int32 and col_map.dim() == 1
+            and col_map.is_contiguous() and col_map.numel() == int(C)):
+        raise TypeError("col_map must be a contiguous CUDA int32 vector with one entry per column of the matrix")
+    n_bytes, offset = int(n_bytes), int(offset)
+    if n_bytes < 1 or n_bytes > text_dev.numel() or n_bytes > host.size:
+        raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
+    for t in (row, col, val):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+                and t.numel() == row.numel()):
+            raise TypeError("row, col and val must be contiguous CUDA int32 vectors of one length")
+    if offset < 0 or offset > row.numel():
+        raise ValueError("offset must be 0 .. the length of the arrays")
+    capacity = row.numel() - offset
+    at = [ct.c_void_p(t.data_ptr() + 4 * offset) if capacity else ct.c_void_p(0) for t in (row, col, val)]
+    kept, seen = ct.c_int64(0), ct.c_int64(0)
+    check(L.icnv_parse_triplets_cols_dev(_ptr(text_dev), ct.c_void_p(host.ctypes.data), n_bytes, int(field), int(G), int(C), int(line0), at[0],
+                                         at[1], at[2], capacity, ct.byref(kept), _ptr(col_map), int(n_cols_out), ct.byref(seen), _stream()))
+    return int(kept.value), int(seen.value)
+
+
 def csc_from_sorted_triplets(row, col, G, C):
     """icnv_csc_from_sorted_triplets_dev: (colptr, -1, CSC_SORTED) for triplets in strictly ascending (col, row) order -- row
     and the values are then the CSC's arrays as they are --, or (None, k, CSC_DUPLICATE | CSC_DESCENT) with k the first entry
@@ -1887,7 +1991,7 @@ def _count_entries(path, skip_bytes):
     return count
 
 
-def read_mtx(path, chunk_bytes=None):
+def read_mtx(path, chunk_bytes=None, cells=None):
     """A MatrixMarket coordinate file (10x: matrix.mtx, or .gz) to a CSC DeviceCounts, parsed on the device
     (icnv_parse_triplets_dev, icnv_csc_from_sorted_triplets_dev; DESIGN K22; the grammar and what is refused: include/icnv.h
     "sparse count matrices").  Returns (DeviceCounts, stats).
@@ -1903,12 +2007,24 @@ def read_mtx(path, chunk_bytes=None):
     PyTorch as plumbing on the cold path; there is no hand-written device sort --, stats["sorted_on_device"] = 1.  A (row,
     column) pair stored twice raises ValueError("duplicate entry for row R, column C"), 1-based.
 
-    stats: bytes (of the body), chunks, entries, sorted_on_device, read_s / parse_s / stall_s / wall_s."""
+    stats: bytes (of the body), chunks, entries, sorted_on_device, read_s / parse_s / stall_s / wall_s.
+
+    cells (DESIGN K26): a list of 0-based matrix columns, in any order, without repeats (ValueError before the file is opened
+    for an empty list, a repeat or a negative entry; once the size line is read for an entry that is no column, with the entry
+    and the count).  The result is the G x len(cells) DeviceCounts whose column k is file column cells[k], through
+    icnv_parse_triplets_cols_dev: every entry of the file is still validated, and a refusal in a column that is not selected
+    reads as it does without `cells`.  The triplet arrays hold the kept entries only; they GROW: they start at the selection's
+    share of the size line's count (plus an eighth) and, when a chunk keeps more than is left, are reallocated to twice the
+    need and the chunk is parsed again.  The entry count that must equal the size line's is the number of entries seen;
+    stats["entries"] is that number, stats["entries_kept"] the entries of the result and stats["arrays_grown"] the reallocations.  A selection that is ascending keeps
+    a column-major file sorted; any other one goes through the torch.sort path."""
     import gzip
     import queue
+    import re
     import threading
     import time
     path = os.fspath(path)
+    sel = None if cells is None else _selected_columns(cells, "read_mtx")
     cap0 = max(64, int(chunk_bytes if chunk_bytes is not None else os.environ.get("ICNV_READ_MTX_CHUNK", READ_MTX_CHUNK)))
     dev = torch.device("cuda", torch.cuda.current_device())
     stats = {"bytes": 0, "chunks": 0, "entries": 0, "sorted_on_device": 0, "read_s": 0.0, "parse_s": 0.0, "stall_s": 0.0}
@@ -1958,8 +2074,33 @@ def read_mtx(path, chunk_bytes=None):
         finally:
             jobs.put(None)
 
-    row, col, val = (torch.empty(nnz, dtype=torch.int32, device=dev) for _ in range(3))
+    col_map, seen = None, 0                                        # K26: the device map of the selection; entries seen
+    try:
+        if sel is not None:
+            col_map = _column_map(sel, C, "read_mtx", dev)
+            stats["arrays_grown"] = 0
+    except BaseException:
+        f.close()
+        raise
+    first_capacity = nnz if sel is None else min(nnz, nnz * sel.size // C + nnz // 8 + 1024)
+    row, col, val = (torch.empty(first_capacity, dtype=torch.int32, device=dev) for _ in range(3))
     dbuf, offset, filled = None, 0, 0                              # bytes of the body before this chunk; entries so far
+
+    def parse_selected(text, host, n, line0=1):
+        """One chunk through the column-selected entry, the arrays grown when they are too short for what it keeps."""
+        nonlocal row, col, val
+        while True:
+            try:
+                return parse_triplets_cols_into(text, host, n, field, G, C, row, col, val, filled, col_map, sel.size, line0=line0)
+            except _lib.IcnvError as exc:
+                need = re.search(r"parse_triplets_cols: (\d+) entries are kept", str(exc))
+                if exc.code != _lib.ERR_ARG or need is None:
+                    raise
+                grown = [torch.empty(2 * (filled + int(need.group(1))), dtype=torch.int32, device=dev) for _ in range(3)]
+                for new, old in zip(grown, (row, col, val)):
+                    new[:filled].copy_(old[:filled])
+                row, col, val = grown
+                stats["arrays_grown"] += 1
     thread = threading.Thread(target=reader, daemon=True)
     thread.start()
     try:
@@ -1973,7 +2114,11 @@ def read_mtx(path, chunk_bytes=None):
                 dbuf[:n].copy_(buf[:n], non_blocking=True)
                 host = buf.numpy()[:n]
                 try:
-                    filled += parse_triplets_into(dbuf, host, n, field, G, C, row, col, val, filled)
+                    if sel is None:
+                        filled += parse_triplets_into(dbuf, host, n, field, G, C, row, col, val, filled)
+                    else:
+                        kept, in_chunk = parse_selected(dbuf, host, n)
+                        filled, seen = filled + kept, seen + in_chunk
                 except _lib.IcnvError as exc:
                     if exc.code != _lib.ERR_ARG or not ("capacity" in str(exc) or "line " in str(exc)):
                         raise
@@ -1981,7 +2126,10 @@ def read_mtx(path, chunk_bytes=None):
                         raise ValueError(f"read_mtx: the size line says {nnz} entries, the body has "
                                          f"{_count_entries(path, header_bytes)}") from None
                     line0 = 1 + _count_newlines(path, header_bytes + offset)      # the refusal again, with the file's line number
-                    parse_triplets_into(dbuf, host, n, field, G, C, row, col, val, filled, line0=line0)
+                    if sel is None:
+                        parse_triplets_into(dbuf, host, n, field, G, C, row, col, val, filled, line0=line0)
+                    else:
+                        parse_selected(dbuf, host, n, line0=line0)
                     raise
                 stats["parse_s"] += time.perf_counter() - t0
                 stats["chunks"] += 1
@@ -1999,9 +2147,15 @@ def read_mtx(path, chunk_bytes=None):
         f.close()
     if failure:
         raise failure[0]
-    if filled != nnz:
-        raise ValueError(f"read_mtx: the size line says {nnz} entries, the body has {filled}")
-    stats["bytes"], stats["entries"] = offset, filled
+    if sel is None:
+        seen = filled
+    if seen != nnz:
+        raise ValueError(f"read_mtx: the size line says {nnz} entries, the body has {seen}")
+    stats["bytes"], stats["entries"] = offset, seen
+    if sel is not None:
+        stats["entries_kept"] = filled
+        row, col, val = (t[:filled].clone() if t.numel() > filled else t for t in (row, col, val))
+        C = int(sel.size)
     colptr, first, kind = csc_from_sorted_triplets(row, col, G, C)
     if kind == _lib.CSC_DESCENT:
         key, perm = torch.sort(col.to(torch.int64) * G + row)
@@ -2013,7 +2167,8 @@ def read_mtx(path, chunk_bytes=None):
         if kind == _lib.CSC_DESCENT:
             raise RuntimeError("read_mtx: the sorted triplets are not in order (internal error)")
     if kind == _lib.CSC_DUPLICATE:
-        raise ValueError(f"duplicate entry for row {int(row[first]) + 1}, column {int(col[first]) + 1}")
+        column = int(col[first]) if sel is None else int(sel[int(col[first])])         # the file's column
+        raise ValueError(f"duplicate entry for row {int(row[first]) + 1}, column {column + 1}")
     del col
     counts = DeviceCounts(G, C, colptr=colptr, rowidx=row, vals=val)
     torch.cuda.synchronize()

@@ -303,3 +303,230 @@ class ShardedIngest:
                 allcs = cs.cpu().numpy() if hasattr(cs, "cpu") else np.asarray(cs)
             factor = float(np.median(allcs))              # stats::median: mean of the two middle values for an even count
         return eng.apply(counts_local, keep, cs, factor), keep, factor
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# From files to a rank's cells (DESIGN K26): CreateInfercnvObject for one rank.  Every rank reads the whole file's bytes and
+# converts its own columns only (device.read_table / read_mtx with cells=); the one exchange is the all-gather of the column
+# sums, from which every rank takes the same cell filter and the same down-sampling.
+def _table_columns(path, sep):
+    """The column names of a text table as device.read_table takes them: the header line has one name per numeric column, or
+    one more with a corner label in front; the first data line decides which."""
+    import gzip
+    import os
+    path = os.fspath(path)
+    if path.endswith(".rds"):
+        raise NotImplementedError("read_table: .rds input is not read; pass the matrix as an array")
+    sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
+    unquote = lambda b: b[1:-1] if len(b) >= 2 and b[:1] == b"\"" and b[-1:] == b"\"" else b
+    with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
+        line = f.readline()
+        line = line[:-1] if line.endswith(b"\n") else line
+        header = [unquote(t) for t in (line[:-1] if line.endswith(b"\r") else line).split(sep_b)]
+        for raw in f:
+            raw = raw.rstrip(b"\n")
+            if raw in (b"", b"\r"):
+                continue
+            k = raw.count(sep_b) + 1
+            if len(header) == k - 1:
+                names = header
+            elif len(header) == k and k >= 2:
+                names = header[1:]
+            else:
+                raise ValueError(f"read_table: the header has {len(header)} names, the first row has {k} fields")
+            if len(names) < 1:
+                raise ValueError("read_table: the table has no numeric column")
+            return [c.decode("utf-8", "surrogateescape") for c in names]
+    raise ValueError("read_table: the file has no data row")
+
+
+class ShardedCreate:
+    """CreateInfercnvObject (create_object.py) for rank `rank` of `world`: the formals of CreateInfercnvObject without
+    return_device, and keyword-only after ref_group_names
+        rank, world     this rank and the number of ranks
+        deal            "cyclic" (cyclic_cells) or "block" (shard_bounds) of the FILE's columns
+        process_group   the torch.distributed group of run()'s all-gather
+        reader          (path, cells) -> (gene names, ALL cell names, the (len(cells), G) array of file columns `cells`, or
+                        for a .mtx / 10x source the G x len(cells) scipy CSC); replaces device.read_table / read_mtx, and the
+                        matrix work then runs in NumPy / SciPy -- the host logic without a GPU.
+    The matrix is a file: a text table, a .mtx or a 10x directory.  Two phases around one exchange:
+        read()              header or size line, gene order, annotations -- CreateInfercnvObject's checks in its order --, the
+                            deal (world > the file's columns: ValueError before the body is read), this rank's columns parsed,
+                            .order_reduce; returns the column sums of its columns over the kept genes, in the order of the deal
+        finish(sums_all)    the sums of ALL file columns in file order -> select_cells with the same seed, so the same global
+                            `columns` on every rank; the rank keeps J = [j : columns[j] is its own], ascending, and returns
+                            (obj_local, x_local, shard): the InfercnvObject over those cells (group dicts of LOCAL indices,
+                            order within a group preserved, every other slot the single-rank object's), what
+                            CreateInfercnvObject(return_device=True) hands back for these cells, and
+                            {"global_index": J, "file_columns": columns[J], "C_total", "rank", "world", "deal"}
+        run()               read(), the all-gather of the padded sums placed into file order by the deal, finish(); without an
+                            initialised process group the one-rank case, equal to CreateInfercnvObject slot for slot."""
+
+    def __init__(self, raw_counts_matrix, gene_order_file, annotations_file, ref_group_names, *, rank, world, deal="cyclic",
+                 process_group=None, reader=None, delim="\t", max_cells_per_group=None, min_max_counts_per_cell=(100, float("inf")),
+                 chr_exclude=("chrX", "chrY", "chrM"), seed=0, gene_names=None, cell_names=None, chunk_bytes=None, sparse=None,
+                 gene_column=2):
+        if deal not in ("cyclic", "block"):
+            raise ValueError("deal must be 'cyclic' or 'block'")
+        rank, world = int(rank), int(world)
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError("rank must be 0 .. world - 1")
+        self.args = dict(raw_counts_matrix=raw_counts_matrix, gene_order_file=gene_order_file, annotations_file=annotations_file,
+                         ref_group_names=ref_group_names, delim=delim, max_cells_per_group=max_cells_per_group,
+                         min_max_counts_per_cell=min_max_counts_per_cell, chr_exclude=chr_exclude,
+                         seed=seed, gene_names=gene_names, cell_names=cell_names, chunk_bytes=chunk_bytes, sparse=sparse,
+                         gene_column=gene_column)
+        self.rank, self.world, self.deal, self.pg, self.reader = rank, world, deal, process_group, reader
+        self._read = None
+
+    def dealt(self, C_file, rank=None):
+        """The file columns of `rank` (default: this rank), in the order of the deal."""
+        rank = self.rank if rank is None else rank
+        if self.deal == "cyclic":
+            return cyclic_cells(C_file, self.world, rank)
+        c0, c1 = shard_bounds(C_file, self.world, rank)
+        return np.arange(c0, c1, dtype=np.int64)
+
+    def read(self):
+        import os
+        from . import create_object as co
+        a = self.args
+        positions = co.read_gene_order(a["gene_order_file"], a["chr_exclude"])
+        annotations = co.read_annotations(a["annotations_file"], a["delim"])
+        raw = a["raw_counts_matrix"]
+        if not isinstance(raw, (str, os.PathLike)):
+            raise ValueError("ShardedCreate reads the matrix from a file: a text table, a .mtx file or a 10x directory")
+        mtx = co._mtx_source(raw, a["gene_names"], a["cell_names"], a["gene_column"])
+        if mtx is None and a["sparse"]:
+            raise ValueError("sparse=True wants a .mtx file, a 10x directory or a scipy sparse matrix")
+        if mtx is not None:                                              # the size line
+            import gzip
+            from .device import _mtx_header
+            with (gzip.open(mtx[0], "rb") if mtx[0].endswith(".gz") else open(mtx[0], "rb")) as f:
+                _, G_file, C_file, _, _, _ = _mtx_header(f)
+        else:                                                            # the header line
+            C_file = len(_table_columns(raw, a["delim"]))
+        if self.world > C_file:
+            raise ValueError(f"world is {self.world}, but the file has only {C_file} columns")
+        mine = self.dealt(C_file)
+        counts = x = None
+        if mtx is not None:
+            genes, cells = mtx[1], mtx[2]
+            if self.reader is not None:
+                _, _, counts = self.reader(mtx[0], mine)
+            else:
+                from . import device
+                counts, _ = device.read_mtx(mtx[0], chunk_bytes=a["chunk_bytes"], cells=mine)
+            if (G_file, C_file) != (len(genes), len(cells)):
+                raise ValueError(f"the matrix is {G_file} x {C_file}, but there are {len(genes)} gene names and {len(cells)} cell names")
+            if a["sparse"] is False:
+                counts, x = None, (np.ascontiguousarray(counts.toarray().T) if self.reader is not None else counts.to_dense())
+        elif self.reader is not None:
+            genes, cells, x = self.reader(raw, mine)
+        else:
+            from . import device
+            genes, cells, x, _ = device.read_table(raw, sep=a["delim"], chunk_bytes=a["chunk_bytes"], cells=mine)
+        genes, cells = [str(g) for g in genes], [str(c) for c in cells]
+        if co._first_duplicate(genes) is not None:
+            raise ValueError(f"{co.ERR_DUP_ROW_NAMES} ({co._first_duplicate(genes)!r})")
+        co.check_annotated_cells(cells, annotations)
+        rows, chrs, start, stop = co.order_reduce(genes, positions)
+        if rows is None:
+            raise ValueError(co.ERR_NO_GENES)
+        if self.reader is not None:
+            if counts is not None:
+                sums = np.asarray(counts.tocsr()[rows].sum(axis=0), dtype=np.float64).ravel()
+            else:
+                x = np.ascontiguousarray(np.asarray(x, dtype=np.float64)[:, rows])
+                sums = x.sum(axis=1)
+        else:
+            from . import device
+            if counts is not None:
+                sums = device.ingest_col_sums(counts, rows).cpu().numpy()
+            else:
+                x = device.gather_matrix(x, genes=rows)
+                sums = device.col_sums(x).cpu().numpy()
+        self._read = dict(annotations=annotations, genes=genes, cells=cells, rows=rows, chrs=chrs, start=start, stop=stop, mine=mine,
+                          C_file=C_file, counts=counts, x=x)
+        return sums
+
+    def finish(self, col_sums_all):
+        from . import create_object as co
+        from .infercnv_object import GeneOrder, InfercnvObject
+        if self._read is None:
+            raise RuntimeError("finish() comes after read()")
+        r, a = self._read, self.args
+        cs = np.asarray(col_sums_all, dtype=np.float64).ravel()
+        if cs.size != r["C_file"]:
+            raise ValueError(f"col_sums_all has {cs.size} entries, the file has {r['C_file']} columns")
+        columns, _, ref, obs = co.select_cells(r["cells"], cs, r["annotations"], a["ref_group_names"], a["min_max_counts_per_cell"],
+                                               a["max_cells_per_group"], a["seed"])
+        if columns.size == 0:
+            raise ValueError("no cell is left after the counts-per-cell filter and the annotations")
+        local_of = np.full(r["C_file"], -1, dtype=np.int64)
+        local_of[r["mine"]] = np.arange(r["mine"].size)
+        J = np.flatnonzero(local_of[columns] >= 0)
+        if J.size == 0:
+            raise ValueError(f"no cell is left on rank {self.rank} of {self.world} after the counts-per-cell filter and the annotations")
+        keep = local_of[columns[J]]                                      # this rank's columns that stay, in the global order
+        counts, x, rows = r["counts"], r["x"], r["rows"]
+        if counts is not None:
+            if self.reader is not None:
+                x_local = counts.tocsr()[rows].tocsc()[:, keep]
+                expr = x_local
+            else:
+                from . import device
+                x_local = device.csc_select(counts, rows, keep)
+                expr = x_local.to_scipy()
+        elif self.reader is not None:
+            x_local = np.ascontiguousarray(x[keep])
+            expr = x_local.T
+        else:
+            from . import device
+            x_local = x if (keep.size == x.shape[0] and np.array_equal(keep, np.arange(keep.size))) else device.gather_matrix(x, cells=keep)
+            expr = x_local.cpu().numpy().T
+        localize = lambda groups: {name: np.searchsorted(J, idx[np.isin(idx, J)]).astype(np.int32) for name, idx in groups.items()}
+        obj = InfercnvObject(expr_data=expr, count_data=expr,
+                             gene_order=GeneOrder(chr=np.array(r["chrs"]), start=np.array(r["start"]), stop=np.array(r["stop"])),
+                             reference_grouped_cell_indices=localize(ref), observation_grouped_cell_indices=localize(obs),
+                             options={"chr_exclude": list(a["chr_exclude"]) if a["chr_exclude"] is not None else None,
+                                      "max_cells_per_group": a["max_cells_per_group"],
+                                      "min_max_counts_per_cell": list(a["min_max_counts_per_cell"]) if a["min_max_counts_per_cell"] is not None
+                                      else None,
+                                      "counts_md5": None},
+                             gene_names=np.array([r["genes"][g] for g in rows]), cell_names=np.array([r["cells"][j] for j in columns[J]]))
+        obj.validate()
+        shard = {"global_index": J, "file_columns": columns[J], "C_total": int(columns.size), "rank": self.rank, "world": self.world,
+                 "deal": self.deal}
+        return obj, x_local, shard
+
+    def place(self, parts):
+        """The ranks' sums (parts[r] in the order of rank r's deal) as one vector in file order."""
+        C_file = int(sum(len(p) for p in parts))
+        out = np.empty(C_file, dtype=np.float64)
+        for rank, p in enumerate(parts):
+            out[self.dealt(C_file, rank)] = np.asarray(p, dtype=np.float64)
+        return out
+
+    def run(self):
+        import torch
+        import torch.distributed as dist
+        sums = self.read()
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size(self.pg) > 1):
+            if self.world != 1:
+                raise RuntimeError(f"world is {self.world} but no process group is initialised: exchange the sums yourself and call finish()")
+            return self.finish(sums)
+        world = dist.get_world_size(self.pg)
+        if world != self.world:
+            raise ValueError(f"world is {self.world}, the process group has {world} ranks")
+        dev = "cuda" if dist.get_backend(self.pg) == "nccl" else "cpu"
+        cs = torch.from_numpy(np.ascontiguousarray(sums, dtype=np.float64)).to(dev)
+        n_local = torch.tensor([cs.numel()], dtype=torch.int64, device=cs.device)         # the size exchange of ShardedIngest.run
+        sizes = [torch.zeros_like(n_local) for _ in range(world)]
+        dist.all_gather(sizes, n_local, group=self.pg)
+        nmax = int(max(int(v.item()) for v in sizes))
+        pad = torch.zeros(nmax, dtype=cs.dtype, device=cs.device)
+        pad[: cs.numel()] = cs
+        parts = [torch.zeros_like(pad) for _ in range(world)]
+        dist.all_gather(parts, pad, group=self.pg)
+        return self.finish(self.place([p[: int(n.item())].cpu().numpy() for p, n in zip(parts, sizes)]))
