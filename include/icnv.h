@@ -1345,6 +1345,35 @@ void icnv_cnv_report_end(icnv_cnv_report_t *plan);
 int icnv_cnv_report_stats(int64_t *out, int32_t n);
 void icnv_cnv_report_stats_reset(void);
 
+/* ---- R's XDR stream of a matrix (K27) ------------------------------------------------------------------------------------------
+ * saveRDS writes a numeric or integer vector as its elements in order, each big-endian (XDR); a matrix is the vector of its
+ * columns, so element (r, c) of a rows x cols matrix is element e = c * rows + r of the stream.  The rest of the format -- the
+ * header, the flag words, attributes, strings -- is written on the host and is set down in infercnv_amd/rds.py.
+ *
+ * icnv_xdr_encode_dev writes the elements [e0, e1) of that stream to dst (DEVICE, (e1 - e0) * elem_size bytes: element e at
+ * dst + (e - e0) * elem_size), every element's bytes reversed.  elem_size is 8 (REALSXP) or 4 (INTSXP, LGLSXP).
+ *   ICNV_XDR_COLS  src is (cols, rows) with contiguous rows, ld >= rows elements apart: the device-resident (cells, genes)
+ *                  matrix, already in R's order.  A coalesced swap; 16-byte loads and stores where the segment is contiguous
+ *                  in src and src's first element and dst share their position in a 16-byte word.
+ *   ICNV_XDR_ROWS  src is (rows, cols) with contiguous rows, ld >= cols: an uploaded host expr_data.  A 64 x 64 tile transpose
+ *                  through LDS (rows padded by one element: no bank conflicts on either side) plus the swap.
+ * A vector is rows = n, cols = 1 (ICNV_XDR_COLS).  e0 and e1 need not fall on tile, row or column boundaries: a stream is cut
+ * into chunks by bytes.  e0 == e1 is a valid empty call.
+ * icnv_xdr_decode_dev is the inverse: src is the stream segment (DEVICE, element e at src + (e - e0) * elem_size), dst the
+ * matrix in either layout; only the elements of the segment are written.
+ * Index arithmetic is 64-bit throughout.  No floating-point operation touches the data: a NaN keeps its payload, NA_real_
+ * (0x7FF00000000007A2) among them.  The calls do not synchronise.
+ * ICNV_ERR_ARG before any launch: a null pointer; elem_size other than 8 or 4; an unknown layout; rows or cols < 1 or
+ *   rows * cols > 2^59; ld below the row length; e0 < 0, e0 > e1 or e1 > rows * cols; a pointer not aligned to elem_size.
+ * ICNV_ERR_UNSUPPORTED: an ICNV_XDR_ROWS segment of more than 2^31 - 1 tiles.
+ * Timer names: "xdr_encode", "xdr_decode". */
+#define ICNV_XDR_COLS 0
+#define ICNV_XDR_ROWS 1
+int icnv_xdr_encode_dev(const void *src, int32_t elem_size, int64_t rows, int64_t cols, int64_t ld, int32_t layout, int64_t e0,
+                        int64_t e1, void *dst, void *stream);
+int icnv_xdr_decode_dev(const void *src, int32_t elem_size, int64_t rows, int64_t cols, int64_t ld, int32_t layout, int64_t e0,
+                        int64_t e1, void *dst, void *stream);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

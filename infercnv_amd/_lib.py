@@ -36,6 +36,7 @@ TABLE_GENE_ROWS, TABLE_CELL_ROWS = 0, 1   # ICNV_TABLE_* orientations of icnv_fo
 REPORT_GENES, REPORT_REGIONS = 0, 1       # ICNV_REPORT_* kinds of icnv_cnv_report_begin_dev
 MM_INTEGER, MM_REAL, MM_PATTERN = 0, 1, 2      # ICNV_MM_* fields of icnv_parse_triplets_dev
 CSC_SORTED, CSC_DUPLICATE, CSC_DESCENT = 0, 1, 2   # ICNV_CSC_* results of icnv_csc_from_sorted_triplets_dev
+XDR_COLS, XDR_ROWS = 0, 1                 # ICNV_XDR_* layouts of icnv_xdr_encode_dev / icnv_xdr_decode_dev
 HSPIKE_GENES_TOKEN = 0x6873706B67656E65   # ICNV_HSPIKE_GENES_TOKEN: the stream of the hidden spike-in's genes_means_use_idx
 
 
@@ -212,6 +213,8 @@ PROTOTYPES = {
     "icnv_parse_triplets_cols_dev": (ct.c_int, [_vp, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64p, _vp, _i64, _i64p, _vp]),
     "icnv_csc_from_sorted_triplets_dev": (ct.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64p, ct.POINTER(ct.c_int32), _vp]),
     "icnv_csc_select_dev": (ct.c_int, [ct.POINTER(Counts), _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64p, _vp]),
+    "icnv_xdr_encode_dev": (ct.c_int, [_vp, _i32, _i64, _i64, _i64, _i32, _i64, _i64, _vp, _vp]),
+    "icnv_xdr_decode_dev": (ct.c_int, [_vp, _i32, _i64, _i64, _i64, _i32, _i64, _i64, _vp, _vp]),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

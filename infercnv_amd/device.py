@@ -2244,6 +2244,69 @@ def median_filter(x, chr_start, tiles, window_size=7, out=None, na_aware=False, 
     return out
 
 
+# ------------------------------------------------------------------ R's XDR stream of a matrix (DESIGN K27)
+XDR_LAYOUTS = {"cols": _lib.XDR_COLS, "rows": _lib.XDR_ROWS}
+_XDR_DTYPES = {torch.float64: 8, torch.int32: 4}
+
+
+def _xdr_matrix(x, layout):
+    """(rows, cols, ld, elem_size, layout code) of a CUDA float64 / int32 vector or matrix with contiguous rows, R's dim being
+    (rows, cols): a "cols" matrix has the shape (cols, rows), a "rows" matrix (rows, cols); a vector is rows = n, cols = 1."""
+    code = XDR_LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in _XDR_DTYPES and x.dim() in (1, 2)):
+        raise TypeError("expected a CUDA float64 or int32 vector or matrix")
+    if x.dim() == 1:
+        if x.numel() > 1 and x.stride(0) != 1:
+            raise TypeError("expected a contiguous vector")
+        if code != _lib.XDR_COLS:
+            raise ValueError('a vector is rows = n, cols = 1 of layout "cols"')
+        return int(x.numel()), 1, int(x.numel()), _XDR_DTYPES[x.dtype], code
+    if (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise TypeError("expected a matrix with contiguous rows")
+    ld = int(x.stride(0)) if x.shape[0] > 1 else int(x.shape[1])
+    rows, cols = (int(x.shape[1]), int(x.shape[0])) if code == _lib.XDR_COLS else (int(x.shape[0]), int(x.shape[1]))
+    return rows, cols, ld, _XDR_DTYPES[x.dtype], code
+
+
+def xdr_encode(x, *, layout="cols", e0=0, e1=None, out=None):
+    """The elements [e0, e1) of R's big-endian, column-major stream of a matrix (icnv_xdr_encode_dev, DESIGN K27) as a CUDA
+    uint8 tensor.  x: a CUDA float64 or int32 tensor with contiguous rows -- layout "cols": shape (cols, rows) of R's
+    rows x cols matrix, the (cells, genes) device matrix of genes x cells expr.data; layout "rows": shape (rows, cols); a
+    one-dimensional tensor is a vector.  out: a contiguous CUDA uint8 tensor that receives the bytes from its start (default:
+    a new one); the returned tensor is its first (e1 - e0) * elem_size bytes.  Does not synchronise."""
+    L = _lib.load()
+    rows, cols, ld, es, code = _xdr_matrix(x, layout)
+    e0, e1 = int(e0), rows * cols if e1 is None else int(e1)
+    nbytes = max(e1 - e0, 0) * es
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous()):
+        raise TypeError("out must be a contiguous one-dimensional CUDA uint8 tensor")
+    if out.numel() < nbytes:
+        raise ValueError(f"out holds {out.numel()} bytes, the segment needs {nbytes}")
+    if x.numel() == 0:
+        return out[:0]
+    check(L.icnv_xdr_encode_dev(_ptr(x), es, rows, cols, ld, code, e0, e1, _ptr(out), _stream()))
+    return out[:nbytes]
+
+
+def xdr_decode(src, out, *, layout="cols", e0=0, e1=None):
+    """The inverse (icnv_xdr_decode_dev): src, a contiguous CUDA uint8 tensor holding the elements [e0, e1) of the stream
+    from its start, into the matrix `out` (as x of xdr_encode; only the segment's elements are written).  Returns out.  Does
+    not synchronise."""
+    L = _lib.load()
+    rows, cols, ld, es, code = _xdr_matrix(out, layout)
+    e0, e1 = int(e0), rows * cols if e1 is None else int(e1)
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous()):
+        raise TypeError("src must be a contiguous one-dimensional CUDA uint8 tensor")
+    if src.numel() < max(e1 - e0, 0) * es:
+        raise ValueError(f"src holds {src.numel()} bytes, the segment needs {max(e1 - e0, 0) * es}")
+    if out.numel() == 0:
+        return out
+    check(L.icnv_xdr_decode_dev(_ptr(src), es, rows, cols, ld, code, e0, e1, _ptr(out), _stream()))
+    return out
+
+
 # ------------------------------------------------------------------ timing hooks
 def timing_enable(on=True):
     """on: False / 0 off, True / 1 every kernel family, 2 only the hot launches "chain_apply" and "viterbi"."""

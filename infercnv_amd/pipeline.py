@@ -6,9 +6,10 @@ tumor_subclusters, hmm, cnv_regions, bayes_net, mask_non_de, heatmap), each a th
 is what R's run() alone wrote down: the order, the guards, `up_to_step`, which object each stage reads, and the file-name
 tokens through which steps 17-20 find each other's files (`file_tokens`, `states_not_constant`).
 
-Not mirrored: resume and serialised step objects (`resume_mode`, `save_rds`, `save_final_rds`), the Bayes plots
-(`plot_probabilities`, `diagnostics`), `plot_subclusters`, and the options the library does not build (they raise
-NotImplementedError before anything runs).  `on_step` is the hook for checkpoints.
+Not mirrored: resume (`resume_mode`), the Bayes plots (`plot_probabilities`, `diagnostics`), `plot_subclusters`, and the
+options the library does not build (they raise NotImplementedError before anything runs).  run() itself serialises nothing
+(`save_rds`, `save_final_rds` are accepted and ignored); `on_step` is the hook for checkpoints, and `rds_checkpoints` the
+hook that writes R's serialised step objects under R's file names (DESIGN K27).
 """
 from __future__ import annotations
 
@@ -88,6 +89,134 @@ def states_not_constant(states) -> bool:
     if s.size == 0:
         return True           # length(unique(list())) is 0, and 0 != 1
     return bool((s != s.ravel()[0]).any())
+
+
+def _r_chr(v):
+    """sprintf("%s", v) of a scalar run() argument: NA for None, TRUE / FALSE, a number as as.character prints it."""
+    if v is None or (isinstance(v, float) and math.isnan(v)):
+        return "NA"
+    if isinstance(v, (bool, np.bool_)):
+        return "TRUE" if v else "FALSE"
+    if isinstance(v, (float, np.floating)):
+        return "%.15g" % v
+    return str(v)
+
+
+def checkpoint_file_names(**run_args):
+    """{step: file name} of the objects infercnv::run saves with save_rds (expected_file_names of .get_relevant_args_list,
+    R/inferCNV_ops.R:3316-3492, with R's own sprintf patterns), for the run() arguments given (the others at their defaults).
+    Steps R gives no file for these arguments are absent; step 18 is R's .mcmc_obj."""
+    a = {"HMM": False, "HMM_type": "i6", "analysis_mode": "subclusters", "tumor_subcluster_partition_method": "leiden",
+         "BayesMaxPNormal": 0.5, "num_ref_groups": None, "max_centered_threshold": 3, "remove_genes_at_chr_ends": False,
+         "prune_outliers": False, "mask_nonDE_genes": False, "denoise": False, "noise_filter": None, "sd_amplifier": 1.5,
+         "noise_logistic": False}
+    a.update({k: v for k, v in run_args.items() if k in a})
+    for k, choices in (("HMM_type", HMM_TYPES), ("analysis_mode", ANALYSIS_MODES), ("tumor_subcluster_partition_method", PARTITION_METHODS)):
+        a[k] = _match_arg(k, a[k], choices)
+    method, mode = a["tumor_subcluster_partition_method"], a["analysis_mode"]
+    token = "HMM" + a["HMM_type"] if a["HMM"] else ""
+    names = {1: "%02d_incoming_data.infercnv_obj" % 1, 2: "%02d_reduced_by_cutoff.infercnv_obj" % 2,
+             3: "%02d_normalized_by_depth%s.infercnv_obj" % (3, token), 4: "%02d_logtransformed%s.infercnv_obj" % (4, token),
+             5: "%02d_scaled%s.infercnv_obj" % (5, token)}
+    if a["num_ref_groups"] is not None:
+        names[6] = "%02d_split_%sf_refs%s.infercnv_obj" % (6, token, _r_chr(a["num_ref_groups"]))
+    if mode == "subclusters" and method == "random_trees":
+        token += ".rand_trees"
+        names[7] = "%02d_tumor_subclusters%s.%s.infercnv_obj" % (7, token, method)
+    names[8] = "%02d_remove_ref_avg_from_obs_logFC%s.infercnv_obj" % (8, token)
+    if not _is_na(a["max_centered_threshold"]):
+        names[9] = "%02d_apply_max_centered_expr_threshold%s.infercnv_obj" % (9, token)
+    names[10] = "%02d_smoothed_by_chr%s.infercnv_obj" % (10, token)
+    names[11] = "%02d_recentered_cells_by_chr%s.infercnv_obj" % (11, token)
+    names[12] = "%02d_remove_ref_avg_from_obs_adjust%s.infercnv_obj" % (12, token)
+    if a["remove_genes_at_chr_ends"]:
+        names[13] = "%02d_remove_gene_at_chr_ends%s.infercnv_obj" % (13, token)
+    names[14] = "%02d_invert_log_transform%s.infercnv_obj" % (14, token)
+    if mode == "subclusters" and method != "random_trees":
+        token += "." + method
+        names[15] = "%02d_tumor_subclusters%s.infercnv_obj" % (15, token)
+    elif mode != "subclusters":
+        names[15] = "%02d_no_subclustering%s.infercnv_obj" % (15, token)
+    if a["prune_outliers"]:
+        names[16] = "%02d_remove_outlier%s.infercnv_obj" % (16, token)
+    tokens = file_tokens(a["HMM"], a["HMM_type"], mode, method, a["BayesMaxPNormal"])
+    assert tokens["resume_file_token"] == token
+    hmm_token = tokens["hmm_resume_file_token"]
+    if a["HMM"]:
+        names[17] = "%02d_HMM_pred%s.infercnv_obj" % (17, hmm_token)
+        if a["BayesMaxPNormal"] > 0:
+            names[18] = "%02d_HMM_pred.Bayes_Net%s.mcmc_obj" % (18, hmm_token)
+            names[19] = "%02d_HMM_pred.Bayes_Net%s.Pnorm_%g.infercnv_obj" % (19, hmm_token, a["BayesMaxPNormal"])
+        names[20] = "%02d_HMM_pred.repr_intensities%s.Pnorm_%g.infercnv_obj" % (20, hmm_token, a["BayesMaxPNormal"])
+    if a["mask_nonDE_genes"]:
+        names[21] = "%02d_mask_nonDE%s.infercnv_obj" % (21, token)
+    if a["denoise"]:
+        names[22] = "%02d_denoise%s.NF_%s.SD_%g.NL_%s.infercnv_obj" % (22, token, _r_chr(a["noise_filter"]), a["sd_amplifier"],
+                                                                      _r_chr(a["noise_logistic"]))
+    return names
+
+
+def rds_checkpoints(out_dir, which="all", *, saver=None, **run_args):
+    """An on_step(step, label, obj) callable for run() that saves what infercnv::run saves with save_rds = TRUE and
+    save_final_rds = TRUE (DESIGN K27), as .rds files R reads (rds.save_infercnv_obj), under R's own names:
+
+      which="all"    every infercnv / HMM object under checkpoint_file_names(**run_args)[step], plus `preliminary.infercnv_obj`
+                     (R/inferCNV_ops.R:1156: the object after step 15 -- after step 14 when step 15 does not run) and
+                     `run.final.infercnv_obj` (:1618: the infercnv object after the last step that ran).  The two are hard
+                     links to the step file that holds the same object (a copy where the file system has no links): no second
+                     encode.
+      which="final"  only those two: the object is written at step 14, again at step 15 if it runs, and `run.final` follows
+                     the steps 16, 21 and 22 that run.
+    run_args: the arguments run() is called with (the ones the names depend on are read, the others ignored); pass the same
+    dict to both.  The step-18 MCMCInferCNV object has no R form here and is skipped with one log line.  A run that stops
+    early (up_to_step) leaves `run.final.infercnv_obj` naming the last object it reached, which R would not have written.
+    saver(obj, path): what writes a file (default rds.save_infercnv_obj); files are written under a temporary name and
+    renamed.  Resuming from these files is not built."""
+    if which not in ("all", "final"):
+        raise ValueError("which: 'all' or 'final'")
+    names = checkpoint_file_names(**run_args)
+    if saver is None:
+        from .rds import save_infercnv_obj as saver
+
+    def write(obj, name):
+        path = os.path.join(out_dir, name)
+        saver(obj, path + ".tmp")
+        os.replace(path + ".tmp", path)
+        return path
+
+    def alias(path, name):
+        target = os.path.join(out_dir, name)
+        if os.path.lexists(target + ".tmp"):
+            os.remove(target + ".tmp")
+        try:
+            os.link(path, target + ".tmp")
+        except OSError:
+            import shutil
+            shutil.copyfile(path, target + ".tmp")
+        os.replace(target + ".tmp", target)
+
+    def on_step(step, label, obj):
+        if step == 18:
+            log.info("rds_checkpoints: the step-18 MCMCInferCNV object (%s) is not written", names.get(18, "no file in R either"))
+            return
+        is_hmm_obj = step in (17, 19, 20)
+        path = None
+        if which == "all" and step in names:
+            path = write(obj, names[step])
+        if is_hmm_obj:
+            return
+        if step in (14, 15):
+            path = path or write(obj, "preliminary.infercnv_obj")
+            if which == "all":
+                alias(path, "preliminary.infercnv_obj")
+            alias(path, "run.final.infercnv_obj")
+        elif which == "all" and path is not None:
+            alias(path, "run.final.infercnv_obj")
+        elif which == "final" and step > 15:
+            write(obj, "run.final.infercnv_obj")
+
+    on_step.file_names = names
+    return on_step
 
 
 def check_arguments(a):
