@@ -1374,6 +1374,40 @@ int icnv_xdr_encode_dev(const void *src, int32_t elem_size, int64_t rows, int64_
 int icnv_xdr_decode_dev(const void *src, int32_t elem_size, int64_t rows, int64_t cols, int64_t ld, int32_t layout, int64_t e0,
                         int64_t e1, void *dst, void *stream);
 
+/* ---- DEFLATE in independent pieces (K28) ------------------------------------------------------------------------------------------
+ * A payload-agnostic compressor: bytes on the device in, DEFLATE (RFC 1951) out.  The input is cut into pieces of piece_bytes
+ * (the last one shorter); piece i compresses src[i * piece_bytes, min(n, (i + 1) * piece_bytes)) on its own, one workgroup per
+ * piece, and lands at dst + i * dst_stride.  saveRDS's gzip stream is assembled from such pieces in infercnv_amd/rds.py.
+ *   a piece     a sequence of complete DEFLATE blocks: no block has BFINAL set; no match distance reaches before the piece's
+ *               first byte; the piece ends on a byte boundary (after a Huffman-coded block the empty stored block of zlib's
+ *               Z_SYNC_FLUSH follows: 000, pad, 00 00 FF FF).  A raw inflater started fresh on a piece returns the piece's
+ *               input and accepts the next piece, or a final empty block, directly behind it.
+ *   its form    whichever is smaller: one stored block (5 bytes of header), or one dynamic-Huffman block (BTYPE 10) over LZ77
+ *               tokens -- matches of 3..258 bytes at distance 8, distance 1 or to the latest earlier position with the same
+ *               4-byte hash; code lengths <= 15 (literal/length, distance) and <= 7 (code-length alphabet), the length sequence
+ *               run-length coded with 16, 17, 18.  A length limit that cannot be met stores the piece.  No fixed-Huffman block.
+ *   piece_len   DEVICE int32 [pieces]: the bytes of piece i, 6 <= piece_len[i] <= icnv_deflate_bound(piece_bytes).
+ *   piece_crc   DEVICE uint32 [pieces]: the CRC-32 of piece i's INPUT (zlib's: reflected 0xEDB88320, initial value and final xor
+ *               0xFFFFFFFF); the stream's CRC follows by crc32_combine without a pass over the payload.
+ *   bound       icnv_deflate_bound(piece_bytes) = piece_bytes + 5 * ceil(piece_bytes / 65535), or -1 outside the allowed range.
+ *               No store lands outside [dst + i * dst_stride, + bound): every store's offset is tested against it.
+ *   range       256 <= piece_bytes <= 16384 (the piece, its match records and its hash table live in 77 KiB of LDS).
+ * The output is a function of src's bytes, n and piece_bytes only: every atomic is an integer max, sum, or or xor in LDS, no
+ * workgroup looks at another, and the geometry is fixed.  src needs no alignment (4-byte aligned pieces are loaded as dwords).
+ * n == 0 is a valid empty call.  The call does not synchronise.
+ * icnv_deflate_pack_dev: the lengths pass plus emit pass of K20 / K24 -- a prefix sum of piece_len (each clamped to
+ * [0, dst_stride]), then a copy of every piece behind the one before into out (DEVICE, out_cap bytes).  *out_len (HOST) is
+ * the packed size.  The call WAITS on `stream` twice: for the size, ahead of the copy, and at its end.
+ * ICNV_ERR_ARG before any launch: n < 0; piece_bytes outside the range; dst_stride below the bound; a null pointer with work
+ *   to do; piece_len / piece_crc not 4-byte aligned; more than 2^31 - 1 pieces.  icnv_deflate_pack_dev: the same kind, and,
+ *   after the lengths pass and before the copy, out_cap below the packed size -- nothing is written to out then.
+ * Timer names: "deflate_pieces", "deflate_pack". */
+int64_t icnv_deflate_bound(int64_t piece_bytes);
+int icnv_deflate_pieces_dev(const uint8_t *src, int64_t n, int64_t piece_bytes, uint8_t *dst, int64_t dst_stride, int32_t *piece_len,
+                            uint32_t *piece_crc, void *stream);
+int icnv_deflate_pack_dev(const uint8_t *dst, int64_t dst_stride, const int32_t *piece_len, int64_t n_pieces, uint8_t *out,
+                          int64_t out_cap, int64_t *out_len /* HOST */, void *stream);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

@@ -215,6 +215,9 @@ PROTOTYPES = {
     "icnv_csc_select_dev": (ct.c_int, [ct.POINTER(Counts), _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64p, _vp]),
     "icnv_xdr_encode_dev": (ct.c_int, [_vp, _i32, _i64, _i64, _i64, _i32, _i64, _i64, _vp, _vp]),
     "icnv_xdr_decode_dev": (ct.c_int, [_vp, _i32, _i64, _i64, _i64, _i32, _i64, _i64, _vp, _vp]),
+    "icnv_deflate_bound": (ct.c_int64, [_i64]),
+    "icnv_deflate_pieces_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "icnv_deflate_pack_dev": (ct.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64p, _vp]),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

@@ -12,6 +12,7 @@ at offset g + G*c.  State matrices are uint8 (C, G).
 from __future__ import annotations
 
 import ctypes as ct
+import functools
 import os
 
 import numpy as np
@@ -2305,6 +2306,133 @@ def xdr_decode(src, out, *, layout="cols", e0=0, e1=None):
         return out
     check(L.icnv_xdr_decode_dev(_ptr(src), es, rows, cols, ld, code, e0, e1, _ptr(out), _stream()))
     return out
+
+
+# ------------------------------------------------------------------ DEFLATE in independent pieces (DESIGN K28)
+DEFLATE_PIECE = 16384                                  # the default piece_bytes
+DEFLATE_PIECE_MIN, DEFLATE_PIECE_MAX = 256, 16384      # the range icnv_deflate_pieces_dev takes
+_CRC_POLY = 0xEDB88320
+
+
+def deflate_bound(piece_bytes):
+    """icnv_deflate_bound: the most bytes one compressed piece takes (the piece stored: 5 bytes of header per 65 535)."""
+    piece_bytes = int(piece_bytes)
+    if not DEFLATE_PIECE_MIN <= piece_bytes <= DEFLATE_PIECE_MAX:
+        raise ValueError(f"piece_bytes must lie in [{DEFLATE_PIECE_MIN}, {DEFLATE_PIECE_MAX}]")
+    return piece_bytes + 5 * ((piece_bytes + 65534) // 65535)
+
+
+def _is_bytes_tensor(t, dim):
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == dim
+
+
+def deflate_pieces(src, piece_bytes=DEFLATE_PIECE, *, dst=None):
+    """icnv_deflate_pieces_dev (DESIGN K28): the contiguous CUDA uint8 vector src as independent DEFLATE pieces of piece_bytes
+    of input each.  Returns (dst, piece_len, piece_crc): dst a (pieces, >= deflate_bound) CUDA uint8 tensor with piece i at the
+    start of row i (dst=: a caller's tensor of that shape, rows of contiguous bytes at any row stride), piece_len int32, and
+    piece_crc the CRC-32 of every piece's input as int32 bit patterns (`.cpu().numpy().view(np.uint32)`).  Does not
+    synchronise."""
+    L = _lib.load()
+    bound = deflate_bound(piece_bytes)
+    if not (_is_bytes_tensor(src, 1) and (src.numel() <= 1 or src.stride(0) == 1)):
+        raise TypeError("src must be a contiguous one-dimensional CUDA uint8 tensor")
+    n = int(src.numel())
+    n_pieces = -(-n // int(piece_bytes))
+    if dst is None:
+        dst = torch.empty((n_pieces, bound), dtype=torch.uint8, device=src.device)
+    if not (_is_bytes_tensor(dst, 2) and dst.shape[0] >= n_pieces and dst.shape[1] >= bound and (dst.shape[1] <= 1 or dst.stride(1) == 1)
+            and (dst.shape[0] <= 1 or dst.stride(0) >= dst.shape[1])):
+        raise TypeError(f"dst must be a CUDA uint8 tensor of at least ({n_pieces}, {bound}) with contiguous rows")
+    stride = int(dst.stride(0)) if dst.shape[0] > 1 else int(dst.shape[1])
+    piece_len = torch.empty(n_pieces, dtype=torch.int32, device=src.device)
+    piece_crc = torch.empty(n_pieces, dtype=torch.int32, device=src.device)
+    if n:
+        check(L.icnv_deflate_pieces_dev(_ptr(src), n, int(piece_bytes), _ptr(dst), stride, _ptr(piece_len), _ptr(piece_crc), _stream()))
+    return dst[:n_pieces], piece_len, piece_crc
+
+
+def deflate_pack(dst, piece_len, *, out=None, out_cap=None):
+    """icnv_deflate_pack_dev: the pieces of deflate_pieces one behind the other.  out: a contiguous CUDA uint8 vector that
+    receives them from its start (default: a new one that holds the worst case); out_cap: the bytes of it that may be written
+    (default: all).  Returns out[:packed size].  Waits for the stream."""
+    L = _lib.load()
+    n_pieces = int(piece_len.numel())
+    if not (_is_bytes_tensor(dst, 2) and dst.shape[0] >= n_pieces and (dst.shape[1] <= 1 or dst.stride(1) == 1)):
+        raise TypeError("dst must be the tensor deflate_pieces returned")
+    if not (isinstance(piece_len, torch.Tensor) and piece_len.is_cuda and piece_len.dtype == torch.int32 and piece_len.is_contiguous()):
+        raise TypeError("piece_len must be a contiguous CUDA int32 tensor")
+    stride = int(dst.stride(0)) if dst.shape[0] > 1 else int(dst.shape[1])
+    if out is None:
+        out = torch.empty(n_pieces * int(dst.shape[1]), dtype=torch.uint8, device=dst.device)
+    if not (_is_bytes_tensor(out, 1) and out.is_contiguous()):
+        raise TypeError("out must be a contiguous one-dimensional CUDA uint8 tensor")
+    cap = int(out.numel()) if out_cap is None else int(out_cap)
+    if cap > out.numel():
+        raise ValueError("out_cap is beyond out")
+    total = ct.c_int64(0)
+    check(L.icnv_deflate_pack_dev(_ptr(dst), stride, _ptr(piece_len), n_pieces, _ptr(out), cap, ct.byref(total), _stream()))
+    return out[:total.value]
+
+
+def _crc_mul(a, b):
+    """a(x) * b(x) mod P over GF(2) in the CRC's reflected form (bit 31 is x^0): Python ints, or numpy uint32 arrays."""
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        a, b = np.broadcast_arrays(np.asarray(a, dtype=np.uint32), np.asarray(b, dtype=np.uint32))
+        b, p = b.copy(), np.zeros(a.shape, dtype=np.uint32)
+        for i in range(32):
+            p ^= np.where(a & np.uint32(0x80000000 >> i), b, np.uint32(0))
+            b = np.where(b & np.uint32(1), (b >> np.uint32(1)) ^ np.uint32(_CRC_POLY), b >> np.uint32(1))
+        return p
+    p = 0
+    for i in range(32):
+        if a & (0x80000000 >> i):
+            p ^= b
+        b = (b >> 1) ^ _CRC_POLY if b & 1 else b >> 1
+    return p
+
+
+@functools.lru_cache(maxsize=256)
+def crc32_shift_operator(n_bytes):
+    """x^(8 * n_bytes) mod P: the operator that moves a CRC-32 across n_bytes of data (zlib's crc32_combine_gen).  Square and
+    multiply on the bits of n_bytes: any length, nothing allocated.  (Cached: a stream's chunks ask for the same few.)"""
+    n_bytes = int(n_bytes)
+    if n_bytes < 0:
+        raise ValueError("negative length")
+    r, b = 0x80000000, 0x00800000            # x^0, x^8
+    while n_bytes:
+        if n_bytes & 1:
+            r = _crc_mul(r, b)
+        b = _crc_mul(b, b)
+        n_bytes >>= 1
+    return r
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """zlib's crc32_combine: the CRC-32 of A + B from crc32(A), crc32(B) and len(B), as a pure function on the host."""
+    return _crc_mul(crc32_shift_operator(len_b), int(crc_a) & 0xFFFFFFFF) ^ (int(crc_b) & 0xFFFFFFFF)
+
+
+def crc32_combine_pieces(crcs, piece_bytes, last_bytes=None):
+    """The CRC-32 of the concatenation of pieces of one common length: crcs[i] = crc32(piece i), every piece piece_bytes long
+    but the last, which holds last_bytes (default piece_bytes).  A pairwise tree over numpy vectors: level k combines
+    neighbours with the one operator x^(8 * piece_bytes * 2^k), so a payload of tens of thousands of pieces costs
+    log2(pieces) operators, not one per piece.  An empty list gives 0, the CRC of no bytes."""
+    c = (np.asarray(crcs).astype(np.int64).ravel() & 0xFFFFFFFF).astype(np.uint32)      # (int32 bit patterns are taken as they are)
+    if c.size == 0:
+        return 0
+    last = int(c[-1])
+    last_bytes = int(piece_bytes) if last_bytes is None else int(last_bytes)
+    head = c[:-1]
+    acc, span = 0, int(piece_bytes)
+    if head.size:
+        m = 1 << (int(head.size) - 1).bit_length()
+        v = np.zeros(m, dtype=np.uint32)
+        v[m - head.size:] = head             # leading zeros are neutral: 0 * x^k = 0
+        while v.size > 1:
+            v = _crc_mul(v[0::2], np.uint32(crc32_shift_operator(span))) ^ v[1::2]
+            span *= 2
+        acc = int(v[0])
+    return crc32_combine(acc, last, last_bytes)
 
 
 # ------------------------------------------------------------------ timing hooks

@@ -156,7 +156,7 @@ def checkpoint_file_names(**run_args):
     return names
 
 
-def rds_checkpoints(out_dir, which="all", *, saver=None, **run_args):
+def rds_checkpoints(out_dir, which="all", *, saver=None, compress=False, **run_args):
     """An on_step(step, label, obj) callable for run() that saves what infercnv::run saves with save_rds = TRUE and
     save_final_rds = TRUE (DESIGN K27), as .rds files R reads (rds.save_infercnv_obj), under R's own names:
 
@@ -171,12 +171,16 @@ def rds_checkpoints(out_dir, which="all", *, saver=None, **run_args):
     dict to both.  The step-18 MCMCInferCNV object has no R form here and is skipped with one log line.  A run that stops
     early (up_to_step) leaves `run.final.infercnv_obj` naming the last object it reached, which R would not have written.
     saver(obj, path): what writes a file (default rds.save_infercnv_obj); files are written under a temporary name and
-    renamed.  Resuming from these files is not built."""
+    renamed.  compress: handed to the default saver (gzip files, as saveRDS writes by default; compressed on the device where
+    the payloads go through it, DESIGN K28); ignored when `saver` is given.  Resuming from these files is not built."""
     if which not in ("all", "final"):
         raise ValueError("which: 'all' or 'final'")
     names = checkpoint_file_names(**run_args)
     if saver is None:
-        from .rds import save_infercnv_obj as saver
+        from . import rds
+
+        def saver(obj, path):
+            return rds.save_infercnv_obj(obj, path, compress=compress)
 
     def write(obj, name):
         path = os.path.join(out_dir, name)

@@ -10,7 +10,9 @@ structure of an R-written infercnv object as a skeleton that our file must repro
 
 The format (R Internals, "Serialization Formats"), as written here
 ------------------------------------------------------------------
-XDR, version 3, uncompressed unless compress=True -- what saveRDS(compress = FALSE) writes; readRDS detects it.
+XDR, version 3, uncompressed unless compress=True -- what saveRDS(compress = FALSE) writes; readRDS detects it.  With
+compress=True the same stream inside one gzip member, as saveRDS writes by default: put together by GzipAssembler from
+pieces compressed on the device where that route exists (DESIGN K28), by Python's GzipFile otherwise.
 
   header   `X\\n`, int32 3, int32 writer version (0x00040000: R 4.0.0), int32 min-reader 0x00030500 (R 3.5.0),
            int32 5, `UTF-8`.  All integers big-endian.
@@ -81,8 +83,10 @@ import bz2
 import gzip
 import lzma
 import mmap
+import os
 import struct
 import time
+import zlib
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -321,31 +325,7 @@ class _Writer:
         on_device = cuda or (self.device is not False and n * es >= DEVICE_THRESHOLD and _device_available())
         if not on_device:
             return self.host_payload(v)
-        import torch
-        from . import device as dev, text_stream
-        upload_s = 0.0
-        if cuda:
-            x, layout = v, "cols"
-        else:                       # an uploaded host array: a vector as it is, a matrix in its own (rows, cols) layout
-            target = self.device if self.device not in (None, True) else "cuda"
-            t0 = time.perf_counter()
-            x, layout = torch.from_numpy(np.ascontiguousarray(v)).to(target), ("rows" if v.ndim == 2 else "cols")
-            torch.cuda.synchronize(x.device)
-            upload_s = time.perf_counter() - t0
-        self.flush()
-        per_chunk = max(1, min(CHUNK_BYTES, -(-n * es // 16) * 16) // es)
-        state = {"e": 0}
-
-        def fill(buf):
-            e0 = state["e"]
-            if e0 >= n:
-                return None
-            e1 = min(n, e0 + per_chunk)
-            dev.xdr_encode(x, layout=layout, e0=e0, e1=e1, out=buf)
-            state["e"] = e1
-            return (e1 - e0) * es
-
-        self.stats.append(dict(text_stream.stream_chunks(self.f, per_chunk * es, x.device, fill), upload_s=upload_s))
+        self.stats.append(_stream_payload(self, v, cuda, n, es))
 
     def host_payload(self, v):
         """The CPU-testable restatement of the device route: transpose, then swap."""
@@ -367,16 +347,147 @@ def _device_available():
         return False
 
 
+def _deflate_enabled():
+    """ICNV_DEFLATE=0 (environment, read per call): compress=True keeps Python's GzipFile even where a GPU is present."""
+    return os.environ.get("ICNV_DEFLATE", "1").strip() != "0"
+
+
+def _stream_payload(w, v, cuda, n, es):
+    """The device route of one numeric payload of n elements of es bytes: v, a CUDA tensor or a host array that is uploaded, is
+    encoded chunk by chunk and streamed to the file (text_stream.stream_chunks).  Under a GzipAssembler every chunk is
+    compressed where it was encoded -- xdr_encode into a scratch, deflate_pieces, deflate_pack into the streamed buffer -- and
+    the packed pieces go to the raw file.  Returns the payload's statistics."""
+    import torch
+    from . import device as dev, text_stream
+    upload_s = 0.0
+    if cuda:
+        x, layout = v, "cols"
+    else:                       # an uploaded host array: a vector as it is, a matrix in its own (rows, cols) layout
+        target = w.device if w.device not in (None, True) else "cuda"
+        t0 = time.perf_counter()
+        x, layout = torch.from_numpy(np.ascontiguousarray(v)).to(target), ("rows" if v.ndim == 2 else "cols")
+        torch.cuda.synchronize(x.device)
+        upload_s = time.perf_counter() - t0
+    w.flush()
+    per_chunk = max(1, min(CHUNK_BYTES, -(-n * es // 16) * 16) // es)
+    state = {"e": 0}
+    gz = w.f if isinstance(w.f, GzipAssembler) else None
+    if gz is None:
+        def fill(buf):
+            e0 = state["e"]
+            if e0 >= n:
+                return None
+            e1 = min(n, e0 + per_chunk)
+            dev.xdr_encode(x, layout=layout, e0=e0, e1=e1, out=buf)
+            state["e"] = e1
+            return (e1 - e0) * es
+
+        return dict(text_stream.stream_chunks(w.f, per_chunk * es, x.device, fill), upload_s=upload_s)
+
+    piece = dev.DEFLATE_PIECE
+    max_pieces = -(-per_chunk * es // piece)
+    with torch.cuda.device(x.device):
+        scratch = torch.empty(per_chunk * es, dtype=torch.uint8, device=x.device)
+        slots = torch.empty((max_pieces, dev.deflate_bound(piece)), dtype=torch.uint8, device=x.device)
+    extra = {"raw_bytes": 0, "compressed_bytes": 0, "pieces": 0, "stored_pieces": 0, "deflate_s": 0.0}
+
+    def fill(buf):
+        e0 = state["e"]
+        if e0 >= n:
+            return None
+        e1 = min(n, e0 + per_chunk)
+        raw = dev.xdr_encode(x, layout=layout, e0=e0, e1=e1, out=scratch)
+        t0 = time.perf_counter()
+        dst, piece_len, piece_crc = dev.deflate_pieces(raw, piece, dst=slots)
+        packed = dev.deflate_pack(dst, piece_len, out=buf)              # waits for the stream: the size comes back
+        lens = piece_len.cpu().numpy()
+        extra["deflate_s"] += time.perf_counter() - t0
+        nbytes = (e1 - e0) * es
+        gz.add_pieces(piece_crc.cpu().numpy(), piece, nbytes, int(packed.numel()))
+        inputs = np.full(lens.size, piece, dtype=np.int64)
+        inputs[-1] = nbytes - (lens.size - 1) * piece
+        extra["raw_bytes"] += nbytes
+        extra["compressed_bytes"] += int(packed.numel())
+        extra["pieces"] += int(lens.size)
+        extra["stored_pieces"] += int((lens == inputs + 5).sum())       # a Huffman-coded piece is smaller than that
+        state["e"] = e1
+        return int(packed.numel())
+
+    stats = text_stream.stream_chunks(gz.begin_payload(), max_pieces * dev.deflate_bound(piece), x.device, fill)
+    return dict(stats, upload_s=upload_s, **extra)
+
+
+GZIP_HEADER = b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff"      # deflate, no flags, mtime 0, no extra flags, OS unknown
+
+
+class GzipAssembler:
+    """One gzip member (RFC 1952) around ONE raw DEFLATE stream that two compressors write in turn: the small host-side
+    parts go through zlib (level 6, raw), every device payload is the packed pieces of icnv_deflate_pieces_dev, written to
+    the raw file by the caller between begin_payload() and add_pieces().  A Z_FULL_FLUSH ahead of every payload ends the host
+    compressor's block on a byte boundary and empties its window, so it never refers back across bytes it did not see; the
+    pieces end on byte boundaries and set no BFINAL; the host compressor's Z_FINISH ends the stream.  The trailer's CRC-32 is
+    combined from the host segments' zlib.crc32 and the pieces' CRCs (device.crc32_combine): no host pass over a payload."""
+
+    def __init__(self, raw):
+        self.raw = raw
+        self.z = zlib.compressobj(6, zlib.DEFLATED, -15)
+        self.crc, self.size, self.compressed = 0, 0, 0
+        self._raw(GZIP_HEADER)
+
+    def _raw(self, b):
+        if b:
+            self.raw.write(b)
+            self.compressed += len(b)
+
+    def write(self, b):
+        """Host bytes of the uncompressed stream."""
+        self.crc = zlib.crc32(b, self.crc)
+        self.size += len(b)
+        self._raw(self.z.compress(b))
+        return len(b)
+
+    def begin_payload(self):
+        """Ends the host compressor's part; returns the raw file, which the caller writes the packed pieces to."""
+        self._raw(self.z.flush(zlib.Z_FULL_FLUSH))
+        return self.raw
+
+    def add_pieces(self, piece_crcs, piece_bytes, raw_bytes, compressed_bytes):
+        """Accounts for pieces the caller wrote (or is writing) to the raw file: the CRC-32 of every piece's input, the
+        common input length of all but the last, the input bytes and the compressed bytes in all."""
+        from .device import crc32_combine, crc32_combine_pieces
+        n = len(piece_crcs)
+        if n == 0:
+            return
+        last = int(raw_bytes) - (n - 1) * int(piece_bytes)
+        if not 0 < last <= piece_bytes:
+            raise ValueError("the pieces do not add up to raw_bytes")
+        self.crc = crc32_combine(self.crc, crc32_combine_pieces(piece_crcs, piece_bytes, last), raw_bytes)
+        self.size += int(raw_bytes)
+        self.compressed += int(compressed_bytes)
+
+    def close(self):
+        self._raw(self.z.flush(zlib.Z_FINISH))
+        self._raw(struct.pack("<II", self.crc & 0xFFFFFFFF, self.size & 0xFFFFFFFF))
+
+
 def write_rds(value, path, *, compress=False, device=None):
     """Writes `value` (module docstring: the value model) as an .rds file readRDS detects.  path: a file name or a binary
     file object.  Numeric arrays of at least DEVICE_THRESHOLD bytes are uploaded, encoded on the device in chunks of
     CHUNK_BYTES and streamed to the file (text_stream.stream_chunks); a CUDA tensor is encoded from where it lives; smaller
     arrays, and every array with device=False or without a GPU, are encoded with NumPy.  Both routes write the same bytes.
-    compress=True wraps the stream in Python's gzip (what saveRDS does by default): it is slow, several seconds per
-    100 MB, and is meant for small objects.  Returns the stream statistics of the payloads that went through the device."""
+    compress=True writes a gzip file, what saveRDS does by default.  Where the device route exists (device is not False and a
+    GPU is present) it is one gzip member with mtime 0 put together by GzipAssembler: the payloads that go through the device
+    are compressed there in independent pieces (icnv_deflate_pieces_dev, DESIGN K28), everything else by zlib on the host,
+    and the statistics of such a payload gain raw_bytes, compressed_bytes, pieces, stored_pieces and deflate_s.  With
+    device=False, without a GPU or with ICNV_DEFLATE=0 in the environment the stream goes through Python's GzipFile on the
+    host as before (tens of MB per second).  Either file inflates to the bytes compress=False writes.  Returns the stream
+    statistics of the payloads that went through the device."""
     own = isinstance(path, (str, bytes)) or hasattr(path, "__fspath__")
     raw = open(path, "wb") if own else path
-    f = gzip.GzipFile(fileobj=raw, mode="wb") if compress else raw
+    if compress and device is not False and _deflate_enabled() and _device_available():
+        f = GzipAssembler(raw)
+    else:
+        f = gzip.GzipFile(fileobj=raw, mode="wb") if compress else raw
     try:
         w = _Writer(f, device)
         w.put(b"X\n" + struct.pack(">iIIi", 3, WRITER_VERSION, MIN_READER_VERSION, 5) + b"UTF-8")
