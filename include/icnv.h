@@ -1408,6 +1408,68 @@ int icnv_deflate_pieces_dev(const uint8_t *src, int64_t n, int64_t piece_bytes, 
 int icnv_deflate_pack_dev(const uint8_t *dst, int64_t dst_stride, const int32_t *piece_len, int64_t n_pieces, uint8_t *out,
                           int64_t out_cap, int64_t *out_len /* HOST */, void *stream);
 
+/* ---- INFLATE in independent units (K29) ---------------------------------------------------------------------------------------------
+ * The way back from K28's files: a raw DEFLATE stream (RFC 1951) that was written with flush points is inflated unit by unit,
+ * one wavefront per unit.  The stream carries no index of its units; the caller finds them with these four calls (the chain
+ * walk between them is host work on a few numbers per unit: infercnv_amd/rds.py, inflate_gzip).
+ *   candidate   an offset p of src with src[p - 4, p) = 00 00 FF FF: the byte behind a flush marker.  The caller adds the
+ *               stream's first byte.  A marker pattern inside compressed or stored data is a false candidate: it costs one
+ *               wasted measure and is never reached by the chain.
+ *   unit        starts at a candidate, on a byte boundary: the run of complete DEFLATE blocks from there up to and including
+ *               the first EMPTY stored block (LEN = 0: it ends the unit on a byte boundary behind a marker, so on a candidate)
+ *               or a block with BFINAL set (the unit ends on the next byte boundary).  Stored (non-empty ones are copied and
+ *               do not end the unit), fixed-Huffman and dynamic-Huffman blocks in any number.  A match reaches back anywhere
+ *               inside its own unit, up to 32 768 bytes; one that reaches before the unit's first output byte is NEEDS_HISTORY.
+ *   chain       the first unit ends where the second starts, and so on, up to the unit that ends with BFINAL.
+ *   status      DEVICE int32 per unit:
+ *     ICNV_INFLATE_OK_MARKER      ended by an empty stored block without BFINAL
+ *     ICNV_INFLATE_OK_FINAL       ended by a block with BFINAL
+ *     ICNV_INFLATE_TRUNCATED      ran into src + n
+ *     ICNV_INFLATE_TOO_LONG       needed more than max_in compressed bytes (the measure only)
+ *     ICNV_INFLATE_BAD_STREAM     BTYPE 11; stored LEN != ~NLEN; HLIT > 286 or HDIST > 30 symbols; an over-subscribed set of
+ *                                 code lengths, or an incomplete one -- except, for the literal/length and the distance code,
+ *                                 no code at all or one single code of length one (what zlib accepts); no code for symbol 256;
+ *                                 a repeat code 16 with nothing before it; lengths running past HLIT + HDIST; bits that are no
+ *                                 code; literal/length symbols 286 / 287; distance symbols 30 / 31; a distance code where the
+ *                                 block defines none.  The decode: any disagreement with the caller's end / out_len, an end
+ *                                 that comes too early included.
+ *     ICNV_INFLATE_NEEDS_HISTORY  a distance beyond the bytes the unit has produced so far
+ *               A malformed stream is an ordinary input: it ends in one of these, never in a fault.  Every load is tested
+ *               against [src, src + n) and every store against the unit's own output range before it is issued; every loop
+ *               takes at least one bit (a stored block: four bytes) of the unit's budget per round.
+ * icnv_inflate_scan_dev      cand (DEVICE int64 [cand_cap]) receives the candidates in [4, n] in ascending order, *n_cand (HOST)
+ *               their number.  Two passes (count, emit) compacted by ballot and prefix sums: no atomics.  The call WAITS on
+ *               `stream` for the count; when it exceeds cand_cap the call returns ICNV_ERR_ARG with *n_cand set and nothing
+ *               written to cand.
+ * icnv_inflate_measure_dev   parses the unit at every start[i] (DEVICE int64) without producing bytes: end[i], the offset just
+ *               behind the unit; out_len[i], the bytes it inflates to (both DEVICE int64; with a status other than OK_* they
+ *               hold where the parse stood); status[i].  max_in: the most compressed bytes a unit may take.
+ * icnv_inflate_units_dev     decodes unit i, src[start[i], end[i]), into out[out_off[i], out_off[i] + out_len[i]).  A unit
+ *               whose decode does not end exactly at end[i] with exactly out_len[i] bytes gets BAD_STREAM; its output range
+ *               holds unspecified bytes then, and nothing outside it was written.  Ranges of different units must not overlap
+ *               (not checked: the stores stay inside each unit's own range either way).
+ * icnv_crc32_pieces_dev      crc[i] (DEVICE uint32 [ceil(n / piece_bytes)]) = the CRC-32 (zlib's) of
+ *               src[i * piece_bytes, min(n, (i + 1) * piece_bytes)), any piece_bytes >= 1 -- what icnv_deflate_pieces_dev
+ *               computes of its input, for a buffer that is already there.  crc32_combine folds them (device.py).
+ * The outputs are functions of the inputs alone.  src needs no alignment.  n_units == 0 (n == 0 for the scan and the CRC) is a
+ * valid empty call.  The measure and the decode WAIT on `stream` once, for their check kernel's word; the CRC does not wait.
+ * ICNV_ERR_ARG before the kernel that does the work: a negative size; a null pointer with work to do; int64 arrays not aligned
+ *   to 8 bytes, int32 / uint32 arrays not to 4; piece_bytes < 1; and, by a small check kernel over the units, a start[i]
+ *   outside [0, n), and for the decode an end[i] outside [start[i], n] or an output range outside [0, out_cap].
+ * Timer names: "inflate_scan", "inflate_measure", "inflate_units", "crc32_pieces". */
+#define ICNV_INFLATE_OK_MARKER 0
+#define ICNV_INFLATE_OK_FINAL 1
+#define ICNV_INFLATE_TRUNCATED 2
+#define ICNV_INFLATE_TOO_LONG 3
+#define ICNV_INFLATE_BAD_STREAM 4
+#define ICNV_INFLATE_NEEDS_HISTORY 5
+int icnv_inflate_scan_dev(const uint8_t *src, int64_t n, int64_t *cand, int64_t cand_cap, int64_t *n_cand /* HOST */, void *stream);
+int icnv_inflate_measure_dev(const uint8_t *src, int64_t n, const int64_t *start, int64_t n_units, int64_t max_in, int64_t *end,
+                             int64_t *out_len, int32_t *status, void *stream);
+int icnv_inflate_units_dev(const uint8_t *src, int64_t n, const int64_t *start, const int64_t *end, const int64_t *out_off,
+                           const int64_t *out_len, int64_t n_units, uint8_t *out, int64_t out_cap, int32_t *status, void *stream);
+int icnv_crc32_pieces_dev(const uint8_t *src, int64_t n, int64_t piece_bytes, uint32_t *crc, void *stream);
+
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for
  * every (tile, chromosome) block -- tile = one tumour subcluster or one whole

@@ -37,6 +37,7 @@ REPORT_GENES, REPORT_REGIONS = 0, 1       # ICNV_REPORT_* kinds of icnv_cnv_repo
 MM_INTEGER, MM_REAL, MM_PATTERN = 0, 1, 2      # ICNV_MM_* fields of icnv_parse_triplets_dev
 CSC_SORTED, CSC_DUPLICATE, CSC_DESCENT = 0, 1, 2   # ICNV_CSC_* results of icnv_csc_from_sorted_triplets_dev
 XDR_COLS, XDR_ROWS = 0, 1                 # ICNV_XDR_* layouts of icnv_xdr_encode_dev / icnv_xdr_decode_dev
+INFLATE_OK_MARKER, INFLATE_OK_FINAL, INFLATE_TRUNCATED, INFLATE_TOO_LONG, INFLATE_BAD_STREAM, INFLATE_NEEDS_HISTORY = range(6)   # ICNV_INFLATE_*
 HSPIKE_GENES_TOKEN = 0x6873706B67656E65   # ICNV_HSPIKE_GENES_TOKEN: the stream of the hidden spike-in's genes_means_use_idx
 
 
@@ -218,6 +219,10 @@ PROTOTYPES = {
     "icnv_deflate_bound": (ct.c_int64, [_i64]),
     "icnv_deflate_pieces_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "icnv_deflate_pack_dev": (ct.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64p, _vp]),
+    "icnv_inflate_scan_dev": (ct.c_int, [_vp, _i64, _vp, _i64, _i64p, _vp]),
+    "icnv_inflate_measure_dev": (ct.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "icnv_inflate_units_dev": (ct.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "icnv_crc32_pieces_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

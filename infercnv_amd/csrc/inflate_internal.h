@@ -1,0 +1,347 @@
+// Shared between inflate_api.hip (validation), inflate_kernels.hip (K29: gzip streams with flush points inflated on the device,
+// one wavefront per unit) and inflate_host_check.cpp (the same parser on the host, under the sanitizers).  DESIGN.md section 4 K29.
+//
+// The block parser and the symbol decoder below are __host__ __device__ and free of HIP: a plain C++ compiler builds them.
+// The contract (include/icnv.h "INFLATE in independent units"):
+//   * every load of the compressed stream goes through IfReader, which never reads at or beyond `limit` <= n;
+//   * every store goes through if_put / the caller's copy of an IfOp, both tested against the unit's own out_cap;
+//   * every loop consumes at least one bit of the stream per round (a stored block: four bytes), so it ends with the budget.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/icnv.h"
+
+#if defined(__HIPCC__)
+#define IF_HD __host__ __device__
+#else
+#define IF_HD
+#endif
+
+namespace icnv {
+
+constexpr int IF_WAVES = 4;             // wavefronts of a workgroup: one unit per wavefront
+constexpr int IF_NT = IF_WAVES * 64;
+constexpr int IF_WIDE_MIN = 8;          // matches of at least this many bytes are copied by the whole wavefront
+constexpr int SC_NT = 256;              // scan: lanes of a workgroup
+constexpr int SC_ROUNDS = 16;           // scan: positions per lane; a workgroup covers SC_NT * SC_ROUNDS positions
+constexpr int CRC_SUB = 64;             // crc32_pieces: bytes a lane folds at a time; a wavefront covers 64 * CRC_SUB per round
+
+constexpr int IF_MAX_LIT = 286, IF_MAX_DIST = 30;    // the symbols a dynamic header may define (zlib's limits)
+
+struct IfTables {                       // canonical Huffman codes: counts per length, symbols in code order (1 KiB per wavefront)
+    uint16_t lcount[16], dcount[16];
+    uint16_t lsym[288], dsym[32];
+    uint8_t lens[320];                  // the code lengths while a header is parsed
+};
+
+struct IfReader {
+    const uint8_t *src;
+    int64_t limit;                      // bytes [0, limit) of src may be read: min(n, start + max_in)
+    int64_t p;                          // the next byte to load
+    uint64_t bb;                        // loaded bits, the stream's next bit at bit 0
+    int32_t bc;                         // how many
+    int32_t budget_cut;                 // limit < n: running dry is TOO_LONG, not TRUNCATED
+
+    IF_HD void refill() {               // at least 32 bits, or everything up to the limit
+        while (bc <= 56 && p < limit) {
+            bb |= (uint64_t)src[p++] << bc;
+            bc += 8;
+        }
+    }
+    IF_HD bool need(int k) {            // k <= 32
+        if (bc < k) refill();
+        return bc >= k;
+    }
+    IF_HD uint32_t take(int k) {        // after need(k)
+        const uint32_t v = (uint32_t)(bb & ((1ull << k) - 1));
+        bb >>= k;
+        bc -= k;
+        return v;
+    }
+    IF_HD int64_t bit_pos() const { return p * 8 - bc; }
+    IF_HD int64_t align_to_byte() {     // drops the rest of the current byte and the loaded bytes: returns the byte position
+        const int64_t q = (bit_pos() + 7) >> 3;
+        bb = 0;
+        bc = 0;
+        p = q;
+        return q;
+    }
+};
+
+struct IfState {
+    IfReader r;
+    int64_t out_pos;                    // bytes the unit has produced
+    int64_t end;                        // with a final status: the offset just behind the unit
+    int32_t in_block;                   // 1: inside a Huffman-coded block
+    int32_t last;                       // BFINAL of the current (or the latest) block
+    int32_t have_dist;                  // the block defines at least one distance code
+};
+
+enum { IF_OP_DONE = 0, IF_OP_MATCH = 1, IF_OP_STORED = 2 };
+struct IfOp {
+    int32_t kind;
+    int32_t len;                        // DONE: the status; MATCH / STORED: bytes to produce
+    int64_t a;                          // MATCH: the distance; STORED: the offset in src
+};
+
+IF_HD inline void if_init(IfState &s, const uint8_t *src, int64_t n, int64_t start, int64_t max_in) {
+    s.r.src = src;
+    s.r.limit = max_in < n - start ? start + max_in : n;
+    s.r.budget_cut = s.r.limit < n ? 1 : 0;
+    s.r.p = start;
+    s.r.bb = 0;
+    s.r.bc = 0;
+    s.out_pos = 0;
+    s.end = start;
+    s.in_block = 0;
+    s.last = 0;
+    s.have_dist = 0;
+}
+
+IF_HD inline int if_dry(const IfState &s) { return s.r.budget_cut ? ICNV_INFLATE_TOO_LONG : ICNV_INFLATE_TRUNCATED; }
+
+// count[1..15], sym[] from the n code lengths; returns the code space left over (> 0: incomplete, < 0: over-subscribed)
+IF_HD inline int if_construct(uint16_t *count, uint16_t *sym, int sym_cap, const uint8_t *lens, int n) {
+    for (int l = 0; l < 16; ++l) count[l] = 0;
+    for (int i = 0; i < n; ++i) count[lens[i] & 15]++;
+    int left = 1;
+    for (int l = 1; l < 16; ++l) {
+        left = (left << 1) - count[l];
+        if (left < 0) return left;
+    }
+    uint16_t offs[16];
+    offs[1] = 0;
+    for (int l = 1; l < 15; ++l) offs[l + 1] = (uint16_t)(offs[l] + count[l]);
+    for (int i = 0; i < n; ++i) {
+        const int l = lens[i] & 15;
+        if (l && offs[l] < sym_cap) sym[offs[l]++] = (uint16_t)i;
+    }
+    return left;
+}
+
+// The next symbol of a canonical code: >= 0, -1 when the bits are no code, -2 when the stream runs dry inside the code.
+IF_HD inline int if_symbol(IfReader &r, const uint16_t *count, const uint16_t *sym, int sym_cap) {
+    if (r.bc < 15) r.refill();
+    uint32_t bits = (uint32_t)r.bb;
+    const int avail = r.bc;
+    int code = 0, first = 0, index = 0;
+    for (int len = 1; len <= 15; ++len) {
+        if (len > avail) return -2;
+        code |= (int)(bits & 1u);
+        bits >>= 1;
+        const int c = count[len];
+        if (code - c < first) {
+            const int at = index + (code - first);
+            r.bb >>= len;
+            r.bc -= len;
+            return at < sym_cap ? sym[at] : -1;
+        }
+        index += c;
+        first += c;
+        first <<= 1;
+        code <<= 1;
+    }
+    return -1;
+}
+
+// zlib's rule for the literal/length and the distance code: complete, or no code at all, or one single code of length one
+IF_HD inline bool if_code_ok(int left, const uint16_t *count, int n) {
+    if (left < 0) return false;
+    if (left == 0) return true;
+    const int used = n - count[0];
+    return used == 0 || (used == 1 && count[1] == 1);
+}
+
+IF_HD inline int if_fixed_tables(IfTables &t) {
+    for (int i = 0; i < 288; ++i) t.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8);
+    if_construct(t.lcount, t.lsym, 288, t.lens, 288);
+    for (int i = 0; i < 32; ++i) t.lens[i] = 5;
+    if_construct(t.dcount, t.dsym, 32, t.lens, 32);
+    return 0;
+}
+
+// The header of a dynamic block into the tables: 0, or a final status.
+IF_HD inline int if_dynamic_tables(IfState &s, IfTables &t) {
+    IfReader &r = s.r;
+    if (!r.need(14)) return if_dry(s);
+    const int nlen = (int)r.take(5) + 257, ndist = (int)r.take(5) + 1, ncode = (int)r.take(4) + 4;
+    if (nlen > IF_MAX_LIT || ndist > IF_MAX_DIST) return ICNV_INFLATE_BAD_STREAM;
+    const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    for (int i = 0; i < 19; ++i) t.lens[i] = 0;
+    for (int i = 0; i < ncode; ++i) {
+        if (!r.need(3)) return if_dry(s);
+        t.lens[order[i]] = (uint8_t)r.take(3);
+    }
+    if (if_construct(t.lcount, t.lsym, 288, t.lens, 19) != 0) return ICNV_INFLATE_BAD_STREAM;   // the code-length code: complete
+    const int total = nlen + ndist;                                 // <= 316
+    int at = 0;
+    while (at < total) {                                            // every round takes at least one bit
+        const int sym = if_symbol(r, t.lcount, t.lsym, 288);
+        if (sym == -2) return if_dry(s);
+        if (sym < 0 || sym > 18) return ICNV_INFLATE_BAD_STREAM;
+        if (sym < 16) {
+            t.lens[at++] = (uint8_t)sym;
+            continue;
+        }
+        int value = 0, rep;
+        if (sym == 16) {
+            if (at == 0) return ICNV_INFLATE_BAD_STREAM;            // nothing to repeat
+            if (!r.need(2)) return if_dry(s);
+            value = t.lens[at - 1];
+            rep = 3 + (int)r.take(2);
+        } else if (sym == 17) {
+            if (!r.need(3)) return if_dry(s);
+            rep = 3 + (int)r.take(3);
+        } else {
+            if (!r.need(7)) return if_dry(s);
+            rep = 11 + (int)r.take(7);
+        }
+        if (at + rep > total) return ICNV_INFLATE_BAD_STREAM;      // lengths running past HLIT + HDIST
+        while (rep-- > 0) t.lens[at++] = (uint8_t)value;
+    }
+    if (t.lens[256] == 0) return ICNV_INFLATE_BAD_STREAM;           // a block that could never end
+    uint8_t dl[32];                                                 // the distance lengths: lcount / lsym are rebuilt over lens first
+    for (int i = 0; i < 32; ++i) dl[i] = i < ndist ? t.lens[nlen + i] : 0;
+    int left = if_construct(t.lcount, t.lsym, 288, t.lens, nlen);
+    if (!if_code_ok(left, t.lcount, nlen)) return ICNV_INFLATE_BAD_STREAM;
+    left = if_construct(t.dcount, t.dsym, 32, dl, ndist);
+    if (!if_code_ok(left, t.dcount, ndist)) return ICNV_INFLATE_BAD_STREAM;
+    s.have_dist = ndist - t.dcount[0] > 0 ? 1 : 0;
+    return 0;
+}
+
+IF_HD inline int if_finish(IfState &s, int status, int64_t end) {
+    s.end = end;
+    return status;
+}
+
+// Runs the unit from where it stands.  out == nullptr: measure -- nothing is stored, every match and stored block is only
+// counted.  Otherwise the bytes go to out[0, out_cap); a match of at least wide_min bytes and every stored block is handed
+// back as an IfOp for the caller to copy (the caller then adds op.len to s.out_pos and calls again).  Ends with IF_OP_DONE and
+// the status in op.len; s.end is set with the OK statuses.
+IF_HD inline void if_run(IfState &s, IfTables &t, uint8_t *out, int64_t out_cap, int wide_min, IfOp &op) {
+    IfReader &r = s.r;
+    op.kind = IF_OP_DONE;
+    op.a = 0;
+    for (;;) {
+        if (!s.in_block) {
+            if (s.last) { op.len = if_finish(s, ICNV_INFLATE_OK_FINAL, (r.bit_pos() + 7) >> 3); return; }
+            if (!r.need(3)) { op.len = if_dry(s); return; }
+            s.last = (int32_t)r.take(1);
+            const int type = (int)r.take(2);
+            if (type == 3) { op.len = ICNV_INFLATE_BAD_STREAM; return; }
+            if (type == 0) {
+                const int64_t q = r.align_to_byte();
+                if (q + 4 > r.limit) { op.len = if_dry(s); return; }
+                const int len = r.src[q] | (r.src[q + 1] << 8), nlen = r.src[q + 2] | (r.src[q + 3] << 8);
+                if ((len ^ 0xFFFF) != nlen) { op.len = ICNV_INFLATE_BAD_STREAM; return; }
+                r.p = q + 4;
+                if (len == 0) {                                     // the flush marker: the unit ends here
+                    op.len = if_finish(s, s.last ? ICNV_INFLATE_OK_FINAL : ICNV_INFLATE_OK_MARKER, r.p);
+                    return;
+                }
+                if (r.p + len > r.limit) { op.len = if_dry(s); return; }
+                r.p += len;
+                if (!out) { s.out_pos += len; continue; }
+                if (len > out_cap - s.out_pos) { op.len = ICNV_INFLATE_BAD_STREAM; return; }
+                op.kind = IF_OP_STORED;
+                op.len = len;
+                op.a = q + 4;
+                return;
+            }
+            if (type == 1) {
+                if_fixed_tables(t);
+                s.have_dist = 1;
+            } else {
+                const int rc = if_dynamic_tables(s, t);
+                if (rc) { op.len = rc; return; }
+            }
+            s.in_block = 1;
+        }
+        // ---- symbols of a Huffman-coded block: every round takes at least one bit
+        const int sym = if_symbol(r, t.lcount, t.lsym, 288);
+        if (sym == -2) { op.len = if_dry(s); return; }
+        if (sym < 0 || sym >= IF_MAX_LIT) { op.len = ICNV_INFLATE_BAD_STREAM; return; }
+        if (sym < 256) {
+            if (out) {
+                if (s.out_pos >= out_cap) { op.len = ICNV_INFLATE_BAD_STREAM; return; }
+                out[s.out_pos] = (uint8_t)sym;
+            }
+            ++s.out_pos;
+            continue;
+        }
+        if (sym == 256) { s.in_block = 0; continue; }
+        const int lc = sym - 257;                                   // 0 .. 28
+        int len;
+        if (lc < 8) len = 3 + lc;
+        else if (lc == 28) len = 258;
+        else {
+            const int eb = (lc >> 2) - 1;
+            if (!r.need(eb)) { op.len = if_dry(s); return; }
+            len = 3 + ((4 + (lc & 3)) << eb) + (int)r.take(eb);
+        }
+        if (!s.have_dist) { op.len = ICNV_INFLATE_BAD_STREAM; return; }
+        const int dc = if_symbol(r, t.dcount, t.dsym, 32);
+        if (dc == -2) { op.len = if_dry(s); return; }
+        if (dc < 0 || dc >= IF_MAX_DIST) { op.len = ICNV_INFLATE_BAD_STREAM; return; }
+        int64_t dist;
+        if (dc < 4) dist = dc + 1;
+        else {
+            const int eb = (dc >> 1) - 1;
+            if (!r.need(eb)) { op.len = if_dry(s); return; }
+            dist = 1 + ((2 + (dc & 1)) << eb) + (int)r.take(eb);
+        }
+        if (dist > s.out_pos) { op.len = ICNV_INFLATE_NEEDS_HISTORY; return; }
+        if (!out) { s.out_pos += len; continue; }
+        if (len > out_cap - s.out_pos) { op.len = ICNV_INFLATE_BAD_STREAM; return; }
+        if (len >= wide_min) {
+            op.kind = IF_OP_MATCH;
+            op.len = len;
+            op.a = dist;
+            return;
+        }
+        for (int k = 0; k < len; ++k, ++s.out_pos) out[s.out_pos] = out[s.out_pos - dist];
+    }
+}
+
+// A unit's ops on one thread: the host's way through if_run, and the measure pass of either side.
+IF_HD inline int if_unit_serial(const uint8_t *src, int64_t n, int64_t start, int64_t max_in, IfTables &t, uint8_t *out, int64_t out_cap,
+                                int64_t *end, int64_t *out_len) {
+    IfState s;
+    IfOp op;
+    if_init(s, src, n, start, max_in);
+    for (;;) {
+        if_run(s, t, out, out_cap, 1 << 30, op);
+        if (op.kind == IF_OP_DONE) break;
+        for (int k = 0; k < op.len; ++k) out[s.out_pos + k] = src[op.a + k];   // IF_OP_STORED: tested against out_cap and the limit
+        s.out_pos += op.len;
+    }
+    *end = s.end;
+    *out_len = s.out_pos;
+    return op.len;
+}
+
+struct InflateArgs {
+    const uint8_t *src;
+    int64_t n;
+    const int64_t *start;
+    int64_t n_units;
+    int64_t max_in;             // measure
+    int64_t *end;               // measure: written; units: read (const there)
+    int64_t *out_len;           // measure: written; units: read
+    const int64_t *out_off;     // units
+    uint8_t *out;               // units
+    int64_t out_cap;
+    int32_t *status;
+};
+
+#ifdef __HIPCC__
+int launch_inflate_scan_count(const uint8_t *src, int64_t n, int64_t n_blocks, int64_t *block_off, hipStream_t s);   // block_off[n_blocks]: the total
+int launch_inflate_scan_emit(const uint8_t *src, int64_t n, int64_t n_blocks, const int64_t *block_off, int64_t *cand, int64_t cand_cap, hipStream_t s);
+int launch_inflate_check(const InflateArgs &a, bool units, int32_t *bad, hipStream_t s);
+int launch_inflate_measure(const InflateArgs &a, hipStream_t s);
+int launch_inflate_units(const InflateArgs &a, hipStream_t s);
+int launch_crc32_pieces(const uint8_t *src, int64_t n, int64_t piece_bytes, int64_t n_pieces, uint32_t *crc, hipStream_t s);
+#endif
+
+}  // namespace icnv

@@ -1,0 +1,277 @@
+// K29 kernels: a gzip stream with flush points inflated in independent units, one wavefront per unit; the scan for the units'
+// possible starts; the CRC-32 of equal pieces of a buffer.  DESIGN.md section 4 K29; the contract is in include/icnv.h.
+//
+//   scan      a candidate is an offset p in [4, n] with src[p - 4, p) = 00 00 FF FF.  Two passes over workgroup tiles of
+//             SC_NT * SC_ROUNDS positions: count, a one-workgroup prefix sum of the counts, then emit -- per round the lanes'
+//             flags are ranked by ballot and popcount inside a wavefront and by the wavefronts' sums across the workgroup, so
+//             the list is ascending and no atomic is involved.  Every position reads its own four bytes: a marker that
+//             straddles a tile, a round or a wavefront is nothing special.
+//   measure   lane 0 of a wavefront walks its unit's bit stream with the parser of inflate_internal.h (the code tables, 1 KiB,
+//             in LDS), stores nothing, and reports where the unit ends, what it inflates to, and its status.
+//   units     the same walk with stores.  Lane 0 stores the literals and copies matches shorter than IF_WIDE_MIN itself; a
+//             longer match and every stored block is handed through LDS to all 64 lanes, which copy it together (a match
+//             whose distance is below its length is a periodic fill: byte k comes from offset k mod distance).  A
+//             workgroup-scope fence stands on either side of such a copy: the lanes of a wavefront share one L1.
+//   crc       one wavefront per piece; a lane folds CRC_SUB bytes at a time, moves its running CRC across the 63 other
+//             lanes' bytes with one fixed operator (crc32_combine's identity), and the 64 lanes' values are XOR-ed.
+#include "icnv_internal.h"
+#include "inflate_internal.h"
+
+namespace icnv {
+
+namespace {
+
+// ---- scan -------------------------------------------------------------------------------------------------------------------------------
+__device__ inline bool sc_is_candidate(const uint8_t *src, int64_t n, int64_t p) {     // p - 4 >= 0 and p - 1 < n are tested here
+    if (p < 4 || p > n) return false;
+    return src[p - 4] == 0x00 && src[p - 3] == 0x00 && src[p - 2] == 0xFF && src[p - 1] == 0xFF;
+}
+
+// The workgroup's exclusive rank of this lane's flag in lane order, and the workgroup's total.  s_w: SC_NT / 64 ints.
+__device__ inline int sc_rank(bool flag, int *s_w, int &total) {
+    const int t = threadIdx.x, lane = t & 63;
+    const unsigned long long b = __ballot(flag);
+    const int below = __popcll(b & ((1ull << lane) - 1ull));
+    __syncthreads();                                                // the sums of the round before have been read
+    if (lane == 0) s_w[t >> 6] = __popcll(b);
+    __syncthreads();
+    int base = 0;
+    total = 0;
+    for (int w = 0; w < SC_NT / 64; ++w) {
+        if (w < (t >> 6)) base += s_w[w];
+        total += s_w[w];
+    }
+    return base + below;
+}
+
+__global__ __launch_bounds__(SC_NT) void inflate_scan_count_kernel(const uint8_t *src, int64_t n, int64_t n_blocks, int64_t *block_off) {
+    __shared__ int s_w[SC_NT / 64];
+    const int64_t tile0 = (int64_t)blockIdx.x * (SC_NT * SC_ROUNDS);
+    int count = 0;
+    for (int r = 0; r < SC_ROUNDS; ++r) {
+        int total;
+        sc_rank(sc_is_candidate(src, n, tile0 + r * SC_NT + threadIdx.x), s_w, total);
+        count += total;
+    }
+    if (threadIdx.x == 0 && blockIdx.x < n_blocks) block_off[blockIdx.x] = count;
+}
+
+// one workgroup: block_off[i] becomes the sum of the counts before tile i, block_off[n_blocks] the total
+__global__ __launch_bounds__(1024) void inflate_scan_offsets_kernel(int64_t n_blocks, int64_t *block_off) {
+    __shared__ int64_t s_w[1024 / 64];
+    __shared__ int64_t s_carry;
+    const int t = threadIdx.x;
+    if (t == 0) s_carry = 0;
+    __syncthreads();
+    for (int64_t i0 = 0; i0 < n_blocks; i0 += 1024) {
+        const int64_t i = i0 + t;
+        const int64_t v = i < n_blocks ? block_off[i] : 0;
+        int64_t incl = v;
+        for (int dlt = 1; dlt < 64; dlt <<= 1) {
+            const int64_t u = __shfl_up(incl, dlt, 64);
+            if ((t & 63) >= dlt) incl += u;
+        }
+        if ((t & 63) == 63) s_w[t >> 6] = incl;
+        __syncthreads();
+        int64_t base = s_carry, total = 0;
+        for (int w = 0; w < 1024 / 64; ++w) {
+            if (w < (t >> 6)) base += s_w[w];
+            total += s_w[w];
+        }
+        if (i < n_blocks) block_off[i] = base + incl - v;
+        __syncthreads();
+        if (t == 0) s_carry += total;
+        __syncthreads();
+    }
+    if (t == 0) block_off[n_blocks] = s_carry;
+}
+
+__global__ __launch_bounds__(SC_NT) void inflate_scan_emit_kernel(const uint8_t *src, int64_t n, int64_t n_blocks, const int64_t *block_off,
+                                                                  int64_t *cand, int64_t cand_cap) {
+    __shared__ int s_w[SC_NT / 64];
+    if (blockIdx.x >= n_blocks) return;
+    const int64_t tile0 = (int64_t)blockIdx.x * (SC_NT * SC_ROUNDS);
+    int64_t at = block_off[blockIdx.x];
+    for (int r = 0; r < SC_ROUNDS; ++r) {
+        const int64_t p = tile0 + r * SC_NT + threadIdx.x;
+        const bool flag = sc_is_candidate(src, n, p);
+        int total;
+        const int rank = sc_rank(flag, s_w, total);
+        if (flag && at + rank >= 0 && at + rank < cand_cap) cand[at + rank] = p;
+        at += total;
+    }
+}
+
+// ---- argument check -------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void inflate_check_kernel(InflateArgs a, int units, int32_t *bad) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_units) return;
+    const int64_t st = a.start[i];
+    bool ok = st >= 0 && st < a.n;
+    if (units) {
+        const int64_t e = a.end[i], off = a.out_off[i], len = a.out_len[i];
+        ok = ok && e >= st && e <= a.n && off >= 0 && len >= 0 && off <= a.out_cap && len <= a.out_cap - off;
+    }
+    if (!ok) *bad = 1;                                              // every writer stores the same value
+}
+
+// ---- measure ----------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(IF_NT) void inflate_measure_kernel(InflateArgs a) {
+    __shared__ IfTables s_tab[IF_WAVES];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t u = (int64_t)blockIdx.x * IF_WAVES + w;
+    if (u >= a.n_units || lane != 0) return;
+    const int64_t start = a.start[u];
+    int64_t end = start, out_len = 0;
+    int status = ICNV_INFLATE_BAD_STREAM;
+    if (start >= 0 && start < a.n)                                  // (the check kernel has refused anything else)
+        status = if_unit_serial(a.src, a.n, start, a.max_in, s_tab[w], nullptr, INT64_MAX, &end, &out_len);
+    a.end[u] = end;
+    a.out_len[u] = out_len;
+    a.status[u] = status;
+}
+
+// ---- decode -----------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(IF_NT) void inflate_units_kernel(InflateArgs a) {
+    __shared__ IfTables s_tab[IF_WAVES];
+    __shared__ IfOp s_op[IF_WAVES];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t u = (int64_t)blockIdx.x * IF_WAVES + w;
+    if (u >= a.n_units) return;                                     // whole wavefronts leave: no workgroup barrier follows
+    const int64_t start = a.start[u], end = a.end[u], off = a.out_off[u], cap = a.out_len[u];
+    const bool sane = start >= 0 && start < a.n && end >= start && end <= a.n && off >= 0 && cap >= 0 && off <= a.out_cap && cap <= a.out_cap - off;
+    if (!sane) {                                                    // (the check kernel has refused it)
+        if (lane == 0) a.status[u] = ICNV_INFLATE_BAD_STREAM;
+        return;
+    }
+    uint8_t *out = a.out + off;
+    IfState s;
+    if_init(s, a.src, a.n, start, end - start);
+    int status;
+    for (;;) {                                                      // every round but the last consumes bits of the unit
+        if (lane == 0) {
+            IfOp op;
+            if_run(s, s_tab[w], out, cap, IF_WIDE_MIN, op);
+            s_op[w] = op;
+        }
+        __threadfence_block();                                      // lane 0's op and its stores are visible to the wavefront
+        const IfOp op = s_op[w];
+        if (op.kind == IF_OP_DONE) { status = op.len; break; }
+        const int64_t o = s.out_pos;                                // lane 0's value, broadcast below
+        const int64_t o0 = __shfl(o, 0, 64);
+        const int len = op.len;
+        if (len > 0 && len <= cap - o0) {                           // if_run has tested this; the store's own test all the same
+            if (op.kind == IF_OP_MATCH) {
+                const int64_t dist = op.a;
+                if (dist >= 1 && dist <= o0)
+                    for (int k = lane; k < len; k += 64) out[o0 + k] = out[o0 - dist + (dist >= len ? k : k % dist)];
+            } else if (op.a >= 0 && op.a + len <= a.n) {
+                for (int k = lane; k < len; k += 64) out[o0 + k] = a.src[op.a + k];
+            }
+        }
+        __threadfence_block();                                      // the copy is visible before lane 0 reads behind it
+        s.out_pos = o0 + len;
+    }
+    if (lane == 0) {
+        const bool ok = status == ICNV_INFLATE_OK_MARKER || status == ICNV_INFLATE_OK_FINAL;
+        if (ok && (s.end != end || s.out_pos != cap)) status = ICNV_INFLATE_BAD_STREAM;
+        if (status == ICNV_INFLATE_TOO_LONG) status = ICNV_INFLATE_BAD_STREAM;     // the budget was the caller's end: it is too early
+        a.status[u] = status;
+    }
+}
+
+// ---- CRC-32 of pieces -------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t CRC_POLY = 0xEDB88320u;
+
+__device__ inline uint32_t crc_mul(uint32_t a, uint32_t b) {       // a(x) * b(x) mod P, reflected: bit 31 is x^0
+    uint32_t p = 0;
+    for (int i = 0; i < 32; ++i) {
+        if (a & (0x80000000u >> i)) p ^= b;
+        b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
+    }
+    return p;
+}
+
+__device__ inline uint32_t crc_xpow8(uint64_t nbytes) {            // x^(8 * nbytes) mod P: at most 64 squarings
+    uint32_t r = 0x80000000u, b = 0x00800000u;                     // x^0, x^8
+    while (nbytes) {
+        if (nbytes & 1u) r = crc_mul(r, b);
+        b = crc_mul(b, b);
+        nbytes >>= 1;
+    }
+    return r;
+}
+
+__global__ __launch_bounds__(IF_NT) void crc32_pieces_kernel(const uint8_t *src, int64_t n, int64_t piece_bytes, int64_t n_pieces, uint32_t *crc) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * IF_WAVES + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * IF_WAVES;
+    const uint32_t across = crc_xpow8((uint64_t)64 * CRC_SUB);     // moves a CRC across one round of the wavefront
+    for (int64_t piece = wave; piece < n_pieces; piece += n_waves) {
+        const int64_t p0 = piece * piece_bytes;
+        const int64_t len = n - p0 < piece_bytes ? n - p0 : piece_bytes;       // 1 .. piece_bytes
+        uint32_t acc = 0;
+        int64_t prev_end = 0;
+        for (int64_t b0 = (int64_t)lane * CRC_SUB; b0 < len; b0 += (int64_t)64 * CRC_SUB) {
+            const int64_t b1 = b0 + CRC_SUB < len ? b0 + CRC_SUB : len;
+            uint32_t c = 0xFFFFFFFFu;
+            for (int64_t i = b0; i < b1; ++i) {                     // p0 + i < p0 + len <= n
+                c ^= src[p0 + i];
+                for (int j = 0; j < 8; ++j) c = (c >> 1) ^ (CRC_POLY & (0u - (c & 1u)));
+            }
+            c ^= 0xFFFFFFFFu;
+            if (prev_end) acc = crc_mul(b1 - prev_end == (int64_t)64 * CRC_SUB ? across : crc_xpow8((uint64_t)(b1 - prev_end)), acc);
+            acc ^= c;
+            prev_end = b1;
+        }
+        if (prev_end) acc = crc_mul(crc_xpow8((uint64_t)(len - prev_end)), acc);
+        for (int dlt = 32; dlt >= 1; dlt >>= 1) acc ^= __shfl_xor(acc, dlt, 64);
+        if (lane == 0) crc[piece] = acc;
+    }
+}
+
+}  // namespace
+
+int launch_inflate_scan_count(const uint8_t *src, int64_t n, int64_t n_blocks, int64_t *block_off, hipStream_t s) {
+    hipLaunchKernelGGL(inflate_scan_count_kernel, dim3((unsigned)n_blocks), dim3(SC_NT), 0, s, src, n, n_blocks, block_off);
+    ICNV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(inflate_scan_offsets_kernel, dim3(1), dim3(1024), 0, s, n_blocks, block_off);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_inflate_scan_emit(const uint8_t *src, int64_t n, int64_t n_blocks, const int64_t *block_off, int64_t *cand, int64_t cand_cap,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(inflate_scan_emit_kernel, dim3((unsigned)n_blocks), dim3(SC_NT), 0, s, src, n, n_blocks, block_off, cand, cand_cap);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_inflate_check(const InflateArgs &a, bool units, int32_t *bad, hipStream_t s) {
+    hipLaunchKernelGGL(inflate_check_kernel, dim3((unsigned)((a.n_units + 255) / 256)), dim3(256), 0, s, a, units ? 1 : 0, bad);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_inflate_measure(const InflateArgs &a, hipStream_t s) {
+    KernelTimer kt("inflate_measure", s);
+    hipLaunchKernelGGL(inflate_measure_kernel, dim3((unsigned)((a.n_units + IF_WAVES - 1) / IF_WAVES)), dim3(IF_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_inflate_units(const InflateArgs &a, hipStream_t s) {
+    KernelTimer kt("inflate_units", s);
+    hipLaunchKernelGGL(inflate_units_kernel, dim3((unsigned)((a.n_units + IF_WAVES - 1) / IF_WAVES)), dim3(IF_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+int launch_crc32_pieces(const uint8_t *src, int64_t n, int64_t piece_bytes, int64_t n_pieces, uint32_t *crc, hipStream_t s) {
+    KernelTimer kt("crc32_pieces", s);
+    const int64_t want = (n_pieces + IF_WAVES - 1) / IF_WAVES, cap = (int64_t)num_cus() * 16;
+    hipLaunchKernelGGL(crc32_pieces_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(IF_NT), 0, s, src, n, piece_bytes, n_pieces, crc);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
+}  // namespace icnv

@@ -2435,6 +2435,79 @@ def crc32_combine_pieces(crcs, piece_bytes, last_bytes=None):
     return crc32_combine(acc, last, last_bytes)
 
 
+# ------------------------------------------------------------------ INFLATE in independent units (DESIGN K29)
+def _is_vector(t, dtype):
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 1 and t.is_contiguous()
+
+
+def _bytes_vector(t, name):
+    if not (_is_bytes_tensor(t, 1) and (t.numel() <= 1 or t.stride(0) == 1)):
+        raise TypeError(f"{name} must be a contiguous one-dimensional CUDA uint8 tensor")
+    return int(t.numel())
+
+
+def inflate_scan(src, *, cand=None):
+    """icnv_inflate_scan_dev (DESIGN K29): the offsets p in [4, n] of the CUDA uint8 vector src with src[p - 4:p] = 00 00 FF FF,
+    ascending, as a CUDA int64 vector.  cand: a caller's int64 vector to fill (too small a one raises IcnvError, untouched);
+    by default one is sized from the count.  Waits for the stream."""
+    L = _lib.load()
+    n = _bytes_vector(src, "src")
+    own = cand is None
+    if own:
+        cand = torch.empty(max(1024, n >> 12), dtype=torch.int64, device=src.device)
+    if not _is_vector(cand, torch.int64):
+        raise TypeError("cand must be a contiguous CUDA int64 vector")
+    count = ct.c_int64(0)
+    rc = L.icnv_inflate_scan_dev(_ptr(src), n, _ptr(cand), int(cand.numel()), ct.byref(count), _stream())
+    if own and rc == _lib.ERR_ARG and count.value > cand.numel():          # nothing was written: once more with room for all
+        cand = torch.empty(count.value, dtype=torch.int64, device=src.device)
+        rc = L.icnv_inflate_scan_dev(_ptr(src), n, _ptr(cand), int(cand.numel()), ct.byref(count), _stream())
+    check(rc)
+    return cand[:count.value]
+
+
+def inflate_measure(src, start, max_in):
+    """icnv_inflate_measure_dev: the units that start at the offsets `start` (CUDA int64) of src, parsed without producing
+    bytes.  Returns (end, out_len, status): CUDA int64, int64, int32 (the INFLATE_* codes of _lib)."""
+    L = _lib.load()
+    n = _bytes_vector(src, "src")
+    if not _is_vector(start, torch.int64):
+        raise TypeError("start must be a contiguous CUDA int64 vector")
+    k = int(start.numel())
+    end = torch.empty(k, dtype=torch.int64, device=src.device)
+    out_len = torch.empty(k, dtype=torch.int64, device=src.device)
+    status = torch.empty(k, dtype=torch.int32, device=src.device)
+    check(L.icnv_inflate_measure_dev(_ptr(src), n, _ptr(start), k, int(max_in), _ptr(end), _ptr(out_len), _ptr(status), _stream()))
+    return end, out_len, status
+
+
+def inflate_units(src, start, end, out_off, out_len, out):
+    """icnv_inflate_units_dev: unit i, src[start[i]:end[i]], decoded into out[out_off[i]:out_off[i] + out_len[i]] (all CUDA
+    int64 vectors of one length; out a CUDA uint8 vector).  Returns the status vector (CUDA int32)."""
+    L = _lib.load()
+    n, cap = _bytes_vector(src, "src"), _bytes_vector(out, "out")
+    k = int(start.numel())
+    for name, t in (("start", start), ("end", end), ("out_off", out_off), ("out_len", out_len)):
+        if not (_is_vector(t, torch.int64) and t.numel() == k):
+            raise TypeError(f"{name} must be a contiguous CUDA int64 vector of {k} elements")
+    status = torch.empty(k, dtype=torch.int32, device=src.device)
+    check(L.icnv_inflate_units_dev(_ptr(src), n, _ptr(start), _ptr(end), _ptr(out_off), _ptr(out_len), k, _ptr(out), cap, _ptr(status), _stream()))
+    return status
+
+
+def crc32_pieces(src, piece_bytes):
+    """icnv_crc32_pieces_dev: the CRC-32 of every piece_bytes-sized piece of the CUDA uint8 vector src (the last one shorter), as
+    int32 bit patterns like deflate_pieces' -- what crc32_combine_pieces folds.  Does not synchronise."""
+    L = _lib.load()
+    n = _bytes_vector(src, "src")
+    piece_bytes = int(piece_bytes)
+    if piece_bytes < 1:
+        raise ValueError("piece_bytes must be at least 1")
+    crc = torch.empty(-(-n // piece_bytes), dtype=torch.int32, device=src.device)
+    check(L.icnv_crc32_pieces_dev(_ptr(src), n, piece_bytes, _ptr(crc), _stream()))
+    return crc
+
+
 # ------------------------------------------------------------------ timing hooks
 def timing_enable(on=True):
     """on: False / 0 off, True / 1 every kernel family, 2 only the hot launches "chain_apply" and "viterbi"."""

@@ -12,7 +12,9 @@ The format (R Internals, "Serialization Formats"), as written here
 ------------------------------------------------------------------
 XDR, version 3, uncompressed unless compress=True -- what saveRDS(compress = FALSE) writes; readRDS detects it.  With
 compress=True the same stream inside one gzip member, as saveRDS writes by default: put together by GzipAssembler from
-pieces compressed on the device where that route exists (DESIGN K28), by Python's GzipFile otherwise.
+pieces compressed on the device where that route exists (DESIGN K28), by Python's GzipFile otherwise.  Such a file is read
+back on the device too (inflate_gzip, DESIGN K29: its flush points make it a chain of independently inflatable units); any
+other gzip file -- R's, GzipFile's -- through the host's inflate.
 
   header   `X\\n`, int32 3, int32 writer version (0x00040000: R 4.0.0), int32 min-reader 0x00030500 (R 3.5.0),
            int32 5, `UTF-8`.  All integers big-endian.
@@ -507,6 +509,7 @@ class _Reader:
         self.buf, self.pos, self.n = buf, 0, len(buf)
         self.refs = []
         self.return_device = return_device and device_ok
+        self.windowed = isinstance(buf, _DeviceStream)        # the stream lies on the device (inflate_gzip)
 
     def need(self, k):
         if k < 0 or self.pos + k > self.n:
@@ -514,7 +517,7 @@ class _Reader:
 
     def int(self):
         self.need(4)
-        v = struct.unpack_from(">i", self.buf, self.pos)[0]
+        v = self.buf.int_at(self.pos) if self.windowed else struct.unpack_from(">i", self.buf, self.pos)[0]
         self.pos += 4
         return v
 
@@ -639,8 +642,13 @@ class _Reader:
         pos = self.pos
         self.pos += n * es
         if self.return_device and t != LGLSXP and n * es >= DEVICE_THRESHOLD:
-            return _decode_on_device(self.buf, pos, n, es)
-        v = np.frombuffer(self.buf, dtype=">f8" if t == REALSXP else ">i4", count=n, offset=pos)
+            if self.windowed and self.buf.tensor is not None:
+                return _decode_device_stream(self.buf.tensor, pos, n, es)
+            return _decode_on_device(self.buf[pos:pos + n * es] if self.windowed else self.buf, 0 if self.windowed else pos, n, es)
+        if self.windowed:
+            v = np.frombuffer(self.buf[pos:pos + n * es], dtype=">f8" if t == REALSXP else ">i4", count=n)
+        else:
+            v = np.frombuffer(self.buf, dtype=">f8" if t == REALSXP else ">i4", count=n, offset=pos)
         v = v.astype(v.dtype.newbyteorder("="))
         if t == LGLSXP:
             if (v == NA_INTEGER).any():
@@ -757,6 +765,271 @@ def _decode_on_device(buf, pos, n, es):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- gzip inflated on the device (K29)
+INFLATE_MAX_IN = 16 << 20           # the most compressed bytes one unit may take (inflate_gzip's max_in)
+INFLATE_CRC_PIECE = 1 << 16         # the pieces the inflated stream's CRC-32 is computed in
+WINDOW_BYTES = 4 << 20              # the host window of a device-resident stream
+_INFLATE_STATS = {"route": "none", "reason": "inflate_gzip has not run"}
+
+
+class _DeviceStream:
+    """The inflated stream where inflate_gzip left it, as the buffer _Reader parses: a host window of WINDOW_BYTES is fetched
+    on demand (everything but the payloads is small, and the payloads are decoded from `tensor` device to device).  fetch(lo,
+    hi) returns the bytes [lo, hi); tensor: the CUDA uint8 vector itself, or None (a stand-in without one)."""
+
+    def __init__(self, fetch, n, tensor=None):
+        self.fetch, self.n, self.tensor = fetch, int(n), tensor
+        self.lo, self.win = 0, memoryview(b"")
+
+    def __len__(self):
+        return self.n
+
+    def _window(self, pos, k):
+        """The offset in the window of stream byte pos, with k bytes from there inside it."""
+        if pos < self.lo or pos + k > self.lo + len(self.win):
+            self.lo = pos
+            self.win = memoryview(self.fetch(pos, min(self.n, pos + max(k, WINDOW_BYTES))))
+        return pos - self.lo
+
+    def int_at(self, pos):
+        o = self._window(pos, 4)                              # (first: it may replace the window)
+        return struct.unpack_from(">i", self.win, o)[0]
+
+    def __getitem__(self, s):
+        lo, hi, step = s.indices(self.n)
+        if step != 1:
+            raise ValueError("contiguous slices only")
+        k = max(hi - lo, 0)
+        if k > WINDOW_BYTES:                                  # a payload for the host: not through the window
+            return memoryview(self.fetch(lo, hi))
+        o = self._window(lo, k)
+        return self.win[o:o + k]
+
+
+def _decode_device_stream(stream, pos, n, es):
+    """n big-endian elements at byte pos of the CUDA uint8 vector `stream` as a native CUDA vector.  icnv_xdr_decode_dev wants
+    its source aligned to the element size and a payload's offset in the stream is arbitrary: the segment goes through an
+    aligned staging tensor, CHUNK_BYTES at a time, device to device."""
+    import torch
+    from . import device as dev
+    out = torch.empty(n, dtype=torch.float64 if es == 8 else torch.int32, device=stream.device)
+    per_chunk = max(1, min(CHUNK_BYTES, -(-n * es // 16) * 16) // es)
+    stage = torch.empty(per_chunk * es, dtype=torch.uint8, device=stream.device)
+    for e0 in range(0, n, per_chunk):
+        e1 = min(n, e0 + per_chunk)
+        k = (e1 - e0) * es
+        stage[:k].copy_(stream[pos + e0 * es:pos + e0 * es + k])
+        dev.xdr_decode(stage, out, e0=e0, e1=e1)
+    return out
+
+
+class _DeviceInflate:
+    """The device side of inflate_gzip: host arrays are numpy, `src` and `out` stay where upload / alloc put them."""
+
+    def upload(self, view):
+        """The bytes of a host buffer as a CUDA uint8 vector, through two pinned buffers."""
+        import torch
+        n = len(view)
+        src = torch.empty(n, dtype=torch.uint8, device="cuda")
+        host = np.frombuffer(view, dtype=np.uint8)
+        per = min(CHUNK_BYTES, max(n, 1))
+        pin = [torch.empty(per, dtype=torch.uint8, pin_memory=True) for _ in range(2 if n > per else 1)]
+        events = [None, None]
+        for i, o in enumerate(range(0, n, per)):
+            slot, k = i % 2, min(per, n - o)
+            if events[slot] is not None:
+                events[slot].synchronize()
+            pin[slot].numpy()[:k] = host[o:o + k]
+            src[o:o + k].copy_(pin[slot][:k], non_blocking=True)
+            events[slot] = torch.cuda.Event()
+            events[slot].record()
+        torch.cuda.synchronize()
+        return src
+
+    def scan(self, src):
+        from . import device as dev
+        return dev.inflate_scan(src).cpu().numpy()
+
+    def measure(self, src, start, max_in):
+        import torch
+        from . import device as dev
+        end, out_len, status = dev.inflate_measure(src, torch.from_numpy(start).to(src.device), max_in)
+        return end.cpu().numpy(), out_len.cpu().numpy(), status.cpu().numpy()
+
+    def alloc(self, src, nbytes):
+        import torch
+        return torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+
+    def units(self, src, start, end, out_off, out_len, out):
+        import torch
+        from . import device as dev
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(src.device)
+        return dev.inflate_units(src, up(start), up(end), up(out_off), up(out_len), out).cpu().numpy()
+
+    def crc32_pieces(self, out, piece_bytes):
+        from . import device as dev
+        return dev.crc32_pieces(out, piece_bytes).cpu().numpy()
+
+    def stream(self, out):
+        fetch = lambda lo, hi: out[lo:hi].cpu().numpy().tobytes()
+        return _DeviceStream(fetch, int(out.numel()), out)
+
+
+def _inflate_backend():
+    return _DeviceInflate()
+
+
+def _inflate_enabled():
+    """ICNV_INFLATE=0 (environment, read per call): gzip files are inflated on the host even where a GPU is present."""
+    return os.environ.get("ICNV_INFLATE", "1").strip() != "0"
+
+
+def inflate_stats():
+    """What the latest inflate_gzip did: route ("device", or "host" with the reason it gave up), decode_launched, candidates,
+    chain_units, false_candidates, compressed_bytes, inflated_bytes, and seconds per phase (upload, scan, measure, chain,
+    decode, crc)."""
+    return dict(_INFLATE_STATS, seconds=dict(_INFLATE_STATS.get("seconds", {})))
+
+
+def gzip_header_length(data):
+    """The bytes of a gzip member's header (RFC 1952): FEXTRA, FNAME, FCOMMENT and FHCRC are stepped over.  None when the bytes
+    are no deflate member's header, or end inside it."""
+    n = len(data)
+    if n < 10 or bytes(data[:3]) != b"\x1f\x8b\x08" or data[3] & 0xE0:
+        return None
+    flg, at = data[3], 10
+    if flg & 4:                                               # FEXTRA
+        if at + 2 > n:
+            return None
+        at += 2 + struct.unpack_from("<H", data, at)[0]
+    for bit in (8, 16):                                       # FNAME, FCOMMENT: zero-terminated
+        if flg & bit:
+            while at < n and data[at] != 0:
+                at += 1
+            at += 1
+    if flg & 2:                                               # FHCRC
+        at += 2
+    return at if at <= n else None
+
+
+def inflate_gzip(data, *, max_in=INFLATE_MAX_IN):
+    """The inflated stream of a one-member gzip file with flush points -- what write_rds(compress=True) writes on the device
+    route -- as a CUDA uint8 tensor (read_rds parses it from there through a _DeviceStream), inflated unit by unit on the
+    device (DESIGN K29; the contract of a unit is in include/icnv.h).  data: bytes, an mmap or a path.  The file
+    carries no index of its units, so: scan for the flush markers, measure the unit behind every candidate, walk the chain of
+    true units from the stream's first byte (end of one = start of the next, up to the unit with BFINAL, with exactly the
+    8-byte trailer behind it), decode the chain's units into their places, and check ISIZE and the CRC-32 (computed on the device
+    in pieces, folded on the host).  Returns None whenever that does not work out -- too few candidates for the file's size or a
+    single unit (no flush points: R's own files), a unit that needs history, is malformed, truncated or longer than max_in, a
+    second member, a wrong trailer -- and never raises for the file's content: the host route then succeeds or raises as it
+    always did.  inflate_stats() tells what happened."""
+    global _INFLATE_STATS
+    st = {"route": "host", "reason": "", "decode_launched": False, "candidates": 0, "chain_units": 0, "false_candidates": 0,
+          "compressed_bytes": 0, "inflated_bytes": 0, "seconds": {}}
+    _INFLATE_STATS = st
+    if isinstance(data, (str, os.PathLike)):
+        with open(data, "rb") as fh:
+            data = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if os.fstat(fh.fileno()).st_size else b""
+    out = _inflate_gzip(data, int(max_in), st)
+    if out is not None:
+        st["route"] = "device"
+    return out
+
+
+def _inflate_gzip(data, max_in, st):
+    def give_up(reason):
+        st["reason"] = reason
+        return None
+
+    clock = time.perf_counter
+    view = memoryview(data)
+    head = gzip_header_length(view)
+    if head is None:
+        return give_up("not a gzip header")
+    n = len(view) - head                                      # the raw stream and the trailer
+    st["compressed_bytes"] = len(view)
+    if n < 8 + 2:
+        return give_up("truncated file")
+    be = _inflate_backend()
+    t0 = clock()
+    src = be.upload(view[head:])
+    t1 = clock()
+    cand = np.asarray(be.scan(src), dtype=np.int64)
+    t2 = clock()
+    st["seconds"].update(upload=t1 - t0, scan=t2 - t1)
+    start = np.concatenate([np.zeros(1, dtype=np.int64), cand[cand < n - 8]])
+    st["candidates"] = int(start.size)
+    if start.size < 2 or start.size * max_in < n:             # some unit must be longer than max_in: a stream without flush points
+        return give_up("no flush points: no decode launched")
+    end, out_len, status = be.measure(src, start, max_in)
+    t3 = clock()
+    ok = status <= 1                                          # OK_MARKER, OK_FINAL
+    if ok.all() and np.array_equal(end[:-1], start[1:]) and (status[:-1] == 0).all():
+        chain = np.arange(start.size)                         # every candidate is a true unit
+    else:
+        nxt = np.searchsorted(start, end)
+        hit = (nxt < start.size) & (start[np.minimum(nxt, start.size - 1)] == end)
+        nxt_l, hit_l, st_l = nxt.tolist(), hit.tolist(), status.tolist()
+        chain, i = [], 0
+        while True:                                           # every step moves forward: end > start
+            chain.append(i)
+            if st_l[i] == 1:
+                break
+            if st_l[i] != 0:
+                return give_up(f"the unit at byte {head + int(start[i])} has status {_INFLATE_STATUS[st_l[i]]}: no decode launched")
+            if not hit_l[i] or nxt_l[i] <= i:
+                return give_up(f"the unit at byte {head + int(start[i])} does not end on a candidate: no decode launched")
+            i = nxt_l[i]
+        chain = np.asarray(chain, dtype=np.int64)
+    last = int(chain[-1])
+    st["seconds"].update(measure=t3 - t2, chain=clock() - t3)
+    st["chain_units"], st["false_candidates"] = int(chain.size), int(start.size - chain.size)
+    if status[last] != 1:
+        return give_up("the chain does not end with a final block: no decode launched")
+    if int(end[last]) != n - 8:
+        return give_up("the stream is not followed by exactly the 8-byte trailer (a second member?): no decode launched")
+    if chain.size < 2:
+        return give_up("one unit, no flush points: no decode launched")
+    c_start, c_end, c_len = start[chain], end[chain], out_len[chain]
+    c_off = np.cumsum(c_len) - c_len
+    total = int(c_len.sum())
+    crc, isize = struct.unpack("<II", bytes(view[len(view) - 8:]))
+    if isize != total & 0xFFFFFFFF:
+        return give_up("the trailer's ISIZE does not match: no decode launched")
+    st["inflated_bytes"] = total
+    t4 = clock()
+    out = be.alloc(src, total)
+    st["decode_launched"] = True
+    got = be.units(src, c_start, c_end, c_off, c_len, out)
+    t5 = clock()
+    st["seconds"].update(decode=t5 - t4)
+    if not np.array_equal(got, status[chain]):
+        return give_up("the decode disagrees with the measure")
+    from .device import crc32_combine_pieces
+    crcs = be.crc32_pieces(out, INFLATE_CRC_PIECE)
+    last_bytes = total - (len(crcs) - 1) * INFLATE_CRC_PIECE
+    st["seconds"].update(crc=clock() - t5)
+    if total and crc32_combine_pieces(crcs, INFLATE_CRC_PIECE, last_bytes) != crc:
+        return give_up("the trailer's CRC-32 does not match")
+    if not total and crc != 0:
+        return give_up("the trailer's CRC-32 does not match")
+    return out
+
+
+_INFLATE_STATUS = ("OK_MARKER", "OK_FINAL", "TRUNCATED", "TOO_LONG", "BAD_STREAM", "NEEDS_HISTORY")
+
+
+def _open_on_device(path):
+    """The _DeviceStream of a gzip file that inflate_gzip takes, or None: not gzip, no GPU, ICNV_INFLATE=0, or turned away."""
+    if not (_inflate_enabled() and _device_available()):
+        return None
+    with open(path, "rb") as fh:
+        if fh.read(2) != b"\x1f\x8b":
+            return None
+    out = inflate_gzip(path)
+    return None if out is None else _inflate_backend().stream(out)
+
+
 def _open_bytes(path):
     """(buffer, compressed?): the file's serialised bytes; an uncompressed file is mapped, not read."""
     with open(path, "rb") as fh:
@@ -781,8 +1054,12 @@ def read_rds(path, *, return_device=False):
     the byte offset of its flag word; a file that ends early raises ValueError.  return_device=True: REALSXP / INTSXP
     payloads of at least DEVICE_THRESHOLD bytes of an uncompressed or inflated file are decoded on the device
     (icnv_xdr_decode_dev); a matrix stays there and comes back as RDeviceMatrix of the (cols, rows) tensor, a plain vector is
-    copied back."""
-    buf, _ = _open_bytes(path)
+    copied back.  A gzip file is then first offered to inflate_gzip (DESIGN K29): one written with flush points -- ours, with
+    compress=True -- is inflated on the device and parsed from there, the payloads decoded device to device; any other falls
+    back to the host's inflate at once (ICNV_INFLATE=0 in the environment: always).  Both routes return the same values."""
+    buf = _open_on_device(path) if return_device else None
+    if buf is None:
+        buf, _ = _open_bytes(path)
     rd = _Reader(buf, return_device)
     container = rd.header()
     top = rd.item()
@@ -1059,7 +1336,7 @@ def load_infercnv_obj(path, *, return_device=False):
     """readRDS(path) as an InfercnvObject, from our files and from R's (.rds, or an .rda that holds one infercnv object).  A
     dgCMatrix becomes a scipy.sparse.csc_matrix; indices become 0-based; the names of the subcluster vectors are dropped (they
     are the cells' names).  A slot R allows but the mirror cannot hold raises ValueError naming the slot.
-    return_device=True: the matrix is decoded on the device (when the file is uncompressed and the matrix reaches
-    DEVICE_THRESHOLD; uploaded otherwise) and the pair (object with expr_data None, (cells, genes) CUDA float64 matrix) is
+    return_device=True: the matrix is decoded on the device (when it reaches DEVICE_THRESHOLD; uploaded otherwise -- a gzip
+    file with flush points, what compress=True writes, is inflated there as well: read_rds, inflate_gzip) and the pair (object with expr_data None, (cells, genes) CUDA float64 matrix) is
     returned, as sample_object(return_device=True) does."""
     return from_r(read_rds(path, return_device=return_device), return_device)
