@@ -1077,6 +1077,10 @@ void icnv_table_text_stats_reset(void);
  *
  * The chunk: n_bytes (1 .. 2^31 - 2) of text that consists of whole lines, without the file's header line (the caller reads
  * that).  text_dev is the DEVICE copy (16-byte aligned), text_host the HOST copy of the same bytes; the host flavour takes one.
+ * text_host may be NULL (K30: the chunk is a piece of a file that was inflated on the device): the library then fetches the
+ * chunk from text_dev itself, once, and only if a field the device pass does not certify or a refusal asks for it; the label
+ * ranges it returns then still include a label's enclosing quotes (the caller slices the labels it fetches).  The same holds
+ * for icnv_parse_table_cols_dev.
  * Grammar -- everything else is refused, nothing is quietly misparsed:
  *   lines     end in "\n" or "\r\n"; the last line may lack the terminator.  A line that is empty (or a lone "\r") is skipped.
  *   row       a label and n_cols numeric fields, separated by the one byte of `sep` (not a line end, not a quote).
@@ -1152,6 +1156,7 @@ int icnv_matrix_sum(const double *x, int64_t ld, int64_t G, int64_t C, double *s
  * icnv_parse_triplets_dev: a chunk of the BODY of a coordinate file (the caller reads the banner, the % comments and the size
  * line) to three int32 arrays.  text_dev is the DEVICE copy (16-byte aligned), text_host the HOST copy of the same n_bytes
  * (1 .. 2^31 - 2) of whole lines; the host copy is read only to word a refusal.
+ * text_host may be NULL: a refused chunk is then fetched from text_dev for that wording (icnv_parse_triplets_cols_dev too).
  * Grammar -- everything else is refused, nothing is quietly misparsed:
  *   lines     end in "\n" or "\r\n"; the last line may lack the terminator.  A line that is empty, a lone "\r" or only blanks
  *             (space, tab) is skipped.  Every other line is an entry; the k-th of the chunk goes to slot k of the arrays.
@@ -1469,6 +1474,71 @@ int icnv_inflate_measure_dev(const uint8_t *src, int64_t n, const int64_t *start
 int icnv_inflate_units_dev(const uint8_t *src, int64_t n, const int64_t *start, const int64_t *end, const int64_t *out_off,
                            const int64_t *out_len, int64_t n_units, uint8_t *out, int64_t out_cap, int32_t *status, void *stream);
 int icnv_crc32_pieces_dev(const uint8_t *src, int64_t n, int64_t piece_bytes, uint32_t *crc, void *stream);
+
+/* ---- INFLATE with unknown history (K30) ---------------------------------------------------------------------------------------------
+ * Any raw DEFLATE stream, written by any deflater without flush points (R's gzfile, Python's GzipFile, gzip, 10x), inflated in
+ * parallel: a second route, tried where K29's gives up.  The stream is src[0, n): the bytes between the gzip header and the
+ * 8-byte trailer.  Bit b of the stream is bit b & 7 of byte b >> 3.  W = 32 768.
+ *   candidate   a bit offset b where the bits read BFINAL = 0, BTYPE = 10 and the dynamic header behind them is accepted by the
+ *               rules K29 lists under BAD_STREAM, entirely inside the stream.  Fixed and stored blocks cannot be recognised:
+ *               they are no candidates and are decoded by the unit that runs into them.  A false candidate (the pattern inside
+ *               compressed or stored data) costs one wasted measure and is never reached by the chain.
+ *   unit        starts at bit s -- bit 0, or a candidate -- and decodes block after block.  It ends with
+ *     ICNV_GUNZIP_OK_BOUNDARY   ahead of a block header (not its own first) it stands on a bit offset that is in the candidate
+ *                               list handed to the call (a binary search: the list must ascend); end = that offset
+ *     ICNV_GUNZIP_OK_FINAL      behind a block with BFINAL; end = the bit offset rounded up to a whole byte
+ *     ICNV_GUNZIP_TRUNCATED     ran into src + n
+ *     ICNV_GUNZIP_TOO_LONG      needed a byte at or beyond (s >> 3) + max_in (the measure only)
+ *     ICNV_GUNZIP_BAD_STREAM    K29's causes; a distance beyond q + W (below); for the symbols call any disagreement with the
+ *                               caller's end / out_len.
+ *               There is no NEEDS_HISTORY.  The host walks end -> start from bit 0 (infercnv_amd/gunzip.py).
+ *   symbols     a unit produces out_len symbols of 16 bits.  A value below 256 is that byte.  0x8000 | w, w in [0, W), is "the
+ *               byte at position w of the W bytes in front of this unit's output" (w = W - 1: the byte just before it).  A
+ *               match of distance d that starts at unit position q produces for k = 0 .. len - 1 the symbol at unit position
+ *               q + k - d: when that is >= 0 the stored symbol, which may itself be a marker (an overlapping match over markers
+ *               repeats them), else the marker 0x8000 | (W + q + k - d).  d > q + W is BAD_STREAM.
+ *   places      unit i's symbols lie at sym[out_off[i], out_off[i] + out_len[i]) and its bytes at the same indices of out;
+ *               out_off are the prefix sums of out_len, from 0 (checked).
+ *   tails       goes through the units IN ORDER and resolves the last min(W, out_len[i]) symbols of unit i into out; a marker
+ *               reads out[out_off[i] - W + w].  By induction those bytes are final: the tails of the units before cover the W
+ *               bytes in front of a unit however short those units are.  A marker that points in front of byte 0 sets *bad and
+ *               writes nothing.  The only sequential step: one workgroup, at most W symbols per unit.
+ *   resolve     everything in front of the tails, all units in parallel, by the same rule into the same out.  Afterwards out
+ *               is the inflated stream (icnv_crc32_pieces_dev checks it).
+ *               A malformed stream is an ordinary input, as in K29: every load is tested against the stream's limit, every
+ *               store against the unit's own range of sym / out, and every loop takes at least one bit (a stored block: four
+ *               bytes) per round.
+ * icnv_gunzip_find_dev      cand (DEVICE int64 [cand_cap]) receives EVERY candidate in ascending order, *n_cand (HOST) their
+ *               number.  A lane per bit offset; count, prefix, emit: no atomics.  WAITS on `stream` for the count; when it
+ *               exceeds cand_cap the call returns ICNV_ERR_ARG with *n_cand set and nothing written to cand.
+ * icnv_gunzip_measure_dev   parses the unit at every start[i] (DEVICE int64, bits) without producing symbols: end[i] (bits),
+ *               out_len[i], status[i].  cand / n_cand: the stops.  max_in: the most compressed bytes a unit may take.
+ * icnv_gunzip_symbols_dev   decodes unit i into sym[out_off[i], out_off[i] + out_len[i]).  A unit whose decode does not end
+ *               exactly at end[i] with exactly out_len[i] symbols gets BAD_STREAM; nothing outside its range was written.
+ * icnv_gunzip_tails_dev     *bad (DEVICE int32) is set to 1 or left alone (the caller zeroes it); *markers (DEVICE int64)
+ *               receives the number of markers among the tails' symbols.
+ * icnv_gunzip_resolve_dev   *bad as above.
+ * The outputs are functions of the inputs alone.  src needs no alignment.  n_units == 0 is a valid empty call (n < 3 for the
+ * finder).  Every call but the finder WAITS on `stream` once, for its check kernel's word.
+ * ICNV_ERR_ARG before the kernel that does the work: a negative size; n beyond 2^40 (the finder: 2^32); a null pointer with work to do; int64
+ *   arrays not aligned to 8 bytes, int32 to 4, sym to 2; and, by a small check kernel over the units, a start[i] outside
+ *   [0, 8 n), an end[i] outside [start[i], 8 n], places that are not the prefix sums of out_len inside [0, sym_cap / out_cap].
+ * Timer names: "gunzip_find", "gunzip_measure", "gunzip_symbols", "gunzip_tails", "gunzip_resolve". */
+#define ICNV_GUNZIP_OK_BOUNDARY 0
+#define ICNV_GUNZIP_OK_FINAL 1
+#define ICNV_GUNZIP_TRUNCATED 2
+#define ICNV_GUNZIP_TOO_LONG 3
+#define ICNV_GUNZIP_BAD_STREAM 4
+int icnv_gunzip_find_dev(const uint8_t *src, int64_t n, int64_t *cand, int64_t cand_cap, int64_t *n_cand /* HOST */, void *stream);
+int icnv_gunzip_measure_dev(const uint8_t *src, int64_t n, const int64_t *cand, int64_t n_cand, const int64_t *start, int64_t n_units,
+                            int64_t max_in, int64_t *end, int64_t *out_len, int32_t *status, void *stream);
+int icnv_gunzip_symbols_dev(const uint8_t *src, int64_t n, const int64_t *cand, int64_t n_cand, const int64_t *start, const int64_t *end,
+                            const int64_t *out_off, const int64_t *out_len, int64_t n_units, uint16_t *sym, int64_t sym_cap, int32_t *status,
+                            void *stream);
+int icnv_gunzip_tails_dev(const uint16_t *sym, const int64_t *out_off, const int64_t *out_len, int64_t n_units, uint8_t *out, int64_t out_cap,
+                          int32_t *bad, int64_t *markers, void *stream);
+int icnv_gunzip_resolve_dev(const uint16_t *sym, const int64_t *out_off, const int64_t *out_len, int64_t n_units, uint8_t *out, int64_t out_cap,
+                            int32_t *bad, void *stream);
 
 /* ---- 2-D median denoise -------------------------------------------------- */
 /* apply_median_filtering / .median_filter (R/noise_reduction.R:43-113): for

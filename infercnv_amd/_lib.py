@@ -38,6 +38,7 @@ MM_INTEGER, MM_REAL, MM_PATTERN = 0, 1, 2      # ICNV_MM_* fields of icnv_parse_
 CSC_SORTED, CSC_DUPLICATE, CSC_DESCENT = 0, 1, 2   # ICNV_CSC_* results of icnv_csc_from_sorted_triplets_dev
 XDR_COLS, XDR_ROWS = 0, 1                 # ICNV_XDR_* layouts of icnv_xdr_encode_dev / icnv_xdr_decode_dev
 INFLATE_OK_MARKER, INFLATE_OK_FINAL, INFLATE_TRUNCATED, INFLATE_TOO_LONG, INFLATE_BAD_STREAM, INFLATE_NEEDS_HISTORY = range(6)   # ICNV_INFLATE_*
+GUNZIP_OK_BOUNDARY, GUNZIP_OK_FINAL, GUNZIP_TRUNCATED, GUNZIP_TOO_LONG, GUNZIP_BAD_STREAM = range(5)   # ICNV_GUNZIP_*
 HSPIKE_GENES_TOKEN = 0x6873706B67656E65   # ICNV_HSPIKE_GENES_TOKEN: the stream of the hidden spike-in's genes_means_use_idx
 
 
@@ -223,6 +224,11 @@ PROTOTYPES = {
     "icnv_inflate_measure_dev": (ct.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "icnv_inflate_units_dev": (ct.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "icnv_crc32_pieces_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "icnv_gunzip_find_dev": (ct.c_int, [_vp, _i64, _vp, _i64, _i64p, _vp]),
+    "icnv_gunzip_measure_dev": (ct.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "icnv_gunzip_symbols_dev": (ct.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "icnv_gunzip_tails_dev": (ct.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "icnv_gunzip_resolve_dev": (ct.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "icnv_group_means_dev": (ct.c_int, [_vp, _i64, _i64, _ip, _ip, _i32, _vp, _vp]),
     "icnv_gene_stats": (ct.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "icnv_gene_stats_dev": (ct.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),

@@ -44,6 +44,24 @@ struct DevBuf {  // RAII over the pool
     void release() { pool_free(p); p = nullptr; }
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
+// The host copy of a chunk of text that lies on the device (the parse entries of K21 / K22 / K26 read it for the fields the
+// device pass does not certify and for the text of a refusal): the caller's, or, when the caller passed none -- the chunk is a
+// piece of a file that was inflated on the device (K30) --, fetched here the first time something asks for it.
+struct HostText {
+    const uint8_t *given, *dev;
+    int64_t n;
+    hipStream_t s;
+    std::vector<uint8_t> own;
+    int get(const uint8_t *&text) {
+        if (!given && own.empty()) {
+            own.resize((size_t)n);
+            ICNV_HIP(hipMemcpyAsync(own.data(), dev, (size_t)n, hipMemcpyDeviceToHost, s));
+            ICNV_HIP(hipStreamSynchronize(s));
+        }
+        text = given ? given : own.data();
+        return ICNV_OK;
+    }
+};
 // n elements of host memory into a pool buffer on `s` (never an empty allocation; nothing is copied when n == 0)
 template <typename T>
 inline int upload(DevBuf &b, const T *host, size_t n, hipStream_t s) {

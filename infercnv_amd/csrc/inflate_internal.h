@@ -336,6 +336,24 @@ struct InflateArgs {
 };
 
 #ifdef __HIPCC__
+// The workgroup's exclusive rank of this lane's flag in lane order, and the workgroup's total.  s_w: SC_NT / 64 ints.
+__device__ inline int sc_rank(bool flag, int *s_w, int &total) {
+    const int t = threadIdx.x, lane = t & 63;
+    const unsigned long long b = __ballot(flag);
+    const int below = __popcll(b & ((1ull << lane) - 1ull));
+    __syncthreads();                                                // the sums of the round before have been read
+    if (lane == 0) s_w[t >> 6] = __popcll(b);
+    __syncthreads();
+    int base = 0;
+    total = 0;
+    for (int w = 0; w < SC_NT / 64; ++w) {
+        if (w < (t >> 6)) base += s_w[w];
+        total += s_w[w];
+    }
+    return base + below;
+}
+
+int launch_scan_offsets(int64_t n_blocks, int64_t *block_off, hipStream_t s);   // block_off[i]: the sum before i; block_off[n_blocks]: the total (K30's finder shares it)
 int launch_inflate_scan_count(const uint8_t *src, int64_t n, int64_t n_blocks, int64_t *block_off, hipStream_t s);   // block_off[n_blocks]: the total
 int launch_inflate_scan_emit(const uint8_t *src, int64_t n, int64_t n_blocks, const int64_t *block_off, int64_t *cand, int64_t cand_cap, hipStream_t s);
 int launch_inflate_check(const InflateArgs &a, bool units, int32_t *bad, hipStream_t s);

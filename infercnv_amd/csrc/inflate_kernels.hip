@@ -27,23 +27,6 @@ __device__ inline bool sc_is_candidate(const uint8_t *src, int64_t n, int64_t p)
     return src[p - 4] == 0x00 && src[p - 3] == 0x00 && src[p - 2] == 0xFF && src[p - 1] == 0xFF;
 }
 
-// The workgroup's exclusive rank of this lane's flag in lane order, and the workgroup's total.  s_w: SC_NT / 64 ints.
-__device__ inline int sc_rank(bool flag, int *s_w, int &total) {
-    const int t = threadIdx.x, lane = t & 63;
-    const unsigned long long b = __ballot(flag);
-    const int below = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();                                                // the sums of the round before have been read
-    if (lane == 0) s_w[t >> 6] = __popcll(b);
-    __syncthreads();
-    int base = 0;
-    total = 0;
-    for (int w = 0; w < SC_NT / 64; ++w) {
-        if (w < (t >> 6)) base += s_w[w];
-        total += s_w[w];
-    }
-    return base + below;
-}
-
 __global__ __launch_bounds__(SC_NT) void inflate_scan_count_kernel(const uint8_t *src, int64_t n, int64_t n_blocks, int64_t *block_off) {
     __shared__ int s_w[SC_NT / 64];
     const int64_t tile0 = (int64_t)blockIdx.x * (SC_NT * SC_ROUNDS);
@@ -234,6 +217,10 @@ __global__ __launch_bounds__(IF_NT) void crc32_pieces_kernel(const uint8_t *src,
 int launch_inflate_scan_count(const uint8_t *src, int64_t n, int64_t n_blocks, int64_t *block_off, hipStream_t s) {
     hipLaunchKernelGGL(inflate_scan_count_kernel, dim3((unsigned)n_blocks), dim3(SC_NT), 0, s, src, n, n_blocks, block_off);
     ICNV_HIP(hipGetLastError());
+    return launch_scan_offsets(n_blocks, block_off, s);
+}
+
+int launch_scan_offsets(int64_t n_blocks, int64_t *block_off, hipStream_t s) {
     hipLaunchKernelGGL(inflate_scan_offsets_kernel, dim3(1), dim3(1024), 0, s, n_blocks, block_off);
     ICNV_HIP(hipGetLastError());
     return ICNV_OK;

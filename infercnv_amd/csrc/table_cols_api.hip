@@ -69,6 +69,7 @@ int icnv_parse_table_cols_dev(const uint8_t *text_dev, const uint8_t *text_host,
 
     // the selected fields the parse pass did not certify, at most TP_FLAG_CAP per round: strtod here, the staged value replaced
     int64_t n_host = 0, rounds = 0;
+    HostText host{text_host, text_dev, n_bytes, s, {}};
     for (;;) {
         uint64_t words[2] = {0, 0};                                    // the error word, n_flagged
         ICNV_HIP(hipMemcpyAsync(words, a.error, sizeof words, hipMemcpyDeviceToHost, s));
@@ -84,16 +85,18 @@ int icnv_parse_table_cols_dev(const uint8_t *text_dev, const uint8_t *text_host,
         std::vector<int64_t> slot(n);
         std::vector<uint64_t> bits(n);
         uint64_t worst = words[0];                                     // the device's refusal, if any: the smallest offset wins
+        const uint8_t *text = nullptr;                                 // a flagged field or a refusal: the host copy is needed
+        if ((rc = host.get(text))) return rc;
         for (size_t i = 0; i < n; ++i) {
             if (fl[i].slot < 0 || fl[i].slot >= n_vals || fl[i].pos < 0 || fl[i].pos > n_bytes)
                 ICNV_FAIL(ICNV_ERR_HIP, "parse_table_cols: a flagged field lies outside the chunk (internal error)");
             slot[i] = fl[i].slot;
-            if (tp_host_field(text_host, n_bytes, fl[i].pos, a.sep, bits[i]) != TP_VALUE) {
+            if (tp_host_field(text, n_bytes, fl[i].pos, a.sep, bits[i]) != TP_VALUE) {
                 const uint64_t word = ((uint64_t)fl[i].pos << 8) | (uint64_t)TP_E_NUMBER;
                 if (word < worst) worst = word;
             }
         }
-        if (worst != TP_NO_ERROR) return tp_refusal(text_host, n_bytes, worst, a.sep, line0, n_cols);
+        if (worst != TP_NO_ERROR) return tp_refusal(text, n_bytes, worst, a.sep, line0, n_cols);
         DevBuf d_slot, d_bits;
         if ((rc = upload(d_slot, slot.data(), n, s)) || (rc = upload(d_bits, bits.data(), n, s)) ||
             (rc = launch_tp_patch(a, d_slot.as<int64_t>(), d_bits.as<uint64_t>(), (int32_t)n, s)))
@@ -116,7 +119,7 @@ int icnv_parse_table_cols_dev(const uint8_t *text_dev, const uint8_t *text_host,
     ICNV_HIP(hipStreamSynchronize(s));
     for (int64_t r = 0; r < a.n_rows; ++r) {
         int64_t b = ranges[(size_t)(2 * r)], e = ranges[(size_t)(2 * r + 1)];
-        tp_label_slice(text_host, b, e);
+        if (text_host) tp_label_slice(text_host, b, e);                // (no host copy: the caller slices the labels it fetches)
         label_ranges[2 * r] = b;
         label_ranges[2 * r + 1] = e;
     }

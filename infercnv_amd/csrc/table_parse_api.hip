@@ -20,7 +20,7 @@ std::atomic<int64_t> g_tp[7];   // calls, rows, fields, fields parsed on the hos
 
 int tp_validate(const void *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0,
                 const void *out, int64_t ld, int64_t row0, int64_t max_rows, const int64_t *label_ranges, const int64_t *n_rows) {
-    if (!text_dev || !text_host || !sep || !out || !label_ranges || !n_rows) ICNV_FAIL(ICNV_ERR_ARG, "parse_table: null argument");
+    if (!text_dev || !sep || !out || !label_ranges || !n_rows) ICNV_FAIL(ICNV_ERR_ARG, "parse_table: null argument");
     if (n_bytes < 1 || n_bytes > 0x7ffffffe) ICNV_FAIL(ICNV_ERR_ARG, "parse_table: a chunk has 1 .. 2^31 - 2 bytes");
     if (std::strlen(sep) != 1 || sep[0] == '\n' || sep[0] == '\r' || sep[0] == '"')
         ICNV_FAIL(ICNV_ERR_ARG, "parse_table: sep must be one byte other than a line end or a quote");
@@ -109,6 +109,7 @@ int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int6
 
     // the fields the parse pass did not certify, at most TP_FLAG_CAP per round: strtod here, the staged value replaced
     int64_t n_host = 0, rounds = 0;
+    HostText host{text_host, text_dev, n_bytes, s, {}};
     for (;;) {
         uint64_t words[2] = {0, 0};                                    // the error word, n_flagged
         ICNV_HIP(hipMemcpyAsync(words, a.error, sizeof words, hipMemcpyDeviceToHost, s));
@@ -124,16 +125,18 @@ int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int6
         std::vector<int64_t> slot(n);
         std::vector<uint64_t> bits(n);
         uint64_t worst = words[0];                                     // the device's refusal, if any: the smallest offset wins
+        const uint8_t *text = nullptr;                                 // a flagged field or a refusal: the host copy is needed
+        if ((rc = host.get(text))) return rc;
         for (size_t i = 0; i < n; ++i) {
             if (fl[i].slot < 0 || fl[i].slot >= n_vals || fl[i].pos < 0 || fl[i].pos > n_bytes)
                 ICNV_FAIL(ICNV_ERR_HIP, "parse_table: a flagged field lies outside the chunk (internal error)");
             slot[i] = fl[i].slot;
-            if (tp_host_field(text_host, n_bytes, fl[i].pos, a.sep, bits[i]) != TP_VALUE) {
+            if (tp_host_field(text, n_bytes, fl[i].pos, a.sep, bits[i]) != TP_VALUE) {
                 const uint64_t word = ((uint64_t)fl[i].pos << 8) | (uint64_t)TP_E_NUMBER;
                 if (word < worst) worst = word;
             }
         }
-        if (worst != TP_NO_ERROR) return tp_refused(text_host, n_bytes, worst, a.sep, line0, n_cols);
+        if (worst != TP_NO_ERROR) return tp_refused(text, n_bytes, worst, a.sep, line0, n_cols);
         DevBuf d_slot, d_bits;
         if ((rc = upload(d_slot, slot.data(), n, s)) || (rc = upload(d_bits, bits.data(), n, s)) ||
             (rc = launch_tp_patch(a, d_slot.as<int64_t>(), d_bits.as<uint64_t>(), (int32_t)n, s)))
@@ -154,7 +157,7 @@ int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int6
     ICNV_HIP(hipStreamSynchronize(s));
     for (int64_t r = 0; r < a.n_rows; ++r) {
         int64_t b = ranges[(size_t)(2 * r)], e = ranges[(size_t)(2 * r + 1)];
-        tp_label_slice(text_host, b, e);
+        if (text_host) tp_label_slice(text_host, b, e);                // (no host copy: the caller slices the labels it fetches)
         label_ranges[2 * r] = b;
         label_ranges[2 * r + 1] = e;
     }

@@ -15,7 +15,7 @@ extern "C" {
 int icnv_parse_triplets_cols_dev(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, int32_t field, int64_t n_rows, int64_t n_cols,
                                  int64_t line0, int32_t *row_dev, int32_t *col_dev, int32_t *val_dev, int64_t capacity, int64_t *n_entries,
                                  const int32_t *col_map_dev, int64_t n_cols_out, int64_t *n_seen, void *stream) {
-    if (!text_dev || !text_host || !n_entries || !col_map_dev || !n_seen) ICNV_FAIL(ICNV_ERR_ARG, "parse_triplets: null argument");
+    if (!text_dev || !n_entries || !col_map_dev || !n_seen) ICNV_FAIL(ICNV_ERR_ARG, "parse_triplets: null argument");
     if (n_bytes < 1 || n_bytes > 0x7ffffffe) ICNV_FAIL(ICNV_ERR_ARG, "parse_triplets: a chunk has 1 .. 2^31 - 2 bytes");
     if (reinterpret_cast<uintptr_t>(text_dev) & 15) ICNV_FAIL(ICNV_ERR_ARG, "parse_triplets: the device text must start on a 16-byte boundary");
     if (field != ICNV_MM_INTEGER && field != ICNV_MM_REAL && field != ICNV_MM_PATTERN)
@@ -63,7 +63,10 @@ int icnv_parse_triplets_cols_dev(const uint8_t *text_dev, const uint8_t *text_ho
     ICNV_HIP(hipStreamSynchronize(s));
     if (word != SC_NO_ERROR) {
         if ((int64_t)(word >> 8) >= n_bytes) ICNV_FAIL(ICNV_ERR_HIP, "parse_triplets: a refusal lies outside the chunk (internal error)");
-        ICNV_FAIL(ICNV_ERR_ARG, "parse_triplets: " + sc_describe(text_host, n_bytes, word, field, n_rows, n_cols, line0));
+        HostText host{text_host, text_dev, n_bytes, s, {}};
+        const uint8_t *text = nullptr;
+        if ((rc = host.get(text))) return rc;
+        ICNV_FAIL(ICNV_ERR_ARG, "parse_triplets: " + sc_describe(text, n_bytes, word, field, n_rows, n_cols, line0));
     }
 
     // the kept entries, in file order; the caller's arrays are written only when they hold them all

@@ -420,20 +420,26 @@ def table_parse_stats(reset=False):
     return dict(zip(TABLE_PARSE_STATS, (int(v) for v in out)))
 
 
+def _host_text_ptr(host):
+    """The host copy of a chunk for the parse entries, or NULL: the chunk is a piece of a file inflated on the device (K30), and
+    the library fetches it from text_dev if a field it cannot certify or a refusal asks for it."""
+    return None if host is None else ct.c_void_p(host.ctypes.data)
+
+
 def parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, line0=1):
     """icnv_parse_table_dev: the first n_bytes of `text_dev` (contiguous CUDA uint8) and of `text_host` (a contiguous uint8
     numpy array or CPU tensor with the same bytes) are whole lines of a table with out.shape[0] numeric columns; row i of them
     goes to out[:, row0 + i].  out: a CUDA float64 (n_cols, ld) tensor with contiguous rows.  Returns (rows found, int64 label
-    ranges [rows, 2] into the bytes).  On an IcnvError `out` is as it was.  Synchronises the stream."""
+    ranges [rows, 2] into the bytes).  text_host None: no host copy exists; the ranges then still include a label's quotes.  On an IcnvError `out` is as it was.  Synchronises the stream."""
     L = _lib.load()
     if not (isinstance(text_dev, torch.Tensor) and text_dev.is_cuda and text_dev.dtype == torch.uint8 and text_dev.dim() == 1
             and text_dev.is_contiguous()):
         raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
     host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
-    if not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
-        raise TypeError("text_host must be a contiguous one-dimensional uint8 array")
+    if host is not None and not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
+        raise TypeError("text_host must be a contiguous one-dimensional uint8 array, or None")
     n_bytes = int(n_bytes)
-    if n_bytes < 1 or n_bytes > text_dev.numel() or n_bytes > host.size:
+    if n_bytes < 1 or n_bytes > text_dev.numel() or (host is not None and n_bytes > host.size):
         raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
     n_cols, _, ld = _check_matrix_ld(out)
     row0, max_rows = int(row0), int(max_rows)
@@ -444,7 +450,7 @@ def parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, lin
     sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
     ranges = np.zeros((max_rows, 2), dtype=np.int64)
     n_rows = ct.c_int64(0)
-    check(L.icnv_parse_table_dev(_ptr(text_dev), ct.c_void_p(host.ctypes.data), n_bytes, sep_b, n_cols, int(line0), _ptr(out), int(ld), row0,
+    check(L.icnv_parse_table_dev(_ptr(text_dev), _host_text_ptr(host), n_bytes, sep_b, n_cols, int(line0), _ptr(out), int(ld), row0,
                                  max_rows, ranges.ctypes.data_as(ct.POINTER(ct.c_int64)), ct.byref(n_rows), _stream()))
     return int(n_rows.value), ranges[:int(n_rows.value)]
 
@@ -484,13 +490,13 @@ def parse_table_cols_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows
             and text_dev.is_contiguous()):
         raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
     host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
-    if not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
-        raise TypeError("text_host must be a contiguous one-dimensional uint8 array")
+    if host is not None and not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
+        raise TypeError("text_host must be a contiguous one-dimensional uint8 array, or None")
     if not (isinstance(col_map, torch.Tensor) and col_map.is_cuda and col_map.dtype == torch.int32 and col_map.dim() == 1
             and col_map.is_contiguous() and col_map.numel() >= 1):
         raise TypeError("col_map must be a contiguous one-dimensional CUDA int32 tensor")
     n_bytes = int(n_bytes)
-    if n_bytes < 1 or n_bytes > text_dev.numel() or n_bytes > host.size:
+    if n_bytes < 1 or n_bytes > text_dev.numel() or (host is not None and n_bytes > host.size):
         raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
     n_out, _, ld = _check_matrix_ld(out)
     row0, max_rows = int(row0), int(max_rows)
@@ -501,7 +507,7 @@ def parse_table_cols_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows
     sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
     ranges = np.zeros((max_rows, 2), dtype=np.int64)
     n_rows = ct.c_int64(0)
-    check(L.icnv_parse_table_cols_dev(_ptr(text_dev), ct.c_void_p(host.ctypes.data), n_bytes, sep_b, int(col_map.numel()), int(line0), _ptr(out),
+    check(L.icnv_parse_table_cols_dev(_ptr(text_dev), _host_text_ptr(host), n_bytes, sep_b, int(col_map.numel()), int(line0), _ptr(out),
                                       int(ld), row0, max_rows, ranges.ctypes.data_as(ct.POINTER(ct.c_int64)), ct.byref(n_rows), _ptr(col_map),
                                       n_out, _stream()))
     return int(n_rows.value), ranges[:int(n_rows.value)]
@@ -585,6 +591,158 @@ def _count_newlines(path, n_bytes):
     return count
 
 
+def _gunzip_text(path, stats):
+    """The inflated text of a .gz path as a CUDA uint8 vector where gunzip.gunzip takes it (DESIGN K30), else None;
+    stats["source"] says which: "device_gunzip", or "host" with the reason in stats["source_reason"]."""
+    from . import gunzip
+    stats["source"], stats["source_reason"] = "host", "not a .gz path"
+    if not str(path).endswith(".gz"):
+        return None
+    if not gunzip.enabled():
+        stats["source_reason"] = "switched off by ICNV_GUNZIP=0 or ICNV_INFLATE=0"
+        return None
+    text = gunzip.gunzip(path)
+    if text is None:
+        stats["source_reason"] = gunzip.gunzip_stats()["reason"]
+        return None
+    stats["source"], stats["source_reason"] = "device_gunzip", ""
+    return text
+
+
+def _dev_last_newline(text, lo, hi):
+    """Index of the last '\\n' of the CUDA vector text[lo:hi], or lo - 1: 64 KiB pieces are fetched from the end."""
+    while hi > lo:
+        a = max(lo, hi - (1 << 16))
+        hit = np.flatnonzero(text[a:hi].cpu().numpy() == 10)
+        if hit.size:
+            return a + int(hit[-1])
+        hi = a
+    return lo - 1
+
+
+def _dev_line_chunks(text, pos, cap, stats):
+    """(begin, end) of consecutive chunks of whole lines of text[pos:], each about cap bytes: longer where one line is."""
+    n = int(text.numel())
+    while pos < n:
+        span = cap
+        while True:
+            end = min(n, pos + span)
+            cut = n if end == n else _dev_last_newline(text, pos, end) + 1
+            if cut > pos:
+                break
+            span *= 2                                              # one line is longer than the chunk: look further
+            if "grown" in stats:
+                stats["grown"] += 1
+        yield pos, cut
+        pos = cut
+
+
+def _dev_aligned(text, a, b, stage):
+    """text[a:b] where the parse entries can take it -- on a 16-byte boundary: the view itself, or a device-to-device copy.
+    Returns (chunk, stage)."""
+    if (text.data_ptr() + a) % 16 == 0:
+        return text[a:b], stage
+    if stage is None or stage.numel() < b - a:
+        stage = torch.empty(b - a, dtype=torch.uint8, device=text.device)
+    stage[:b - a].copy_(text[a:b])
+    return stage[:b - a], stage
+
+
+def _dev_labels(chunk, ranges):
+    """The row names of a chunk that has no host copy: the label bytes gathered on the device, fetched in one piece, and the
+    enclosing quotes dropped here (what tp_label_slice does where there is a host copy)."""
+    lens = ranges[:, 1] - ranges[:, 0]
+    total = int(lens.sum())
+    raw = b""
+    if total:
+        lens_t = torch.from_numpy(lens).to(chunk.device)
+        first = torch.from_numpy(np.ascontiguousarray(ranges[:, 0])).to(chunk.device) - (torch.cumsum(lens_t, 0) - lens_t)
+        idx = torch.repeat_interleave(first, lens_t) + torch.arange(total, device=chunk.device)
+        raw = chunk[idx].cpu().numpy().tobytes()
+    out, o = [], 0
+    for k in lens.tolist():
+        out.append(_unquote(raw[o:o + k]).decode("utf-8", "surrogateescape"))
+        o += k
+    return out
+
+
+def _read_table_device(text, sep_b, cap0, sel, stats):
+    """read_table's body for a file that lies inflated on the device: (row names, header names as bytes, parts).  The header
+    and the first data line are fetched; the body goes to the parse entries as views or device-to-device copies of `text`."""
+    import time
+    dev, n = text.device, int(text.numel())
+    fetch = 1 << 16
+    while True:                                                    # the header line and the first line with data
+        head = text[:min(n, fetch)].cpu().numpy().tobytes()
+        lines = head.split(b"\n")
+        data = [l for l in lines[1:-1] if l not in (b"", b"\r")] if len(head) < n else [l for l in lines[1:] if l not in (b"", b"\r")]
+        if data or len(head) == n:
+            break
+        fetch *= 2
+    if not head:
+        raise ValueError("read_table: the file has no data row")
+    line = lines[0]
+    header_names = [_unquote(t) for t in (line[:-1] if line.endswith(b"\r") else line).split(sep_b)]
+    if not data:
+        raise ValueError("read_table: the file has no data row")
+    k = data[0].count(sep_b) + 1
+    if len(header_names) == k - 1:
+        col_names = header_names
+    elif len(header_names) == k and k >= 2:
+        col_names = header_names[1:]
+    else:
+        raise ValueError(f"read_table: the header has {len(header_names)} names, the first row has {k} fields")
+    n_cols = len(col_names)
+    if n_cols < 1:
+        raise ValueError("read_table: the table has no numeric column")
+    col_map = None if sel is None else _column_map(sel, n_cols, "read_table", dev)
+    row_names, parts, scratch, stage = [], [], None, None
+    for a, b in _dev_line_chunks(text, min(len(line) + 1, n), cap0, stats):
+        t0 = time.perf_counter()
+        chunk, stage = _dev_aligned(text, a, b, stage)
+        nb = b - a
+        max_rows = nb // (n_cols + 1) + 1                          # a row is at least its separators and its line end
+        if scratch is None or scratch.shape[1] < max_rows:
+            scratch = torch.empty((n_cols if sel is None else sel.size, max_rows), dtype=torch.float64, device=dev)
+
+        def parse(line0=1):
+            if col_map is None:
+                return parse_table_into(chunk, None, nb, sep_b, scratch, 0, max_rows, line0=line0)
+            return parse_table_cols_into(chunk, None, nb, sep_b, scratch, 0, max_rows, col_map, line0=line0)
+        try:
+            rows, ranges = parse()
+        except _lib.IcnvError as exc:
+            short = "max_rows" in str(exc)                         # more lines than full rows fit: some row is too short
+            if exc.code != _lib.ERR_ARG or not (short or "line " in str(exc)):
+                raise
+            if short:
+                max_rows = int((chunk == 10).sum()) + 1
+                scratch = torch.empty((scratch.shape[0], max_rows), dtype=torch.float64, device=dev)
+            parse(line0=1 + int((text[:a] == 10).sum()))           # the refusal again, with the file's line number
+            raise
+        stats["parse_s"] += time.perf_counter() - t0
+        if rows:
+            parts.append(scratch[:, :rows].clone())
+            row_names += _dev_labels(chunk, ranges)
+        stats["chunks"] += 1
+    stats["bytes"] = n
+    return row_names, col_names, parts
+
+
+def _table_result(row_names, col_names, parts, stats, before, t_start):
+    import time
+    if not parts:
+        raise ValueError("read_table: the file has no data row")
+    x = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+    x = x.contiguous()
+    col_names = [c.decode("utf-8", "surrogateescape") for c in col_names]
+    after = table_parse_stats()
+    stats.update({k: after[k] - before[k] for k in TABLE_PARSE_STATS})
+    torch.cuda.synchronize()                                       # the last chunk's copy and the concatenation are part of the total
+    stats["wall_s"] = time.perf_counter() - t_start
+    return row_names, col_names, x, stats
+
+
 def read_table(path, sep="\t", chunk_bytes=None, cells=None):
     """read.table(path, sep = sep, header = TRUE, row.names = 1, check.names = FALSE) of a numeric table, parsed on the device
     (icnv_parse_table_dev, DESIGN K21; the grammar and what is refused: include/icnv.h "count matrices from text").
@@ -595,8 +753,14 @@ def read_table(path, sep="\t", chunk_bytes=None, cells=None):
     The header line is read here: it has one name per numeric column, as write.table writes it, or one more with a corner
     label in front.  Quotes around a name are dropped.  The body is streamed in chunks of whole lines through two pinned and two
     device buffers: a thread reads chunk i + 1 from the file while chunk i is copied and parsed; a buffer grows when one line
-    is longer than chunk_bytes.  A path that ends in .gz is decompressed by Python's gzip into the same pinned chunks
-    (R/inferCNV.R:146-150 reads it through gzfile); .rds is not read (NotImplementedError).  A refused byte raises IcnvError
+    is longer than chunk_bytes.  A path that ends in .gz (R/inferCNV.R:146-150 reads it through gzfile) is first offered to
+    gunzip.gunzip (DESIGN K30): a one-member gzip file of at least gunzip.GUNZIP_MIN_BYTES is inflated on the device, its header
+    line and first data line are fetched, and the body goes to the same parse entries in chunks of whole lines that are views or
+    device-to-device copies of the inflated tensor -- it does not cross PCIe (the last newline of a chunk is looked for in 64 KiB
+    pieces; the row names are gathered on the device and fetched; a chunk comes to the host only when it holds a field the
+    device pass cannot certify, or is refused).  stats["source"] is then "device_gunzip"; any other file -- stats["source"]
+    "host", stats["source_reason"] why -- is decompressed by Python's gzip into the pinned chunks.  Both routes return the same
+    values and the same refusals.  .rds is not read (NotImplementedError).  A refused byte raises IcnvError
     with the file line and the field.
 
     cells (DESIGN K26): a list of 0-based numeric file columns, in any order, without repeats (ValueError before the file is
@@ -619,9 +783,12 @@ def read_table(path, sep="\t", chunk_bytes=None, cells=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     stats = {"bytes": 0, "chunks": 0, "read_s": 0.0, "parse_s": 0.0, "stall_s": 0.0, "grown": 0}
     before = table_parse_stats()
+    t_start = time.perf_counter()
+    text = _gunzip_text(path, stats)
+    if text is not None:                                           # K30: the file lies inflated on the device; the body stays there
+        return _table_result(*_read_table_device(text, sep_b, cap0, sel, stats), stats, before, t_start)
     jobs, free, failure = queue.Queue(), [threading.Semaphore(1), threading.Semaphore(1)], []
     stop = threading.Event()
-    t_start = time.perf_counter()
     pin = [_pinned(cap0), _pinned(cap0)]
 
     def reader():
@@ -772,16 +939,9 @@ def read_table(path, sep="\t", chunk_bytes=None, cells=None):
         thread.join()
     if failure:
         raise failure[0]
-    if n_cols is None or not parts:
-        raise ValueError("read_table: the file has no data row")
-    x = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
-    x = x.contiguous()
-    col_names = [c.decode("utf-8", "surrogateescape") for c in col_names]
-    after = table_parse_stats()
-    stats.update({k: after[k] - before[k] for k in TABLE_PARSE_STATS})
-    torch.cuda.synchronize()                                       # the last chunk's copy and the concatenation are part of the total
-    stats["wall_s"] = time.perf_counter() - t_start
-    return row_names, col_names, x, stats
+    if n_cols is None:
+        parts = []
+    return _table_result(row_names, col_names, parts, stats, before, t_start)
 
 
 def smooth_chain_windows(x, chr_start, ref_groups, table, max_thresh=3.0, use_bounds=True, sd_amplifier=1.5, noise_filter=None,
@@ -1917,10 +2077,10 @@ def parse_triplets_into(text_dev, text_host, n_bytes, field, G, C, row, col, val
             and text_dev.is_contiguous()):
         raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
     host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
-    if not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
-        raise TypeError("text_host must be a contiguous one-dimensional uint8 array")
+    if host is not None and not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
+        raise TypeError("text_host must be a contiguous one-dimensional uint8 array, or None")
     n_bytes, offset = int(n_bytes), int(offset)
-    if n_bytes < 1 or n_bytes > text_dev.numel() or n_bytes > host.size:
+    if n_bytes < 1 or n_bytes > text_dev.numel() or (host is not None and n_bytes > host.size):
         raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
     for t in (row, col, val):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
@@ -1931,7 +2091,7 @@ def parse_triplets_into(text_dev, text_host, n_bytes, field, G, C, row, col, val
     capacity = row.numel() - offset
     at = [ct.c_void_p(t.data_ptr() + 4 * offset) if capacity else ct.c_void_p(0) for t in (row, col, val)]
     n = ct.c_int64(0)
-    check(L.icnv_parse_triplets_dev(_ptr(text_dev), ct.c_void_p(host.ctypes.data), n_bytes, int(field), int(G), int(C), int(line0), at[0], at[1],
+    check(L.icnv_parse_triplets_dev(_ptr(text_dev), _host_text_ptr(host), n_bytes, int(field), int(G), int(C), int(line0), at[0], at[1],
                                     at[2], capacity, ct.byref(n), _stream()))
     return int(n.value)
 
@@ -1946,13 +2106,13 @@ def parse_triplets_cols_into(text_dev, text_host, n_bytes, field, G, C, row, col
             and text_dev.is_contiguous()):
         raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
     host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
-    if not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
-        raise TypeError("text_host must be a contiguous one-dimensional uint8 array")
+    if host is not None and not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
+        raise TypeError("text_host must be a contiguous one-dimensional uint8 array, or None")
     if not (isinstance(col_map, torch.Tensor) and col_map.is_cuda and col_map.dtype == torch.int32 and col_map.dim() == 1
             and col_map.is_contiguous() and col_map.numel() == int(C)):
         raise TypeError("col_map must be a contiguous CUDA int32 vector with one entry per column of the matrix")
     n_bytes, offset = int(n_bytes), int(offset)
-    if n_bytes < 1 or n_bytes > text_dev.numel() or n_bytes > host.size:
+    if n_bytes < 1 or n_bytes > text_dev.numel() or (host is not None and n_bytes > host.size):
         raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
     for t in (row, col, val):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
@@ -1963,7 +2123,7 @@ def parse_triplets_cols_into(text_dev, text_host, n_bytes, field, G, C, row, col
     capacity = row.numel() - offset
     at = [ct.c_void_p(t.data_ptr() + 4 * offset) if capacity else ct.c_void_p(0) for t in (row, col, val)]
     kept, seen = ct.c_int64(0), ct.c_int64(0)
-    check(L.icnv_parse_triplets_cols_dev(_ptr(text_dev), ct.c_void_p(host.ctypes.data), n_bytes, int(field), int(G), int(C), int(line0), at[0],
+    check(L.icnv_parse_triplets_cols_dev(_ptr(text_dev), _host_text_ptr(host), n_bytes, int(field), int(G), int(C), int(line0), at[0],
                                          at[1], at[2], capacity, ct.byref(kept), _ptr(col_map), int(n_cols_out), ct.byref(seen), _stream()))
     return int(kept.value), int(seen.value)
 
@@ -1992,6 +2152,38 @@ def _count_entries(path, skip_bytes):
     return count
 
 
+def _mtx_result(row, col, val, filled, seen, nnz, G, C, sel, offset, stats, t_start):
+    """read_mtx behind its chunk loop: the entry count against the size line, the CSC arrays, the sort where it is needed."""
+    import time
+    if sel is None:
+        seen = filled
+    if seen != nnz:
+        raise ValueError(f"read_mtx: the size line says {nnz} entries, the body has {seen}")
+    stats["bytes"], stats["entries"] = offset, seen
+    if sel is not None:
+        stats["entries_kept"] = filled
+        row, col, val = (t[:filled].clone() if t.numel() > filled else t for t in (row, col, val))
+        C = int(sel.size)
+    colptr, first, kind = csc_from_sorted_triplets(row, col, G, C)
+    if kind == _lib.CSC_DESCENT:
+        key, perm = torch.sort(col.to(torch.int64) * G + row)
+        del key
+        row, col, val = row[perm], col[perm], val[perm]
+        del perm
+        stats["sorted_on_device"] = 1
+        colptr, first, kind = csc_from_sorted_triplets(row, col, G, C)
+        if kind == _lib.CSC_DESCENT:
+            raise RuntimeError("read_mtx: the sorted triplets are not in order (internal error)")
+    if kind == _lib.CSC_DUPLICATE:
+        column = int(col[first]) if sel is None else int(sel[int(col[first])])         # the file's column
+        raise ValueError(f"duplicate entry for row {int(row[first]) + 1}, column {column + 1}")
+    del col
+    counts = DeviceCounts(G, C, colptr=colptr, rowidx=row, vals=val)
+    torch.cuda.synchronize()
+    stats["wall_s"] = time.perf_counter() - t_start
+    return counts, stats
+
+
 def read_mtx(path, chunk_bytes=None, cells=None):
     """A MatrixMarket coordinate file (10x: matrix.mtx, or .gz) to a CSC DeviceCounts, parsed on the device
     (icnv_parse_triplets_dev, icnv_csc_from_sorted_triplets_dev; DESIGN K22; the grammar and what is refused: include/icnv.h
@@ -1999,7 +2191,12 @@ def read_mtx(path, chunk_bytes=None, cells=None):
 
     The banner, the % comment lines and the size line `G C nnz` are read here; only `%%MatrixMarket matrix coordinate
     {integer|real|pattern} general` is accepted (ValueError names the banner field otherwise).  The body is streamed in chunks
-    of whole lines through two pinned buffers and a device buffer while a thread reads ahead; .gz goes through Python's gzip.
+    of whole lines through two pinned buffers and a device buffer while a thread reads ahead.  A .gz path is first offered to
+    gunzip.gunzip (DESIGN K30): a one-member gzip file of at least gunzip.GUNZIP_MIN_BYTES is inflated on the device, its header
+    lines are fetched, and the body goes to the same parse entries in chunks of whole lines that are views or device-to-device
+    copies of the inflated tensor -- it does not cross PCIe (a chunk's last newline is looked for in 64 KiB pieces; a refused
+    chunk is fetched for the refusal's text).  stats["source"] is then "device_gunzip"; any other .gz -- stats["source"] "host",
+    stats["source_reason"] why -- goes through Python's gzip.  Both routes return the same values and the same refusals.
     The triplet arrays are allocated once from the size line, every chunk parses into its offset, and an entry count other than
     the size line's is a ValueError with both numbers.  A refused byte raises IcnvError with the file line and the field.
 
@@ -2020,6 +2217,7 @@ def read_mtx(path, chunk_bytes=None, cells=None):
     stats["entries"] is that number, stats["entries_kept"] the entries of the result and stats["arrays_grown"] the reallocations.  A selection that is ascending keeps
     a column-major file sorted; any other one goes through the torch.sort path."""
     import gzip
+    import io
     import queue
     import re
     import threading
@@ -2030,12 +2228,28 @@ def read_mtx(path, chunk_bytes=None, cells=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     stats = {"bytes": 0, "chunks": 0, "entries": 0, "sorted_on_device": 0, "read_s": 0.0, "parse_s": 0.0, "stall_s": 0.0}
     t_start = time.perf_counter()
-    f = gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")
-    try:
-        field, G, C, nnz, header_lines, header_bytes = _mtx_header(f)
-    except BaseException:
-        f.close()
-        raise
+    text = _gunzip_text(path, stats)
+    if text is not None:                                           # K30: the header lines are fetched, growing the window if need be
+        window = 1 << 16
+        while True:
+            f = io.BytesIO(text[:window].cpu().numpy().tobytes())
+            whole = window >= text.numel()
+            try:
+                header = _mtx_header(f)
+                if whole or header[5] < window:
+                    break
+            except ValueError:
+                if whole:
+                    raise
+            window *= 2
+        field, G, C, nnz, header_lines, header_bytes = header
+    else:
+        f = gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")
+        try:
+            field, G, C, nnz, header_lines, header_bytes = _mtx_header(f)
+        except BaseException:
+            f.close()
+            raise
     jobs, free, failure = queue.Queue(), [threading.Semaphore(1), threading.Semaphore(1)], []
     stop = threading.Event()
     pin = [_pinned(cap0), _pinned(cap0)]
@@ -2102,6 +2316,44 @@ def read_mtx(path, chunk_bytes=None, cells=None):
                     new[:filled].copy_(old[:filled])
                 row, col, val = grown
                 stats["arrays_grown"] += 1
+
+    def consume(chunk, host, n):
+        """One chunk of whole lines (on the device; host: the same bytes, or None) into the triplet arrays."""
+        nonlocal filled, seen
+        try:
+            if sel is None:
+                filled += parse_triplets_into(chunk, host, n, field, G, C, row, col, val, filled)
+            else:
+                kept, in_chunk = parse_selected(chunk, host, n)
+                filled, seen = filled + kept, seen + in_chunk
+        except _lib.IcnvError as exc:
+            if exc.code != _lib.ERR_ARG or not ("capacity" in str(exc) or "line " in str(exc)):
+                raise
+            if "capacity" in str(exc):
+                raise ValueError(f"read_mtx: the size line says {nnz} entries, the body has "
+                                 f"{_count_entries(path, header_bytes)}") from None
+            line0 = 1 + _count_newlines(path, header_bytes + offset)      # the refusal again, with the file's line number
+            if sel is None:
+                parse_triplets_into(chunk, host, n, field, G, C, row, col, val, filled, line0=line0)
+            else:
+                parse_selected(chunk, host, n, line0=line0)
+            raise
+
+    if text is not None:                                           # K30: the body stays on the device
+        stage = None
+        try:
+            for a, b in _dev_line_chunks(text, header_bytes, cap0, stats):
+                t0 = time.perf_counter()
+                chunk, stage = _dev_aligned(text, a, b, stage)
+                offset = a - header_bytes
+                consume(chunk, None, b - a)
+                stats["parse_s"] += time.perf_counter() - t0
+                stats["chunks"] += 1
+            offset = int(text.numel()) - header_bytes
+        finally:
+            f.close()
+        del text, stage
+        return _mtx_result(row, col, val, filled, seen, nnz, G, C, sel, offset, stats, t_start)
     thread = threading.Thread(target=reader, daemon=True)
     thread.start()
     try:
@@ -2113,25 +2365,7 @@ def read_mtx(path, chunk_bytes=None, cells=None):
                     dbuf = torch.empty(max(cap0, n), dtype=torch.uint8, device=dev)
                 t0 = time.perf_counter()
                 dbuf[:n].copy_(buf[:n], non_blocking=True)
-                host = buf.numpy()[:n]
-                try:
-                    if sel is None:
-                        filled += parse_triplets_into(dbuf, host, n, field, G, C, row, col, val, filled)
-                    else:
-                        kept, in_chunk = parse_selected(dbuf, host, n)
-                        filled, seen = filled + kept, seen + in_chunk
-                except _lib.IcnvError as exc:
-                    if exc.code != _lib.ERR_ARG or not ("capacity" in str(exc) or "line " in str(exc)):
-                        raise
-                    if "capacity" in str(exc):
-                        raise ValueError(f"read_mtx: the size line says {nnz} entries, the body has "
-                                         f"{_count_entries(path, header_bytes)}") from None
-                    line0 = 1 + _count_newlines(path, header_bytes + offset)      # the refusal again, with the file's line number
-                    if sel is None:
-                        parse_triplets_into(dbuf, host, n, field, G, C, row, col, val, filled, line0=line0)
-                    else:
-                        parse_selected(dbuf, host, n, line0=line0)
-                    raise
+                consume(dbuf, buf.numpy()[:n], n)
                 stats["parse_s"] += time.perf_counter() - t0
                 stats["chunks"] += 1
             offset += n
@@ -2148,33 +2382,7 @@ def read_mtx(path, chunk_bytes=None, cells=None):
         f.close()
     if failure:
         raise failure[0]
-    if sel is None:
-        seen = filled
-    if seen != nnz:
-        raise ValueError(f"read_mtx: the size line says {nnz} entries, the body has {seen}")
-    stats["bytes"], stats["entries"] = offset, seen
-    if sel is not None:
-        stats["entries_kept"] = filled
-        row, col, val = (t[:filled].clone() if t.numel() > filled else t for t in (row, col, val))
-        C = int(sel.size)
-    colptr, first, kind = csc_from_sorted_triplets(row, col, G, C)
-    if kind == _lib.CSC_DESCENT:
-        key, perm = torch.sort(col.to(torch.int64) * G + row)
-        del key
-        row, col, val = row[perm], col[perm], val[perm]
-        del perm
-        stats["sorted_on_device"] = 1
-        colptr, first, kind = csc_from_sorted_triplets(row, col, G, C)
-        if kind == _lib.CSC_DESCENT:
-            raise RuntimeError("read_mtx: the sorted triplets are not in order (internal error)")
-    if kind == _lib.CSC_DUPLICATE:
-        column = int(col[first]) if sel is None else int(sel[int(col[first])])         # the file's column
-        raise ValueError(f"duplicate entry for row {int(row[first]) + 1}, column {column + 1}")
-    del col
-    counts = DeviceCounts(G, C, colptr=colptr, rowidx=row, vals=val)
-    torch.cuda.synchronize()
-    stats["wall_s"] = time.perf_counter() - t_start
-    return counts, stats
+    return _mtx_result(row, col, val, filled, seen, nnz, G, C, sel, offset, stats, t_start)
 
 
 def csc_select(counts, genes, cells):
@@ -2506,6 +2714,99 @@ def crc32_pieces(src, piece_bytes):
     crc = torch.empty(-(-n // piece_bytes), dtype=torch.int32, device=src.device)
     check(L.icnv_crc32_pieces_dev(_ptr(src), n, piece_bytes, _ptr(crc), _stream()))
     return crc
+
+
+# ------------------------------------------------------------------ INFLATE with unknown history (DESIGN K30)
+def _int64_vectors(k, **named):
+    for name, t in named.items():
+        if not (_is_vector(t, torch.int64) and (k is None or t.numel() == k)):
+            raise TypeError(f"{name} must be a contiguous CUDA int64 vector" + ("" if k is None else f" of {k} elements"))
+
+
+def gunzip_find(src, *, cand=None):
+    """icnv_gunzip_find_dev (DESIGN K30): every bit offset of the CUDA uint8 vector src (a raw DEFLATE stream) at which a
+    non-final dynamic block's header parses, ascending, as a CUDA int64 vector.  cand: a caller's int64 vector to fill (too
+    small a one raises IcnvError, untouched); by default one is sized from the count.  Waits for the stream."""
+    L = _lib.load()
+    n = _bytes_vector(src, "src")
+    own = cand is None
+    if own:
+        cand = torch.empty(max(1024, n >> 10), dtype=torch.int64, device=src.device)
+    _int64_vectors(None, cand=cand)
+    count = ct.c_int64(0)
+    rc = L.icnv_gunzip_find_dev(_ptr(src), n, _ptr(cand), int(cand.numel()), ct.byref(count), _stream())
+    if own and rc == _lib.ERR_ARG and count.value > cand.numel():          # nothing was written: once more with room for all
+        cand = torch.empty(count.value, dtype=torch.int64, device=src.device)
+        rc = L.icnv_gunzip_find_dev(_ptr(src), n, _ptr(cand), int(cand.numel()), ct.byref(count), _stream())
+    check(rc)
+    return cand[:count.value]
+
+
+def gunzip_measure(src, cand, start, max_in):
+    """icnv_gunzip_measure_dev: the units that start at the BIT offsets `start` (CUDA int64) of src and stop on an offset of
+    the ascending list `cand` or behind BFINAL, parsed without producing symbols.  Returns (end, out_len, status): CUDA int64
+    (bits), int64, int32 (the GUNZIP_* codes of _lib)."""
+    L = _lib.load()
+    n = _bytes_vector(src, "src")
+    _int64_vectors(None, cand=cand, start=start)
+    k = int(start.numel())
+    end = torch.empty(k, dtype=torch.int64, device=src.device)
+    out_len = torch.empty(k, dtype=torch.int64, device=src.device)
+    status = torch.empty(k, dtype=torch.int32, device=src.device)
+    check(L.icnv_gunzip_measure_dev(_ptr(src), n, _ptr(cand), int(cand.numel()), _ptr(start), k, int(max_in), _ptr(end), _ptr(out_len),
+                                    _ptr(status), _stream()))
+    return end, out_len, status
+
+
+def _is_symbols(sym):
+    return _is_vector(sym, torch.int16)
+
+
+def gunzip_symbols(src, cand, start, end, out_off, out_len, sym):
+    """icnv_gunzip_symbols_dev: unit i, from bit start[i] to bit end[i] of src, decoded into the 16-bit symbols
+    sym[out_off[i]:out_off[i] + out_len[i]] (sym: a CUDA int16 vector holding the uint16 bit patterns: below 256 a byte,
+    0x8000 | w a marker; the int64 vectors of one length, out_off the prefix sums of out_len).  Returns the status vector."""
+    L = _lib.load()
+    n = _bytes_vector(src, "src")
+    k = int(start.numel())
+    _int64_vectors(None, cand=cand)
+    _int64_vectors(k, start=start, end=end, out_off=out_off, out_len=out_len)
+    if not _is_symbols(sym):
+        raise TypeError("sym must be a contiguous CUDA int16 vector")
+    status = torch.empty(k, dtype=torch.int32, device=src.device)
+    check(L.icnv_gunzip_symbols_dev(_ptr(src), n, _ptr(cand), int(cand.numel()), _ptr(start), _ptr(end), _ptr(out_off), _ptr(out_len), k,
+                                    _ptr(sym), int(sym.numel()), _ptr(status), _stream()))
+    return status
+
+
+def _gunzip_places(sym, out_off, out_len, out):
+    cap = _bytes_vector(out, "out")
+    k = int(out_off.numel())
+    _int64_vectors(k, out_off=out_off, out_len=out_len)
+    if not (_is_symbols(sym) and sym.numel() == cap):
+        raise TypeError(f"sym must be a contiguous CUDA int16 vector of out's {cap} elements")
+    return k, cap
+
+
+def gunzip_tails(sym, out_off, out_len, out):
+    """icnv_gunzip_tails_dev: the last min(32 768, out_len[i]) symbols of every unit resolved into out, unit after unit.
+    Returns (bad, markers): CUDA int32 [1] (1: a marker pointed in front of byte 0) and CUDA int64 [1] (markers met)."""
+    L = _lib.load()
+    k, cap = _gunzip_places(sym, out_off, out_len, out)
+    bad = torch.zeros(1, dtype=torch.int32, device=out.device)
+    markers = torch.zeros(1, dtype=torch.int64, device=out.device)
+    check(L.icnv_gunzip_tails_dev(_ptr(sym), _ptr(out_off), _ptr(out_len), k, _ptr(out), cap, _ptr(bad), _ptr(markers), _stream()))
+    return bad, markers
+
+
+def gunzip_resolve(sym, out_off, out_len, out):
+    """icnv_gunzip_resolve_dev: every symbol in front of the units' tails resolved into out (after gunzip_tails).  Returns bad:
+    CUDA int32 [1]."""
+    L = _lib.load()
+    k, cap = _gunzip_places(sym, out_off, out_len, out)
+    bad = torch.zeros(1, dtype=torch.int32, device=out.device)
+    check(L.icnv_gunzip_resolve_dev(_ptr(sym), _ptr(out_off), _ptr(out_len), k, _ptr(out), cap, _ptr(bad), _stream()))
+    return bad
 
 
 # ------------------------------------------------------------------ timing hooks

@@ -1020,14 +1020,19 @@ _INFLATE_STATUS = ("OK_MARKER", "OK_FINAL", "TRUNCATED", "TOO_LONG", "BAD_STREAM
 
 
 def _open_on_device(path):
-    """The _DeviceStream of a gzip file that inflate_gzip takes, or None: not gzip, no GPU, ICNV_INFLATE=0, or turned away."""
+    """The _DeviceStream of a gzip file that inflate_gzip or, where that gives up, gunzip.gunzip takes, or None: not gzip, no
+    GPU, ICNV_INFLATE=0, or turned away by both."""
     if not (_inflate_enabled() and _device_available()):
         return None
     with open(path, "rb") as fh:
         if fh.read(2) != b"\x1f\x8b":
             return None
     out = inflate_gzip(path)
-    return None if out is None else _inflate_backend().stream(out)
+    if out is not None:
+        return _inflate_backend().stream(out)
+    from . import gunzip                                      # K30: a stream without flush points (R's, GzipFile's)
+    opened = gunzip.open_on_device(path)
+    return None if opened is None else opened[1]
 
 
 def _open_bytes(path):
@@ -1055,8 +1060,10 @@ def read_rds(path, *, return_device=False):
     payloads of at least DEVICE_THRESHOLD bytes of an uncompressed or inflated file are decoded on the device
     (icnv_xdr_decode_dev); a matrix stays there and comes back as RDeviceMatrix of the (cols, rows) tensor, a plain vector is
     copied back.  A gzip file is then first offered to inflate_gzip (DESIGN K29): one written with flush points -- ours, with
-    compress=True -- is inflated on the device and parsed from there, the payloads decoded device to device; any other falls
-    back to the host's inflate at once (ICNV_INFLATE=0 in the environment: always).  Both routes return the same values."""
+    compress=True -- is inflated on the device and parsed from there, the payloads decoded device to device; any other -- R's
+    own, GzipFile's: no flush points -- is offered to gunzip.gunzip (DESIGN K30), which inflates any one-member gzip stream of
+    at least gunzip.GUNZIP_MIN_BYTES on the device, .rds and gzip .rda alike; what that turns away too falls back to the host's
+    inflate (ICNV_GUNZIP=0: K30 off; ICNV_INFLATE=0: both off, always the host).  All routes return the same values."""
     buf = _open_on_device(path) if return_device else None
     if buf is None:
         buf, _ = _open_bytes(path)
@@ -1337,6 +1344,8 @@ def load_infercnv_obj(path, *, return_device=False):
     dgCMatrix becomes a scipy.sparse.csc_matrix; indices become 0-based; the names of the subcluster vectors are dropped (they
     are the cells' names).  A slot R allows but the mirror cannot hold raises ValueError naming the slot.
     return_device=True: the matrix is decoded on the device (when it reaches DEVICE_THRESHOLD; uploaded otherwise -- a gzip
-    file with flush points, what compress=True writes, is inflated there as well: read_rds, inflate_gzip) and the pair (object with expr_data None, (cells, genes) CUDA float64 matrix) is
+    file is inflated there as well: one with flush points, what compress=True writes, by inflate_gzip; any other one-member
+    gzip file of at least gunzip.GUNZIP_MIN_BYTES -- R's own .rds and gzip .rda -- by gunzip.gunzip: read_rds) and the pair
+    (object with expr_data None, (cells, genes) CUDA float64 matrix) is
     returned, as sample_object(return_device=True) does."""
     return from_r(read_rds(path, return_device=return_device), return_device)
