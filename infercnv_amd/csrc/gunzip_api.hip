@@ -8,24 +8,16 @@ using namespace icnv;
 
 namespace {
 
-bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 // the units' starts / ends / places against n and cap: one small kernel, one word back
 int check_units(const GunzipArgs &a, int mode, const char *who, hipStream_t s) {
-    DevBuf d_bad;
-    int rc;
-    if ((rc = d_bad.alloc(sizeof(int32_t)))) return rc;
-    int32_t bad = 0;
-    ICNV_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int32_t), s));
-    if ((rc = launch_gunzip_check(a, mode, d_bad.as<int32_t>(), s))) return rc;
-    ICNV_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    if (bad)
-        ICNV_FAIL(ICNV_ERR_ARG, std::string(who) + (mode == GZ_CHECK_MEASURE   ? ": a unit's start is outside [0, 8 n)"
-                                                    : mode == GZ_CHECK_SYMBOLS ? ": a unit's start is outside [0, 8 n), its end outside [start, 8 n], or the units' places are not the "
-                                                                                 "prefix sums of out_len inside [0, sym_cap]"
-                                                                               : ": the units' places are not the prefix sums of out_len inside [0, out_cap]"));
-    return ICNV_OK;
+    return check_on_device([&](int32_t *bad, hipStream_t st) { return launch_gunzip_check(a, mode, bad, st); },
+                           [&] {
+                               return std::string(who) + (mode == GZ_CHECK_MEASURE   ? ": a unit's start is outside [0, 8 n)"
+                                                          : mode == GZ_CHECK_SYMBOLS ? ": a unit's start is outside [0, 8 n), its end outside [start, 8 n], or the units' places are not the "
+                                                                                       "prefix sums of out_len inside [0, sym_cap]"
+                                                                                     : ": the units' places are not the prefix sums of out_len inside [0, out_cap]");
+                           },
+                           s);
 }
 
 }  // namespace
@@ -40,7 +32,7 @@ int icnv_gunzip_find_dev(const uint8_t *src, int64_t n, int64_t *cand, int64_t c
     if (!src || (cand_cap > 0 && !cand)) ICNV_FAIL(ICNV_ERR_ARG, "gunzip_find: null argument");
     if (misaligned(cand, 8)) ICNV_FAIL(ICNV_ERR_ARG, "gunzip_find: cand is not aligned to 8 bytes");
     if (n > ((int64_t)1 << 32)) ICNV_FAIL(ICNV_ERR_ARG, "gunzip_find: the stream is beyond 2^32 bytes");   // 2^23 workgroups: the grid stays below 2^32 lanes
-    const int64_t n_blocks = (n * 8 - 1) / (GZ_FIND_NT * GZ_FIND_ROUNDS) + 1;     // bit offsets 0 .. 8 n - 1
+    const int64_t n_blocks = (n * 8 - 1) / (SC_NT * SC_ROUNDS) + 1;    // bit offsets 0 .. 8 n - 1
     hipStream_t s = (hipStream_t)stream;
     DevBuf offsets;
     int rc;

@@ -4,6 +4,7 @@
 // of exactly its size and every unit's symbols in one of exactly its out_len, so a load or store outside them stops the program.
 // Per stream:
 //   * gz_header_ok at EVERY bit offset, against if_dynamic_tables behind the three header bits (the rule it restates);
+//   * a valid stream that is one unit for K29 from byte 0: the same unit for K30 from bit 0 under an empty candidate list;
 //   * the measure from bit 0 and from every candidate, the chain walk, the symbols of the chain's units, tails and resolve by
 //     gz_resolve_one: a valid stream must give exactly its inflated bytes;
 //   * the symbols call with out_len and end wrong by one, short budgets, starts at the bits around every candidate;
@@ -49,13 +50,31 @@ void fail(const Record &r, const char *what, long a = 0, long b = 0) {
     fprintf(stderr, "FAIL %s: %s (%ld, %ld)\n", r.name.c_str(), what, a, b);
 }
 
-bool header_by_k29(const uint8_t *src, int64_t n, int64_t bit) {
+bool header_by_k29(const uint8_t *src, int64_t n, int64_t bit) {    // the rule gz_header_ok restates
     IfState s;
-    if_init(s, src, n, 0, n);
-    gz_reader_at(s.r, src, n, bit);
+    if_init<GzSymbols>(s, src, n, bit, n);
     if (!s.r.need(3) || s.r.take(3) != 4u) return false;
     IfTables t;
     return if_dynamic_tables(s, t) == 0;
+}
+
+// Both policies go through one walker: a stream that is ONE unit for K29 from byte 0 (no flush marker in front of BFINAL) is the
+// same unit for K30 from bit 0 with no candidate listed -- as many symbols as bytes, the end counted in bits, and every symbol
+// K29's byte (so none a marker).  Not counted among the measures and decodes of the summary line.
+void one_unit_under_both_policies(const Record &r, const uint8_t *src, int64_t n) {
+    IfTables t;
+    int64_t end29 = 0, len29 = 0, end30 = 0, len30 = 0, e = 0, l = 0;
+    if (if_unit_serial(IfBytes(), src, n, 0, n, t, nullptr, 0, &end29, &len29) != ICNV_INFLATE_OK_FINAL) return;
+    Heap<uint8_t> bytes((size_t)len29);
+    Heap<uint16_t> sym((size_t)len29);
+    if (if_unit_serial(IfBytes(), src, n, 0, end29, t, bytes.p, len29, &e, &l) != ICNV_INFLATE_OK_FINAL || e != end29 || l != len29)
+        return fail(r, "K29's decode of its own measure");
+    if (if_unit_serial(GzSymbols{nullptr, 0, 0}, src, n, 0, n, t, sym.p, len29, &end30, &len30) != ICNV_GUNZIP_OK_FINAL)
+        return fail(r, "one unit for K29 is not one for K30");
+    if (len30 != len29) return fail(r, "the two policies' out_len", (long)len29, (long)len30);
+    if (end30 != 8 * end29) fail(r, "K30's end is not 8 x K29's", (long)end29, (long)end30);
+    for (int64_t j = 0; j < len29; ++j)
+        if (sym.p[j] >= 256 || sym.p[j] != bytes.p[j]) return fail(r, "a symbol is not K29's byte", (long)j, sym.p[j]);
 }
 
 std::vector<int64_t> find(const Record &r, const uint8_t *src, int64_t n, bool compare) {
@@ -72,7 +91,7 @@ std::vector<int64_t> find(const Record &r, const uint8_t *src, int64_t n, bool c
 int measure(const uint8_t *src, int64_t n, int64_t start, int64_t max_in, const std::vector<int64_t> &cand, int64_t *end, int64_t *out_len) {
     IfTables t;
     ++g_measures;
-    return gz_unit_serial(src, n, start, max_in, cand.data(), (int64_t)cand.size(), t, nullptr, 0, end, out_len);
+    return if_unit_serial(GzSymbols{cand.data(), (int64_t)cand.size(), 0}, src, n, start, max_in, t, nullptr, 0, end, out_len);
 }
 
 // the symbols as the device calls them: budget up to the end's byte, symbols of exactly out_len
@@ -82,7 +101,7 @@ int symbols(const uint8_t *src, int64_t n, int64_t start, int64_t end, int64_t o
     Heap<uint16_t> sym((size_t)out_len);
     int64_t got_end = 0, got_len = 0;
     ++g_decodes;
-    int st = gz_unit_serial(src, n, start, ((end + 7) >> 3) - (start >> 3), cand.data(), (int64_t)cand.size(), t, sym.p, out_len, &got_end, &got_len);
+    int st = if_unit_serial(GzSymbols{cand.data(), (int64_t)cand.size(), 0}, src, n, start, ((end + 7) >> 3) - (start >> 3), t, sym.p, out_len, &got_end, &got_len);
     if (st <= ICNV_GUNZIP_OK_FINAL && (got_end != end || got_len != out_len)) st = ICNV_GUNZIP_BAD_STREAM;
     if (st == ICNV_GUNZIP_TOO_LONG) st = ICNV_GUNZIP_BAD_STREAM;
     if (got) got->assign(sym.p, sym.p + (st <= ICNV_GUNZIP_OK_FINAL ? out_len : 0));
@@ -135,6 +154,7 @@ void run(const Record &r, int flips) {
         }
         if (ok && out != r.raw) fail(r, "the inflated bytes", (long)out.size(), (long)r.raw.size());
         if (ok && end[chain.back()] != n * 8) fail(r, "the chain does not end with the stream", (long)end[chain.back()]);
+        one_unit_under_both_policies(r, src.p, n);
     }
     for (size_t i = 0; i < start.size(); ++i) {
         if (status[i] <= ICNV_GUNZIP_OK_FINAL && len[i] <= (16 << 20)) symbols(src.p, n, start[i], end[i], len[i], cand, nullptr);

@@ -1,15 +1,16 @@
 // K30 kernels: a gzip stream WITHOUT flush points inflated on the device.  DESIGN.md section 4 K30; the contract is in
-// include/icnv.h "INFLATE with unknown history"; the parser is gunzip_internal.h.
+// include/icnv.h "INFLATE with unknown history"; the parser and the bodies of find, measure and symbols are inflate_internal.h's,
+// shared with K29, under the policy GzSymbols of gunzip_internal.h.
 //
-//   find      a lane per bit offset runs gz_header_ok (cheap tests first).  Count, K29's one-workgroup prefix sum, emit: the
-//             flags are ranked by ballot and popcount (sc_rank), so the list is ascending and no atomic is involved.  Every
-//             offset reads its own bits through a bounds-tested reader: a header that straddles two workgroups' ranges is
-//             nothing special, and one cut by the end of the stream runs dry and is no candidate.
+//   find      a lane per bit offset runs gz_header_ok (cheap tests first).  Count, K29's one-workgroup prefix sum, emit
+//             (sc_count_tile, sc_emit_tile): the flags are ranked by ballot and popcount, so the list is ascending and no
+//             atomic is involved.  Every offset reads its own bits through a bounds-tested reader: a header that straddles
+//             two workgroups' ranges is nothing special, and one cut by the end of the stream runs dry and is no candidate.
 //   measure   lane 0 of a wavefront walks its unit's bits (code tables in LDS), stores nothing, and reports the bit offset
-//             where the unit ends, the symbols it produces, and its status.
-//   symbols   the same walk with stores of 16-bit symbols.  Lane 0 stores literals and short matches; a match of at least
-//             IF_WIDE_MIN symbols and every stored block is copied by the 64 lanes together.  A source position in front of
-//             the unit becomes a marker; an overlapping match is a periodic fill, over markers as over bytes.
+//             where the unit ends, the symbols it produces, and its status (if_measure_lane).
+//   symbols   the same walk with stores of 16-bit symbols (if_decode_wave).  Lane 0 stores literals and short matches; a match
+//             of at least IF_WIDE_MIN symbols and every stored block is copied by the 64 lanes together.  A source position in
+//             front of the unit becomes a marker; an overlapping match is a periodic fill, over markers as over bytes.
 //   tails     ONE workgroup goes through the units in order and resolves the last min(W, out_len) symbols of each into
 //             `out`; a marker reads out[off - W + w], which an earlier unit's tail has written (a barrier stands between
 //             two units).  The only sequential step: at most W symbols per unit.
@@ -21,35 +22,14 @@ namespace icnv {
 
 namespace {
 
-static_assert(GZ_FIND_NT == SC_NT, "sc_rank ranks a workgroup of SC_NT lanes");
-
 // ---- find -------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(GZ_FIND_NT) void gunzip_find_count_kernel(const uint8_t *src, int64_t n, int64_t n_blocks, int64_t *block_off) {
-    __shared__ int s_w[GZ_FIND_NT / 64];
-    const int64_t tile0 = (int64_t)blockIdx.x * (GZ_FIND_NT * GZ_FIND_ROUNDS);
-    int count = 0;
-    for (int r = 0; r < GZ_FIND_ROUNDS; ++r) {
-        int total;
-        sc_rank(gz_header_ok(src, n, tile0 + r * GZ_FIND_NT + threadIdx.x), s_w, total);
-        count += total;
-    }
-    if (threadIdx.x == 0 && blockIdx.x < n_blocks) block_off[blockIdx.x] = count;
+__global__ __launch_bounds__(SC_NT) void gunzip_find_count_kernel(const uint8_t *src, int64_t n, int64_t n_blocks, int64_t *block_off) {
+    sc_count_tile<gz_header_ok>(src, n, n_blocks, block_off);
 }
 
-__global__ __launch_bounds__(GZ_FIND_NT) void gunzip_find_emit_kernel(const uint8_t *src, int64_t n, int64_t n_blocks, const int64_t *block_off,
-                                                                      int64_t *cand, int64_t cand_cap) {
-    __shared__ int s_w[GZ_FIND_NT / 64];
-    if (blockIdx.x >= n_blocks) return;
-    const int64_t tile0 = (int64_t)blockIdx.x * (GZ_FIND_NT * GZ_FIND_ROUNDS);
-    int64_t at = block_off[blockIdx.x];
-    for (int r = 0; r < GZ_FIND_ROUNDS; ++r) {
-        const int64_t b = tile0 + r * GZ_FIND_NT + threadIdx.x;
-        const bool flag = gz_header_ok(src, n, b);
-        int total;
-        const int rank = sc_rank(flag, s_w, total);
-        if (flag && at + rank >= 0 && at + rank < cand_cap) cand[at + rank] = b;
-        at += total;
-    }
+__global__ __launch_bounds__(SC_NT) void gunzip_find_emit_kernel(const uint8_t *src, int64_t n, int64_t n_blocks, const int64_t *block_off,
+                                                                 int64_t *cand, int64_t cand_cap) {
+    sc_emit_tile<gz_header_ok>(src, n, n_blocks, block_off, cand, cand_cap);
 }
 
 // ---- argument check -------------------------------------------------------------------------------------------------------------------
@@ -73,68 +53,10 @@ __global__ __launch_bounds__(256) void gunzip_check_kernel(GunzipArgs a, int mod
 }
 
 // ---- measure ----------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(IF_NT) void gunzip_measure_kernel(GunzipArgs a) {
-    __shared__ IfTables s_tab[IF_WAVES];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t u = (int64_t)blockIdx.x * IF_WAVES + w;
-    if (u >= a.n_units || lane != 0) return;
-    const int64_t start = a.start[u];
-    int64_t end = start, out_len = 0;
-    int status = ICNV_GUNZIP_BAD_STREAM;
-    if (start >= 0 && (start >> 3) < a.n)                           // (the check kernel has refused anything else)
-        status = gz_unit_serial(a.src, a.n, start, a.max_in, a.cand, a.n_cand, s_tab[w], nullptr, 0, &end, &out_len);
-    a.end[u] = end;
-    a.out_len[u] = out_len;
-    a.status[u] = status;
-}
+__global__ __launch_bounds__(IF_NT) void gunzip_measure_kernel(GunzipArgs a) { if_measure_lane(a, GzSymbols{a.cand, a.n_cand, 0}); }
 
 // ---- symbols ----------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(IF_NT) void gunzip_symbols_kernel(GunzipArgs a) {
-    __shared__ IfTables s_tab[IF_WAVES];
-    __shared__ IfOp s_op[IF_WAVES];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t u = (int64_t)blockIdx.x * IF_WAVES + w;
-    if (u >= a.n_units) return;                                     // whole wavefronts leave: no workgroup barrier follows
-    const int64_t start = a.start[u], end = a.end[u], off = a.out_off[u], cap = a.out_len[u];
-    const bool sane = start >= 0 && (start >> 3) < a.n && end >= start && end <= a.n * 8 && off >= 0 && cap >= 0 && off <= a.cap && cap <= a.cap - off;
-    if (!sane) {                                                    // (the check kernel has refused it)
-        if (lane == 0) a.status[u] = ICNV_GUNZIP_BAD_STREAM;
-        return;
-    }
-    uint16_t *sym = a.sym + off;
-    GzState g;
-    gz_init(g, a.src, a.n, start, ((end + 7) >> 3) - (start >> 3));     // the budget is the caller's end
-    int status;
-    for (;;) {                                                      // every round but the last consumes bits of the unit
-        if (lane == 0) {
-            IfOp op;
-            gz_run(g, s_tab[w], a.cand, a.n_cand, sym, cap, IF_WIDE_MIN, op);
-            s_op[w] = op;
-        }
-        __threadfence_block();                                      // lane 0's op and its stores are visible to the wavefront
-        const IfOp op = s_op[w];
-        if (op.kind == IF_OP_DONE) { status = op.len; break; }
-        const int64_t o0 = __shfl(g.s.out_pos, 0, 64);              // lane 0's value
-        const int len = op.len;
-        if (len > 0 && len <= cap - o0) {                           // gz_run has tested this; the store's own test all the same
-            if (op.kind == IF_OP_MATCH) {
-                const int64_t dist = op.a;
-                if (dist >= 1 && dist <= o0 + GZ_W)
-                    for (int k = lane; k < len; k += 64) sym[o0 + k] = gz_back(sym, o0 - dist + (dist >= len ? k : k % dist));
-            } else if (op.a >= 0 && op.a + len <= a.n) {
-                for (int k = lane; k < len; k += 64) sym[o0 + k] = a.src[op.a + k];
-            }
-        }
-        __threadfence_block();                                      // the copy is visible before lane 0 reads behind it
-        g.s.out_pos = o0 + len;
-    }
-    if (lane == 0) {
-        const bool ok = status == ICNV_GUNZIP_OK_BOUNDARY || status == ICNV_GUNZIP_OK_FINAL;
-        if (ok && (g.s.end != end || g.s.out_pos != cap)) status = ICNV_GUNZIP_BAD_STREAM;
-        if (status == ICNV_GUNZIP_TOO_LONG) status = ICNV_GUNZIP_BAD_STREAM;       // the budget was the caller's end: it is too early
-        a.status[u] = status;
-    }
-}
+__global__ __launch_bounds__(IF_NT) void gunzip_symbols_kernel(GunzipArgs a) { if_decode_wave(a, GzSymbols{a.cand, a.n_cand, 0}, a.sym, a.cap); }
 
 // ---- tails ------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(GZ_TAILS_NT) void gunzip_tails_kernel(GunzipArgs a, int32_t *bad, int64_t *markers) {
@@ -187,14 +109,14 @@ __global__ __launch_bounds__(GZ_RESOLVE_NT) void gunzip_resolve_kernel(GunzipArg
 }  // namespace
 
 int launch_gunzip_find_count(const uint8_t *src, int64_t n, int64_t n_blocks, int64_t *block_off, hipStream_t s) {
-    hipLaunchKernelGGL(gunzip_find_count_kernel, dim3((unsigned)n_blocks), dim3(GZ_FIND_NT), 0, s, src, n, n_blocks, block_off);
+    hipLaunchKernelGGL(gunzip_find_count_kernel, dim3((unsigned)n_blocks), dim3(SC_NT), 0, s, src, n, n_blocks, block_off);
     ICNV_HIP(hipGetLastError());
     return launch_scan_offsets(n_blocks, block_off, s);
 }
 
 int launch_gunzip_find_emit(const uint8_t *src, int64_t n, int64_t n_blocks, const int64_t *block_off, int64_t *cand, int64_t cand_cap,
                             hipStream_t s) {
-    hipLaunchKernelGGL(gunzip_find_emit_kernel, dim3((unsigned)n_blocks), dim3(GZ_FIND_NT), 0, s, src, n, n_blocks, block_off, cand, cand_cap);
+    hipLaunchKernelGGL(gunzip_find_emit_kernel, dim3((unsigned)n_blocks), dim3(SC_NT), 0, s, src, n, n_blocks, block_off, cand, cand_cap);
     ICNV_HIP(hipGetLastError());
     return ICNV_OK;
 }

@@ -70,6 +70,23 @@ inline int upload(DevBuf &b, const T *host, size_t n, hipStream_t s) {
     if (n) ICNV_HIP(hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
     return ICNV_OK;
 }
+inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+// An entry point's check of arguments that lie on the device (K29, K30): one word is zeroed, launch(bad, s) starts a small
+// kernel that sets it for anything out of range, the word comes back, and a set word fails with ICNV_ERR_ARG and message(),
+// which is called only then.
+template <class Launch, class Message>
+inline int check_on_device(Launch launch, Message message, hipStream_t s) {
+    DevBuf d_bad;
+    int rc;
+    if ((rc = d_bad.alloc(sizeof(int32_t)))) return rc;
+    int32_t bad = 0;
+    ICNV_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int32_t), s));
+    if ((rc = launch(d_bad.as<int32_t>(), s))) return rc;
+    ICNV_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
+    ICNV_HIP(hipStreamSynchronize(s));
+    if (bad) ICNV_FAIL(ICNV_ERR_ARG, message());
+    return ICNV_OK;
+}
 inline int64_t env_int(const char *name, int64_t dflt) {   // an integer tuning knob of the environment (ICNV_*_SCRATCH_MB, ...)
     const char *e = std::getenv(name);
     return (e && *e) ? std::atoll(e) : dflt;

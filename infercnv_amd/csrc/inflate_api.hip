@@ -8,22 +8,14 @@ using namespace icnv;
 
 namespace {
 
-bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 // start (and, for the decode, end / out_off / out_len) of every unit against n and out_cap: one small kernel, one word back
 int check_units(const InflateArgs &a, bool units, const char *who, hipStream_t s) {
-    DevBuf d_bad;
-    int rc;
-    if ((rc = d_bad.alloc(sizeof(int32_t)))) return rc;
-    int32_t bad = 0;
-    ICNV_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int32_t), s));
-    if ((rc = launch_inflate_check(a, units, d_bad.as<int32_t>(), s))) return rc;
-    ICNV_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
-    ICNV_HIP(hipStreamSynchronize(s));
-    if (bad)
-        ICNV_FAIL(ICNV_ERR_ARG, std::string(who) + (units ? ": a unit's start is outside [0, n), its end outside [start, n], or its output range outside [0, out_cap]"
-                                                          : ": a unit's start is outside [0, n)"));
-    return ICNV_OK;
+    return check_on_device([&](int32_t *bad, hipStream_t st) { return launch_inflate_check(a, units, bad, st); },
+                           [&] {
+                               return std::string(who) + (units ? ": a unit's start is outside [0, n), its end outside [start, n], or its output range outside [0, out_cap]"
+                                                                : ": a unit's start is outside [0, n)");
+                           },
+                           s);
 }
 
 }  // namespace

@@ -43,7 +43,7 @@ long g_measures = 0, g_decodes = 0, g_failures = 0;
 int measure(const uint8_t *src, int64_t n, int64_t start, int64_t max_in, int64_t *end, int64_t *out_len) {
     IfTables t;
     ++g_measures;
-    return if_unit_serial(src, n, start, max_in, t, nullptr, INT64_MAX, end, out_len);
+    return if_unit_serial(IfBytes(), src, n, start, max_in, t, nullptr, INT64_MAX, end, out_len);
 }
 
 // the decode as the device calls it: budget end - start, output of exactly out_len bytes
@@ -53,7 +53,7 @@ int decode(const uint8_t *src, int64_t n, int64_t start, int64_t end, int64_t ou
     Heap out((size_t)out_len);
     int64_t got_end = 0, got_len = 0;
     ++g_decodes;
-    int st = if_unit_serial(src, n, start, end - start, t, out.p, out_len, &got_end, &got_len);
+    int st = if_unit_serial(IfBytes(), src, n, start, end - start, t, out.p, out_len, &got_end, &got_len);
     if ((st == ICNV_INFLATE_OK_MARKER || st == ICNV_INFLATE_OK_FINAL) && (got_end != end || got_len != out_len)) st = ICNV_INFLATE_BAD_STREAM;
     if (st == ICNV_INFLATE_TOO_LONG) st = ICNV_INFLATE_BAD_STREAM;
     if (bytes) bytes->assign(out.p, out.p + (st <= ICNV_INFLATE_OK_FINAL ? out_len : 0));

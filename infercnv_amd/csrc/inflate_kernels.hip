@@ -5,13 +5,11 @@
 //             SC_NT * SC_ROUNDS positions: count, a one-workgroup prefix sum of the counts, then emit -- per round the lanes'
 //             flags are ranked by ballot and popcount inside a wavefront and by the wavefronts' sums across the workgroup, so
 //             the list is ascending and no atomic is involved.  Every position reads its own four bytes: a marker that
-//             straddles a tile, a round or a wavefront is nothing special.
+//             straddles a tile, a round or a wavefront is nothing special.  The tile bodies are sc_count_tile / sc_emit_tile.
 //   measure   lane 0 of a wavefront walks its unit's bit stream with the parser of inflate_internal.h (the code tables, 1 KiB,
-//             in LDS), stores nothing, and reports where the unit ends, what it inflates to, and its status.
-//   units     the same walk with stores.  Lane 0 stores the literals and copies matches shorter than IF_WIDE_MIN itself; a
-//             longer match and every stored block is handed through LDS to all 64 lanes, which copy it together (a match
-//             whose distance is below its length is a periodic fill: byte k comes from offset k mod distance).  A
-//             workgroup-scope fence stands on either side of such a copy: the lanes of a wavefront share one L1.
+//             in LDS), stores nothing, and reports where the unit ends, what it inflates to, and its status: if_measure_lane.
+//   units     the same walk with stores, wide matches and stored blocks copied by all 64 lanes: if_decode_wave, with K29's
+//             policy IfBytes.  K30's kernels (gunzip_kernels.hip) are the same bodies with another policy.
 //   crc       one wavefront per piece; a lane folds CRC_SUB bytes at a time, moves its running CRC across the 63 other
 //             lanes' bytes with one fixed operator (crc32_combine's identity), and the 64 lanes' values are XOR-ed.
 #include "icnv_internal.h"
@@ -28,15 +26,7 @@ __device__ inline bool sc_is_candidate(const uint8_t *src, int64_t n, int64_t p)
 }
 
 __global__ __launch_bounds__(SC_NT) void inflate_scan_count_kernel(const uint8_t *src, int64_t n, int64_t n_blocks, int64_t *block_off) {
-    __shared__ int s_w[SC_NT / 64];
-    const int64_t tile0 = (int64_t)blockIdx.x * (SC_NT * SC_ROUNDS);
-    int count = 0;
-    for (int r = 0; r < SC_ROUNDS; ++r) {
-        int total;
-        sc_rank(sc_is_candidate(src, n, tile0 + r * SC_NT + threadIdx.x), s_w, total);
-        count += total;
-    }
-    if (threadIdx.x == 0 && blockIdx.x < n_blocks) block_off[blockIdx.x] = count;
+    sc_count_tile<sc_is_candidate>(src, n, n_blocks, block_off);
 }
 
 // one workgroup: block_off[i] becomes the sum of the counts before tile i, block_off[n_blocks] the total
@@ -71,18 +61,7 @@ __global__ __launch_bounds__(1024) void inflate_scan_offsets_kernel(int64_t n_bl
 
 __global__ __launch_bounds__(SC_NT) void inflate_scan_emit_kernel(const uint8_t *src, int64_t n, int64_t n_blocks, const int64_t *block_off,
                                                                   int64_t *cand, int64_t cand_cap) {
-    __shared__ int s_w[SC_NT / 64];
-    if (blockIdx.x >= n_blocks) return;
-    const int64_t tile0 = (int64_t)blockIdx.x * (SC_NT * SC_ROUNDS);
-    int64_t at = block_off[blockIdx.x];
-    for (int r = 0; r < SC_ROUNDS; ++r) {
-        const int64_t p = tile0 + r * SC_NT + threadIdx.x;
-        const bool flag = sc_is_candidate(src, n, p);
-        int total;
-        const int rank = sc_rank(flag, s_w, total);
-        if (flag && at + rank >= 0 && at + rank < cand_cap) cand[at + rank] = p;
-        at += total;
-    }
+    sc_emit_tile<sc_is_candidate>(src, n, n_blocks, block_off, cand, cand_cap);
 }
 
 // ---- argument check -------------------------------------------------------------------------------------------------------------------
@@ -99,69 +78,10 @@ __global__ __launch_bounds__(256) void inflate_check_kernel(InflateArgs a, int u
 }
 
 // ---- measure ----------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(IF_NT) void inflate_measure_kernel(InflateArgs a) {
-    __shared__ IfTables s_tab[IF_WAVES];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t u = (int64_t)blockIdx.x * IF_WAVES + w;
-    if (u >= a.n_units || lane != 0) return;
-    const int64_t start = a.start[u];
-    int64_t end = start, out_len = 0;
-    int status = ICNV_INFLATE_BAD_STREAM;
-    if (start >= 0 && start < a.n)                                  // (the check kernel has refused anything else)
-        status = if_unit_serial(a.src, a.n, start, a.max_in, s_tab[w], nullptr, INT64_MAX, &end, &out_len);
-    a.end[u] = end;
-    a.out_len[u] = out_len;
-    a.status[u] = status;
-}
+__global__ __launch_bounds__(IF_NT) void inflate_measure_kernel(InflateArgs a) { if_measure_lane(a, IfBytes()); }
 
 // ---- decode -----------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(IF_NT) void inflate_units_kernel(InflateArgs a) {
-    __shared__ IfTables s_tab[IF_WAVES];
-    __shared__ IfOp s_op[IF_WAVES];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t u = (int64_t)blockIdx.x * IF_WAVES + w;
-    if (u >= a.n_units) return;                                     // whole wavefronts leave: no workgroup barrier follows
-    const int64_t start = a.start[u], end = a.end[u], off = a.out_off[u], cap = a.out_len[u];
-    const bool sane = start >= 0 && start < a.n && end >= start && end <= a.n && off >= 0 && cap >= 0 && off <= a.out_cap && cap <= a.out_cap - off;
-    if (!sane) {                                                    // (the check kernel has refused it)
-        if (lane == 0) a.status[u] = ICNV_INFLATE_BAD_STREAM;
-        return;
-    }
-    uint8_t *out = a.out + off;
-    IfState s;
-    if_init(s, a.src, a.n, start, end - start);
-    int status;
-    for (;;) {                                                      // every round but the last consumes bits of the unit
-        if (lane == 0) {
-            IfOp op;
-            if_run(s, s_tab[w], out, cap, IF_WIDE_MIN, op);
-            s_op[w] = op;
-        }
-        __threadfence_block();                                      // lane 0's op and its stores are visible to the wavefront
-        const IfOp op = s_op[w];
-        if (op.kind == IF_OP_DONE) { status = op.len; break; }
-        const int64_t o = s.out_pos;                                // lane 0's value, broadcast below
-        const int64_t o0 = __shfl(o, 0, 64);
-        const int len = op.len;
-        if (len > 0 && len <= cap - o0) {                           // if_run has tested this; the store's own test all the same
-            if (op.kind == IF_OP_MATCH) {
-                const int64_t dist = op.a;
-                if (dist >= 1 && dist <= o0)
-                    for (int k = lane; k < len; k += 64) out[o0 + k] = out[o0 - dist + (dist >= len ? k : k % dist)];
-            } else if (op.a >= 0 && op.a + len <= a.n) {
-                for (int k = lane; k < len; k += 64) out[o0 + k] = a.src[op.a + k];
-            }
-        }
-        __threadfence_block();                                      // the copy is visible before lane 0 reads behind it
-        s.out_pos = o0 + len;
-    }
-    if (lane == 0) {
-        const bool ok = status == ICNV_INFLATE_OK_MARKER || status == ICNV_INFLATE_OK_FINAL;
-        if (ok && (s.end != end || s.out_pos != cap)) status = ICNV_INFLATE_BAD_STREAM;
-        if (status == ICNV_INFLATE_TOO_LONG) status = ICNV_INFLATE_BAD_STREAM;     // the budget was the caller's end: it is too early
-        a.status[u] = status;
-    }
-}
+__global__ __launch_bounds__(IF_NT) void inflate_units_kernel(InflateArgs a) { if_decode_wave(a, IfBytes(), a.out, a.out_cap); }
 
 // ---- CRC-32 of pieces -------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t CRC_POLY = 0xEDB88320u;

@@ -17,7 +17,6 @@ from __future__ import annotations
 
 import mmap
 import os
-import struct
 import time
 
 import numpy as np
@@ -35,11 +34,9 @@ _STATUS = ("OK_BOUNDARY", "OK_FINAL", "TRUNCATED", "TOO_LONG", "BAD_STREAM")
 _STATS = {"route": "none", "reason": "gunzip has not run"}
 
 
-class _DeviceGunzip:
-    """The device side of gunzip: host arrays are numpy; src, sym and out stay on the device."""
-
-    def __init__(self):
-        self._k29 = rds._DeviceInflate()                      # upload, crc32_pieces, stream: K29's, unchanged
+class _DeviceGunzip(rds._DeviceBytes):
+    """The device side of gunzip: host arrays are numpy; src, sym and out stay on the device.  upload, crc32_pieces and stream
+    are the shared base's, as K29's."""
 
     def available(self):
         import torch
@@ -48,9 +45,6 @@ class _DeviceGunzip:
     def free_bytes(self):
         import torch
         return int(torch.cuda.mem_get_info()[0])
-
-    def upload(self, view):
-        return self._k29.upload(view)
 
     def _up(self, src, a):
         import torch
@@ -82,12 +76,6 @@ class _DeviceGunzip:
     def resolve(self, sym, out_off, out_len, out):
         from . import device as dev
         return int(dev.gunzip_resolve(sym, self._up(sym, out_off), self._up(sym, out_len), out).item())
-
-    def crc32_pieces(self, out, piece_bytes):
-        return self._k29.crc32_pieces(out, piece_bytes)
-
-    def stream(self, out):
-        return self._k29.stream(out)
 
 
 def _backend():
@@ -181,20 +169,10 @@ def _gunzip(be, data, max_in, st):
         return give_up("fewer than 2 units: nothing to gain")
     end, out_len, status = be.measure(src, cand, start, max_in)
     t3 = clock()
-    nxt = np.searchsorted(start, end)
-    nxt_l, end_l, st_l, start_l = nxt.tolist(), end.tolist(), status.tolist(), start.tolist()
-    chain, i = [], 0
-    while True:                                               # every step moves forward: a unit ends behind its first block
-        chain.append(i)
-        if st_l[i] == 1:
-            break
-        if st_l[i] != 0:
-            return give_up(f"the unit at bit {start_l[i]} has status {_STATUS[st_l[i]]}")
-        j = nxt_l[i]
-        if j <= i or j >= len(start_l) or start_l[j] != end_l[i]:
-            return give_up(f"the unit at bit {start_l[i]} does not end on a candidate")
-        i = j
-    chain = np.asarray(chain, dtype=np.int64)
+    chain, refused = rds._walk_chain(start, end, status, lambda i, s: f"the unit at bit {int(start[i])} " + (
+        "does not end on a candidate" if s is None else f"has status {_STATUS[s]}"))
+    if chain is None:
+        return give_up(refused)
     st["seconds"].update(measure=t3 - t2, chain=clock() - t3)
     st["chain_units"], st["false_candidates"] = int(chain.size), int(start.size - chain.size)
     if int(end[chain[-1]]) != n * 8:
@@ -205,8 +183,7 @@ def _gunzip(be, data, max_in, st):
     c_off = np.cumsum(c_len) - c_len
     total = int(c_len.sum())
     st["units_short"] = int((c_len < W).sum())
-    crc, isize = struct.unpack("<II", bytes(view[len(view) - 8:]))
-    if isize != total & 0xFFFFFFFF:
+    if not rds._isize_matches(view, total):
         return give_up("the trailer's ISIZE does not match")
     st["inflated_bytes"] = total
     if n + 3 * total > be.free_bytes() // 2:
@@ -223,14 +200,9 @@ def _gunzip(be, data, max_in, st):
     st["seconds"].update(symbols=t5 - t4, tails=t6 - t5, resolve=t7 - t6)
     if bad:
         return give_up("a match refers in front of the stream's first byte")
-    from .device import crc32_combine_pieces
-    if total:
-        crcs = be.crc32_pieces(out, rds.INFLATE_CRC_PIECE)
-        got_crc = crc32_combine_pieces(crcs, rds.INFLATE_CRC_PIECE, total - (len(crcs) - 1) * rds.INFLATE_CRC_PIECE)
-    else:
-        got_crc = 0
+    crc_ok = rds._crc32_matches(view, be, out, total)
     st["seconds"].update(crc=clock() - t7)
-    if got_crc != crc:
+    if not crc_ok:
         return give_up("the trailer's CRC-32 does not match")
     return out
 

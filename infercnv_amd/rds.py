@@ -823,8 +823,9 @@ def _decode_device_stream(stream, pos, n, es):
     return out
 
 
-class _DeviceInflate:
-    """The device side of inflate_gzip: host arrays are numpy, `src` and `out` stay where upload / alloc put them."""
+class _DeviceBytes:
+    """What the device sides of inflate_gzip (K29) and gunzip.gunzip (K30) share: the file's bytes up, the CRC-32 of the
+    result, and the result as the stream read_rds parses."""
 
     def upload(self, view):
         """The bytes of a host buffer as a CUDA uint8 vector, through two pinned buffers."""
@@ -846,6 +847,18 @@ class _DeviceInflate:
         torch.cuda.synchronize()
         return src
 
+    def crc32_pieces(self, out, piece_bytes):
+        from . import device as dev
+        return dev.crc32_pieces(out, piece_bytes).cpu().numpy()
+
+    def stream(self, out):
+        fetch = lambda lo, hi: out[lo:hi].cpu().numpy().tobytes()
+        return _DeviceStream(fetch, int(out.numel()), out)
+
+
+class _DeviceInflate(_DeviceBytes):
+    """The device side of inflate_gzip: host arrays are numpy, `src` and `out` stay where upload / alloc put them."""
+
     def scan(self, src):
         from . import device as dev
         return dev.inflate_scan(src).cpu().numpy()
@@ -865,14 +878,6 @@ class _DeviceInflate:
         from . import device as dev
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(src.device)
         return dev.inflate_units(src, up(start), up(end), up(out_off), up(out_len), out).cpu().numpy()
-
-    def crc32_pieces(self, out, piece_bytes):
-        from . import device as dev
-        return dev.crc32_pieces(out, piece_bytes).cpu().numpy()
-
-    def stream(self, out):
-        fetch = lambda lo, hi: out[lo:hi].cpu().numpy().tobytes()
-        return _DeviceStream(fetch, int(out.numel()), out)
 
 
 def _inflate_backend():
@@ -910,6 +915,42 @@ def gzip_header_length(data):
     if flg & 2:                                               # FHCRC
         at += 2
     return at if at <= n else None
+
+
+def _walk_chain(start, end, status, refusal):
+    """The chain of true units among the measured ones (K29's and K30's): from unit 0, the unit that starts where the one
+    before it ends, up to the first with status 1 (OK_FINAL).  start is ascending; start and end count alike (bytes, or bits).
+    Returns (indices, None), or (None, refusal(i, s)) for the first unit i whose status s is no OK, or which ends (s None) on
+    no later unit's start: the wording is the caller's."""
+    nxt_l, end_l, st_l, start_l = np.searchsorted(start, end).tolist(), end.tolist(), status.tolist(), start.tolist()
+    chain, i = [], 0
+    while True:                                               # every step moves forward: j > i
+        chain.append(i)
+        if st_l[i] == 1:
+            return np.asarray(chain, dtype=np.int64), None
+        if st_l[i] != 0:
+            return None, refusal(i, st_l[i])
+        j = nxt_l[i]
+        if j <= i or j >= len(start_l) or start_l[j] != end_l[i]:
+            return None, refusal(i, None)
+        i = j
+
+
+def _isize_matches(view, total):
+    """Does ISIZE, the last 4 bytes of the gzip file `view`, equal `total` inflated bytes mod 2^32 (tested before anything is
+    decoded)?"""
+    return struct.unpack("<I", bytes(view[len(view) - 4:]))[0] == total & 0xFFFFFFFF
+
+
+def _crc32_matches(view, be, out, total):
+    """Does the CRC-32 of the `total` inflated bytes `out` on the device -- INFLATE_CRC_PIECE pieces there (be.crc32_pieces),
+    folded on the host; 0 for no bytes, without a launch -- equal the trailer's, bytes [-8, -4) of the gzip file `view`?"""
+    got = 0
+    if total:
+        from .device import crc32_combine_pieces
+        crcs = be.crc32_pieces(out, INFLATE_CRC_PIECE)
+        got = crc32_combine_pieces(crcs, INFLATE_CRC_PIECE, total - (len(crcs) - 1) * INFLATE_CRC_PIECE)
+    return got == struct.unpack("<I", bytes(view[len(view) - 8:len(view) - 4]))[0]
 
 
 def inflate_gzip(data, *, max_in=INFLATE_MAX_IN):
@@ -967,20 +1008,10 @@ def _inflate_gzip(data, max_in, st):
     if ok.all() and np.array_equal(end[:-1], start[1:]) and (status[:-1] == 0).all():
         chain = np.arange(start.size)                         # every candidate is a true unit
     else:
-        nxt = np.searchsorted(start, end)
-        hit = (nxt < start.size) & (start[np.minimum(nxt, start.size - 1)] == end)
-        nxt_l, hit_l, st_l = nxt.tolist(), hit.tolist(), status.tolist()
-        chain, i = [], 0
-        while True:                                           # every step moves forward: end > start
-            chain.append(i)
-            if st_l[i] == 1:
-                break
-            if st_l[i] != 0:
-                return give_up(f"the unit at byte {head + int(start[i])} has status {_INFLATE_STATUS[st_l[i]]}: no decode launched")
-            if not hit_l[i] or nxt_l[i] <= i:
-                return give_up(f"the unit at byte {head + int(start[i])} does not end on a candidate: no decode launched")
-            i = nxt_l[i]
-        chain = np.asarray(chain, dtype=np.int64)
+        chain, refused = _walk_chain(start, end, status, lambda i, s: f"the unit at byte {head + int(start[i])} " + (
+            "does not end on a candidate" if s is None else f"has status {_INFLATE_STATUS[s]}") + ": no decode launched")
+        if chain is None:
+            return give_up(refused)
     last = int(chain[-1])
     st["seconds"].update(measure=t3 - t2, chain=clock() - t3)
     st["chain_units"], st["false_candidates"] = int(chain.size), int(start.size - chain.size)
@@ -993,8 +1024,7 @@ def _inflate_gzip(data, max_in, st):
     c_start, c_end, c_len = start[chain], end[chain], out_len[chain]
     c_off = np.cumsum(c_len) - c_len
     total = int(c_len.sum())
-    crc, isize = struct.unpack("<II", bytes(view[len(view) - 8:]))
-    if isize != total & 0xFFFFFFFF:
+    if not _isize_matches(view, total):
         return give_up("the trailer's ISIZE does not match: no decode launched")
     st["inflated_bytes"] = total
     t4 = clock()
@@ -1005,13 +1035,9 @@ def _inflate_gzip(data, max_in, st):
     st["seconds"].update(decode=t5 - t4)
     if not np.array_equal(got, status[chain]):
         return give_up("the decode disagrees with the measure")
-    from .device import crc32_combine_pieces
-    crcs = be.crc32_pieces(out, INFLATE_CRC_PIECE)
-    last_bytes = total - (len(crcs) - 1) * INFLATE_CRC_PIECE
+    crc_ok = _crc32_matches(view, be, out, total)
     st["seconds"].update(crc=clock() - t5)
-    if total and crc32_combine_pieces(crcs, INFLATE_CRC_PIECE, last_bytes) != crc:
-        return give_up("the trailer's CRC-32 does not match")
-    if not total and crc != 0:
+    if not crc_ok:
         return give_up("the trailer's CRC-32 does not match")
     return out
 

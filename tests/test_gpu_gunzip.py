@@ -153,6 +153,78 @@ def test_tails_and_resolve_equal_the_restatement(dev, name):
         assert int((host_sym >= 256).sum()) - want_markers == 449060 and (lens > gr.W).all()
 
 
+# ---- K29's and K30's kernels are one walker and one wavefront copy loop under two policies ---------------------------------------------
+@functools.lru_cache(maxsize=None)
+def one_unit_streams():
+    """name -> (raw stream, K29's end, its bytes): the hand-built units and streams and zlib's streams that are ONE unit for K29
+    from byte 0 -- no flush marker in front of BFINAL -- by the restatement."""
+    named = {name: v[0] for name, v in ir.hand_units().items()}
+    named.update({name: v[0] for name, v in gr.zlib_streams().items()})
+    named.update({name: v[0] for name, v in gr.hand_streams().items()})
+    units = {name: (raw, ir.unit_cached(raw)) for name, raw in named.items()}
+    return {name: (raw, u[1], u[3]) for name, (raw, u) in sorted(units.items()) if u[0] == ir.OK_FINAL}
+
+
+def block_kinds(raw):
+    """What a valid stream holds, by a walk with the restatement's reader and codes: "stored" (a stored block with bytes),
+    "fixed", "dynamic", and "wide_periodic": a match of at least 8 bytes (IF_WIDE_MIN: the 64 lanes copy it together) whose
+    distance is below its length, so that byte k comes from offset k mod distance."""
+    r, kinds = ir._Reader(raw, 0, len(raw)), set()
+    while True:
+        last, kind = r.take(1), r.take(2)
+        if kind == 0:
+            q = r.byte_pos()
+            ln = struct.unpack_from("<H", raw, q)[0]
+            r.bb, r.bc, r.p = 0, 0, q + 4 + ln
+            kinds |= {"stored"} if ln else set()
+        else:
+            lit, dist = (ir.FIXED_LIT, ir.FIXED_DIST) if kind == 1 else ir._dynamic(r)
+            while True:
+                s = r.symbol(lit)
+                if s == 256:
+                    break
+                kinds.add("fixed" if kind == 1 else "dynamic")
+                if s > 256:
+                    ln = ir.LEN_BASE[s - 257] + r.take(ir.LEN_EXTRA[s - 257])
+                    d = r.symbol(dist)
+                    d = ir.DIST_BASE[d] + r.take(ir.DIST_EXTRA[d])
+                    kinds |= {"wide_periodic"} if ln >= 8 and d < ln else set()
+        if last:
+            return kinds
+
+
+def test_one_unit_is_the_same_for_k29_and_k30(dev):
+    """A stream that is one unit for K29 from byte 0 is the same unit for K30 from bit 0 under an EMPTY candidate list: the same
+    out_len, the end 8 x K29's, and symbols that are K29's bytes, none a marker -- measured and decoded by both sets of kernels
+    on the same bytes, all streams side by side in one buffer (a unit per wavefront, several workgroups)."""
+    streams = one_unit_streams()
+    kinds = set().union(*(block_kinds(raw) for raw, _, _ in streams.values()))
+    assert kinds == {"stored", "fixed", "dynamic", "wide_periodic"} and len(streams) > 8, (kinds, sorted(streams))
+    raws = [raw for raw, _, _ in streams.values()]
+    starts = np.cumsum([len(r) for r in raws]) - [len(r) for r in raws]
+    ends = starts + [end for _, end, _ in streams.values()]
+    want = b"".join(data for _, _, data in streams.values())
+    lens = np.array([len(data) for _, _, data in streams.values()], dtype=np.int64)
+    offs = np.cumsum(lens) - lens
+    total = int(lens.sum())
+    src = on_device(b"".join(raws))
+
+    end29, len29, st29 = (t.cpu().numpy() for t in dev.inflate_measure(src, i64(starts), 1 << 30))
+    end30, len30, st30 = measure(dev, src, [], starts * 8)
+    assert (st29 == ir.OK_FINAL).all() and (st30 == gr.OK_FINAL).all()
+    assert np.array_equal(end29, ends) and np.array_equal(end30, 8 * end29)
+    assert np.array_equal(len29, lens) and np.array_equal(len30, len29)
+
+    out = torch.full((total + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+    st29 = dev.inflate_units(src, i64(starts), i64(end29), i64(offs), i64(len29), out[:total])
+    st30, sym, _ = symbols(dev, src, [], starts * 8, end30, len30)
+    assert (st29.cpu().numpy() == ir.OK_FINAL).all() and (st30 == gr.OK_FINAL).all()
+    got = out.cpu().numpy()
+    assert (got[total:] == 0xA5).all(), "a store behind the last unit's range"
+    assert got[:total].tobytes() == want, "K29's bytes"
+    assert (sym < 256).all() and np.array_equal(sym, got[:total]), "K30's symbols are K29's bytes"
+
+
 @pytest.mark.parametrize("back", [1, 3, 8, 16, 17, 18])
 def test_find_a_header_that_straddles_two_workgroups(dev, back):
     """A true header that starts `back` bits before a workgroup's range ends: the 17 bits in front of its code lengths lie in
