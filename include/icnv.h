@@ -826,6 +826,63 @@ int icnv_state_fill_regions_dev(uint8_t *states, int64_t G, int64_t C, int64_t l
                                 const int32_t *gene_count, const int64_t *cell_off, const int32_t *cell_idx, int64_t n_idx,
                                 const uint8_t *value, void *stream);
 
+/* ---- MCMC convergence diagnostics of the Bayesian filter's chains (K31) ---------------------------------------------------
+ * What mcmcDiagnosticPlots (R/inferCNV_BayesNet.R:866-990, diagnostics = TRUE) asks of coda, as numbers: per region, state and
+ * chain the mean, variance, spectral density at zero, Geweke score and autocorrelations; per region and state the pooled
+ * moments and quantiles, Gelman-Rubin's potential scale reduction factor and the effective sample size.  The contract is THIS
+ * LIBRARY'S OWN, modelled on coda (spectrum0.ar, geweke.diag, autocorr, gelman.diag, effectiveSize as read from its sources):
+ * believed, not verified against coda -- no R run stands behind it.  DESIGN.md section 4 K31, restated in
+ * tests/mcmc_diag_restate.py.  Plots (trace, density, autocorrelation, Gelman) stay in R.  Not bound in the R shim.
+ * theta_samples: DEVICE doubles [n_regions, n_chains, n_keep, K] exactly as icnv_bayes_sample_dev lays them out (there
+ *   n_chains == K; here it is a parameter of its own).  Outputs, DEVICE doubles:
+ *   chain_stats [n_regions, K, n_chains, 9]: mean, var, spec0, order, geweke, acf1, acf5, acf10, acf50
+ *   pooled      [n_regions, K, 7]:           mean, sd, q2.5, q50, q97.5, psrf, ess
+ * Every operation below is one rounded IEEE-754 double operation, every sum runs sequentially in t from s = 0 (no FMA).
+ * One series x[0 .. n-1] (region, state k, chain ch; n = n_keep).  A WINDOW is a range t = lo .. lo + m - 1 of it:
+ *   mean  = (sum_t x[t]) / m
+ *   c[l]  = (sum_{t = lo .. lo + m - 1 - l} (x[t] - mean) * (x[t + l] - mean)) / m     for l = 0 .. P,
+ *           P = min(m - 1, floor(10 log10 m)), the floor in integers: the largest p with 10^p <= m^10
+ *   AR fit (spectrum0.ar: Yule-Walker by Levinson-Durbin, order by AIC).  c[0] == 0: spec0 = 0, order = 0, nothing is fitted.
+ *     c[0] NaN: both NaN.  Else v_0 = c[0], crit_0 = m * log_lib(v_0) + 0, and for p = 1 .. P:
+ *       acc = c[p]; for j = 1 .. p-1: acc = acc - phi_{p-1}[j] * c[p - j];   k = acc / v_{p-1}
+ *       phi_p[j] = phi_{p-1}[j] - k * phi_{p-1}[p - j]  (j = 1 .. p-1),  phi_p[p] = k;   v_p = v_{p-1} * (1 - k * k)
+ *       crit_p = m * log_lib(v_p) + 2 * p                      (log_lib: the library's table log, K13)
+ *     order = the p with the smallest crit_p, the first on ties (a NaN crit_p is never chosen);
+ *     var_pred = (v_p * m) / (m - (p + 1));  S = ((phi_p[1] + phi_p[2]) + ..) + phi_p[p] (0 for p = 0);  d = 1 - S;
+ *     spec0 = var_pred / (d * d)
+ *   Windows: the whole series (lo = 0, m = n); Geweke's A: t in [0, ceil((n - 1) / 10)]; B: t in [floor((n - 1) / 2), n - 1]
+ *   (integer arithmetic; each with its own mean, c, P and AR fit).
+ *   chain_stats: mean, spec0 and order of the whole series;  var = (the sum of c[0], before its division by n) / (n - 1);
+ *     geweke = (mean_A - mean_B) / sqrt(spec0_A / m_A + spec0_B / m_B);
+ *     acf1, acf5, acf10 = c[1], c[5], c[10] over c[0];  acf50 = ((sum as for c[50]) / n) / c[0], NaN when n <= 50.
+ * Pooled, over the N = n_chains n draws of a (region, state) in (chain, t) order:
+ *   mean = (sum x) / N;  sd = sqrt((sum (x - mean) * (x - mean)) / (N - 1))
+ *   q2.5, q50, q97.5: quantile(type = 7) at 0.025, 0.5, 0.975 in the operation order of icnv_quantiles_excluding (-0.0 counts
+ *     as +0.0); NaN when any draw is NaN.
+ *   psrf (gelman.diag's point estimate, transform = FALSE), from the chains' mean_i and var_i (m = n_chains), sums in chain order:
+ *     W = (sum var_i) / m;  W not > 0: psrf = NaN.  mu = (sum mean_i) / m;  B = n * ((sum (mean_i - mu)^2) / (m - 1))
+ *     var_w = ((sum (var_i - W)^2) / (m - 1)) / m;  var_b = (2 * (B * B)) / (m - 1);  q = (sum mean_i * mean_i) / m
+ *     cov_wb = (n / m) * ((sum (var_i - W) * (mean_i * mean_i - q)) / (m - 1) - (2 * mu) * ((sum (var_i - W) * (mean_i - mu)) / (m - 1)))
+ *     f = 1 + 1 / m;  V = ((n - 1) * W) / n + (f * B) / n
+ *     var_V = ((((n-1) * (n-1)) * var_w + (f * f) * var_b) + ((2 * (n-1)) * f) * cov_wb) / (n * n);  df = (2 * (V * V)) / var_V
+ *     psrf = sqrt(((df + 3) / (df + 1)) * ((n - 1) / n + (f * (1 / n)) * (B / W)))
+ *   ess = sum over the chains, in order, of (n * var_i) / spec0_i; a chain with spec0_i == 0 contributes 0.
+ * Degenerate input is ordinary input.  A region without cells has NaN samples: every output is NaN.  A constant series (the
+ *   sum of its draws divides back to the draw exactly, so c[0] == 0): mean = the value, var = 0, spec0 = 0, order = 0, geweke
+ *   and the acf NaN (0 / 0), ess contribution 0; all chains constant: W = 0 and psrf = NaN.  Chains with equal means and
+ *   variances give var_V = 0 and psrf = NaN, as the formula does in coda.
+ * Deviations from coda: psrf is computed over ALL kept iterations (gelman.diag's autoburnin halves the chain first; the burn-in
+ *   is already discarded here); the upper confidence limit of the psrf (an F quantile) is not built; the window ends are
+ *   integers, where coda matches times with a tolerance.
+ * Refusals before any launch: a null pointer, n_regions < 1, K or n_chains outside 2 .. 8, n_keep < 20 (the Geweke windows
+ *   need it): ICNV_ERR_ARG.  n_chains * n_keep > 8192 (the pooled draws are sorted in LDS; no memory fallback), or more than
+ *   2^31 - 1 (region, state) pairs: ICNV_ERR_UNSUPPORTED.  Synchronises.  Timer name: "mcmc_diag". */
+int icnv_mcmc_diag_dev(const double *theta_samples, int32_t n_regions, int32_t n_chains, int32_t n_keep, int32_t K, double *chain_stats,
+                       double *pooled, void *stream);
+/* The same with HOST samples and HOST outputs. */
+int icnv_mcmc_diag(const double *theta_samples, int32_t n_regions, int32_t n_chains, int32_t n_keep, int32_t K, double *chain_stats,
+                   double *pooled);
+
 /* ---- per-cell CNV features and run-length segmentation (K14) -------------------------------------------------------------
  * The numbers behind add_to_seurat's map_metadata_from_infercnv.txt (.get_features, R/seurat_interaction.R:244-353) and the
  * segmentation of state columns into CNV regions (.define_cnv_gene_regions, R/inferCNV_HMM.R:1005-1057, called per cell

@@ -167,6 +167,8 @@ PROTOTYPES = {
     "icnv_bayes_sample": (ct.c_int, [_vp, _i64p, _u64p, _i32, _i32, _i32, _i32, _i32, _u64, _vp, _vp, _vp]),
     "icnv_bayes_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
     "icnv_bayes_stats_reset": (None, []),
+    "icnv_mcmc_diag_dev": (ct.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "icnv_mcmc_diag": (ct.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "icnv_state_fill_regions_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "icnv_cnv_features_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _i32, _i32, _i32, _vp, _vp, _vp]),
     "icnv_cnv_features": (ct.c_int, [_vp, _i64, _i64, _ip, _i32, _i32, _i32, _vp, _vp]),

@@ -4,10 +4,11 @@ inferCNVBayesNet / filterHighPNormals (R/inferCNV_BayesNet.R) on the GPU sampler
 The reference fits one JAGS mixture model per region; here every region of a run goes through ONE likelihood pass and ONE
 sampler launch (device.bayes_loglik / device.bayes_sample, contract in include/icnv.h).  The posterior is the same, the random
 stream is this library's own (seeded, per draw), so probabilities agree with JAGS up to Monte-Carlo error, not bit for bit.
-Plotting (postProbNormal, plotProbabilities, mcmcDiagnosticPlots) stays out.  Index vectors are 0-based (R: 1-based);
-states keep R's numbering 1..K."""
+Plotting (postProbNormal, plotProbabilities, mcmcDiagnosticPlots) stays out; the numbers under mcmcDiagnosticPlots' plots
+and table are mcmc_diagnostics (DESIGN K31).  Index vectors are 0-based (R: 1-based); states keep R's numbering 1..K."""
 from __future__ import annotations
 
+import logging
 import operator
 import os
 from collections.abc import Sequence
@@ -21,6 +22,7 @@ from .infercnv_object import InfercnvObject
 from .tumor_subclusters import fnv1a64
 
 NA_INTEGER = np.iinfo(np.int32).min
+log = logging.getLogger("infercnv_amd")
 
 
 def _normal_state(HMM_type):
@@ -517,3 +519,105 @@ def filterHighPNormals(mcmc_obj: MCMCInferCNV, HMM_states, BayesMaxPNormal):
         if obj.args.get("reassignCNVs"):
             obj = _reassign_cnv(obj, st)
     return obj, st.result()
+
+
+# ---- convergence diagnostics of the chains (DESIGN K31) -----------------------------------------------------------------
+MCMC_TABLE_FILE = "CNV_MCMC_Diagnostics.dat"
+MCMC_TABLE_COLUMNS = ("Mean", "St.Dev", "2.5%", "50%", "97.5%", "Rhat", "ESS", "Geweke", "acf1", "acf5", "acf10", "acf50")
+MCMC_DEVICE_TABLE_ROWS = 1 << 16          # a table of at least this many rows is formatted on the device (K20)
+
+
+@dataclass
+class McmcDiagnostics:
+    """What mcmcDiagnosticPlots (R/inferCNV_BayesNet.R:866-990) takes from coda, as numbers (device.mcmc_diag; the library's
+    own contract, modelled on coda: believed, not verified against it).  regions: the region names; chain_stats: (regions, K,
+    n_chains, 9) host array, chain_fields per region, state and chain; pooled: (regions, K, 7), pooled_fields per region and
+    state.  States keep R's numbering: index k is state k + 1."""
+    regions: Sequence
+    chain_stats: np.ndarray
+    pooled: np.ndarray
+    chain_fields: tuple = device.MCMC_CHAIN_FIELDS
+    pooled_fields: tuple = device.MCMC_POOLED_FIELDS
+
+    def table(self):
+        """The (regions * K, 12) matrix of CNV_MCMC_Diagnostics.dat: MCMC_TABLE_COLUMNS per (region, state) -- R's
+        CNVSummaryTablels columns, then Rhat and ESS, then Geweke and the autocorrelations of chain 0."""
+        R, K = self.pooled.shape[:2]
+        return np.concatenate([self.pooled.reshape(R * K, -1), self.chain_stats[:, :, 0, 4:].reshape(R * K, -1)], axis=1)
+
+    def row_names(self):
+        K = self.pooled.shape[1]
+        return [f"{name}:State:{k + 1}" for name in self.regions for k in range(K)]
+
+
+def write_mcmc_diagnostics(diag: McmcDiagnostics, out_dir, device_rows=MCMC_DEVICE_TABLE_ROWS):
+    """CNV_MCMC_Diagnostics.dat in out_dir: write.table(sep = "\\t", quote = FALSE) of diag.table() with R's number formatting.
+    A small table goes through heatmap.write_table; from device_rows rows on the numbers are formatted on the device and
+    streamed (heatmap.write_matrix, DESIGN K20): the bytes are the same."""
+    import torch
+    from . import heatmap
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, MCMC_TABLE_FILE)
+    tab, names = diag.table(), diag.row_names()
+    if 0 < device_rows <= tab.shape[0]:
+        x = torch.from_numpy(np.ascontiguousarray(tab)).cuda()
+        heatmap.write_matrix(path, x, np.arange(tab.shape[0], dtype=np.int32), "cell_rows", row_names=names,
+                             col_names=MCMC_TABLE_COLUMNS, quote=False, sep="\t")
+    else:
+        heatmap.write_table(path, tab.tolist(), row_names=names, col_names=MCMC_TABLE_COLUMNS, quote=False, sep="\t")
+    return path
+
+
+def _resample(obj: MCMCInferCNV, lo, hi):
+    """The kept theta samples of the regions lo .. hi - 1, (hi - lo, K, n_keep, K) on the device: the likelihoods again from
+    obj.x_dev, the sampler again with the object's schedule, seed and tokens.  Every draw has its own counter and a region's
+    chains do not depend on the other regions of a call, so these are the samples of the run itself."""
+    a = obj.args
+    if obj.table is not None:
+        t = obj.table
+        c0, c1 = int(t.cell_off[lo]), int(t.cell_off[hi])
+        _, L, off = device.bayes_loglik_arrays(obj.x_dev, t.row_first[lo:hi], t.gene_count[lo:hi], t.cell_idx[c0:c1],
+                                               t.cell_off[lo:hi + 1] - c0, obj.mu, obj.sig)
+        tokens = t.token[lo:hi]
+    else:
+        cgs = [obj.cell_gene[r] for r in range(lo, hi)]
+        regions = [_gene_run(cg["Genes"], cg["cnv_regions"]) + (np.asarray(cg["Cells"], dtype=np.int32),) for cg in cgs]
+        _, L, off = device.bayes_loglik(obj.x_dev, regions, obj.mu, obj.sig)
+        tokens = [fnv1a64(cg["cnv_regions"]) for cg in cgs]
+    return device.bayes_sample(L, off, tokens, a["n_adapt"], a["n_burn"], a["n_keep"], a["seed"], want_samples=True)[1]
+
+
+def mcmc_diagnostics(mcmc_obj: MCMCInferCNV, *, max_sample_bytes=2 << 30, out_dir=None) -> McmcDiagnostics:
+    """Convergence diagnostics of every region's chains (DESIGN K31): R-hat, effective sample size, Geweke scores,
+    autocorrelations and the pooled quantiles, as a table one can filter -- the data under mcmcDiagnosticPlots' PDFs.
+    mcmc_obj: what inferCNVBayesNet returned (either route), or filterHighPNormals' object.  keep_samples is not needed: the
+    regions are sampled again in batches whose kept samples fit max_sample_bytes (K n_keep K doubles per region; at least one
+    region per batch), and device.mcmc_diag runs on each batch; the result does not depend on the batching.  An object that
+    holds its samples (keep_samples = True) is not sampled again.  out_dir: also write CNV_MCMC_Diagnostics.dat there."""
+    import torch
+    a = mcmc_obj.args
+    K, n_keep, R = len(mcmc_obj.mu), int(a["n_keep"]), len(mcmc_obj.cnv_regions)
+    cs = np.empty((R, K, K, len(device.MCMC_CHAIN_FIELDS)))
+    po = np.empty((R, K, len(device.MCMC_POOLED_FIELDS)))
+    batch = max(1, int(max_sample_bytes) // (K * n_keep * K * 8))
+    held = R > 0 and mcmc_obj.cnv_probabilities[0] is not None
+    for lo in range(0, R, batch):
+        hi = min(R, lo + batch)
+        if held:
+            host = np.stack([np.asarray(mcmc_obj.cnv_probabilities[r], dtype=np.float64).reshape(K, n_keep, K) for r in range(lo, hi)])
+            samples = torch.from_numpy(host).to(mcmc_obj.x_dev.device)
+        else:
+            samples = _resample(mcmc_obj, lo, hi)
+        c, p = device.mcmc_diag(samples)
+        cs[lo:hi], po[lo:hi] = c.cpu().numpy(), p.cpu().numpy()
+        del samples
+    diag = McmcDiagnostics(regions=list(mcmc_obj.cnv_regions) if R <= MCMC_DEVICE_TABLE_ROWS else mcmc_obj.cnv_regions,
+                           chain_stats=cs, pooled=po)
+    rhat, ess = po[:, :, 5], po[:, :, 6]
+    with np.errstate(invalid="ignore"):
+        n_bad = int((rhat >= 1.1).any(axis=1).sum()) if R else 0
+    min_ess = float(np.nanmin(ess)) if R and not np.isnan(ess).all() else float("nan")
+    log.info("MCMC diagnostics: %d regions, %d with a state of Rhat >= 1.1, smallest ESS %.6g", R, n_bad, min_ess)
+    if out_dir is not None:
+        write_mcmc_diagnostics(diag, out_dir)
+    return diag

@@ -1779,6 +1779,41 @@ def bayes_stats(reset=False):
     return dict(zip(BAYES_STATS, (int(v) for v in out)))
 
 
+MCMC_CHAIN_FIELDS = ("mean", "var", "spec0", "order", "geweke", "acf1", "acf5", "acf10", "acf50")
+MCMC_POOLED_FIELDS = ("mean", "sd", "q2.5", "q50", "q97.5", "psrf", "ess")
+
+
+def mcmc_diag(theta_samples):
+    """Convergence diagnostics of the sampler's chains (icnv_mcmc_diag_dev, DESIGN K31; the library's own contract, modelled on
+    coda).  theta_samples: contiguous (regions, n_chains, n_keep, K) CUDA float64 tensor as bayes_sample(want_samples=True)
+    returns it.  Returns (chain_stats (regions, K, n_chains, 9): MCMC_CHAIN_FIELDS per region, state and chain; pooled
+    (regions, K, 7): MCMC_POOLED_FIELDS per region and state) as CUDA float64 tensors.  Synchronises the device."""
+    L = _lib.load()
+    t = theta_samples
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 4 and t.is_contiguous()):
+        raise TypeError("theta_samples must be a contiguous (regions, n_chains, n_keep, K) CUDA float64 tensor")
+    R, m, n, K = (int(v) for v in t.shape)
+    chain_stats = torch.empty((R, K, m, len(MCMC_CHAIN_FIELDS)), dtype=torch.float64, device=t.device)
+    pooled = torch.empty((R, K, len(MCMC_POOLED_FIELDS)), dtype=torch.float64, device=t.device)
+    if R:
+        check(L.icnv_mcmc_diag_dev(_ptr(t), R, m, n, K, _ptr(chain_stats), _ptr(pooled), _stream()))
+    return chain_stats, pooled
+
+
+def mcmc_diag_host(theta_samples):
+    """mcmc_diag for a host array (icnv_mcmc_diag: the library uploads the samples and downloads both results)."""
+    L = _lib.load()
+    t = np.ascontiguousarray(theta_samples, dtype=np.float64)
+    if t.ndim != 4:
+        raise TypeError("theta_samples must have the shape (regions, n_chains, n_keep, K)")
+    R, m, n, K = t.shape
+    chain_stats = np.empty((R, K, m, len(MCMC_CHAIN_FIELDS)))
+    pooled = np.empty((R, K, len(MCMC_POOLED_FIELDS)))
+    if R:
+        check(L.icnv_mcmc_diag(ct.c_void_p(t.ctypes.data), R, m, n, K, ct.c_void_p(chain_stats.ctypes.data), ct.c_void_p(pooled.ctypes.data)))
+    return chain_stats, pooled
+
+
 def fill_regions(states, gene_first, gene_count, cell_off, cell_idx, value):
     """The rectangle rewrite of the Bayesian filter in one launch (icnv_state_fill_regions_dev, DESIGN K25), IN PLACE: states
     (C, G) uint8 CUDA tensor, rows `ld` apart; region r = the genes gene_first[r] .. + gene_count[r] - 1 of the cells

@@ -223,6 +223,44 @@ def rds_checkpoints(out_dir, which="all", *, saver=None, compress=False, **run_a
     return on_step
 
 
+def mcmc_diagnostics_hook(out_dir, *, max_sample_bytes=2 << 30, **run_args):
+    """An on_step(step, label, obj) callable for run() that does what `diagnostics = TRUE` stands for in infercnv::run, as
+    data (DESIGN K31): at step 18, where run() passes the MCMC object, bayes_net.mcmc_diagnostics writes
+    CNV_MCMC_Diagnostics.dat into R's `BayesNetOutput.<token>` directory under out_dir (file_tokens); every other step is
+    ignored.  run_args: the arguments run() is called with (the ones the directory depends on are read, the others ignored).
+    The record of the last call is kept as on_step.diagnostics.  run()'s own `diagnostics` argument stays accepted and ignored:
+    the plots are R's."""
+    a = {"HMM": False, "HMM_type": "i6", "analysis_mode": "subclusters", "tumor_subcluster_partition_method": "leiden",
+         "BayesMaxPNormal": 0.5}
+    a.update({k: v for k, v in run_args.items() if k in a})
+    for k, choices in (("HMM_type", HMM_TYPES), ("analysis_mode", ANALYSIS_MODES), ("tumor_subcluster_partition_method", PARTITION_METHODS)):
+        a[k] = _match_arg(k, a[k], choices)
+    target = os.path.join(out_dir, file_tokens(a["HMM"], a["HMM_type"], a["analysis_mode"], a["tumor_subcluster_partition_method"],
+                                               a["BayesMaxPNormal"])["bayes_dir"])
+
+    def on_step(step, label, obj):
+        if step != 18:
+            return
+        from . import bayes_net
+        on_step.diagnostics = bayes_net.mcmc_diagnostics(obj, max_sample_bytes=max_sample_bytes, out_dir=target)
+
+    on_step.diagnostics = None
+    on_step.out_dir = target
+    return on_step
+
+
+def chain_hooks(*hooks):
+    """One on_step(step, label, obj) that calls every hook given, in order (None entries are skipped): rds_checkpoints next to
+    mcmc_diagnostics_hook, for instance."""
+    hooks = [h for h in hooks if h is not None]
+
+    def on_step(step, label, obj):
+        for h in hooks:
+            h(step, label, obj)
+
+    return on_step
+
+
 def check_arguments(a):
     """R's own stops and adjustments (R/inferCNV_ops.R:351-392) and the refusals of what the library does not build, on the
     dict of evaluated arguments `a` (adjusted in place).  Needs no GPU and writes nothing."""
