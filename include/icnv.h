@@ -1640,6 +1640,28 @@ int icnv_median_filter_na_dev(const double *expr_in, double *expr_out, int64_t G
                               const int32_t *tile_off, int32_t n_tiles, int32_t window_size,
                               int64_t *n_na_out /* HOST, nullable */, void *stream);
 
+/* ---- reference z-score gene filter (K32) ---------------------------------------------------------------------------------------
+ * The statistics of the gene filter of define_signif_tumor_subclusters (R/inferCNV_tumor_subclusters.R:45-71) on a resident
+ * matrix: over the N = n_ref * G values v of the listed reference cells of a (C, G) DEVICE matrix whose rows lie ld >= G apart,
+ *   mean       sum(v) / N
+ *   sd         sqrt(sum((v - mean)^2) / (N - 1)), around the ROUNDED mean (R's two-pass sd); NaN when N < 2, as R's
+ *   row_mean   per gene g: sum over the listed cells of |(v - mean) / sd| / n_ref, each term two fp64 operations as R evaluates
+ *              (ref - mean) / sd, with the rounded mean and sd
+ * The three sums are accumulated in double-double (about 104 bits) and rounded to double once at the end, so every result is
+ * the correctly rounded value of its exact expression whenever that value lies further from a rounding boundary than the
+ * accumulation's error: N * 2^-104 of the sum of the |terms|.  That is every input the pipeline produces; it is not
+ * certified, and a mean that is the small remainder of large cancelling values can miss.  tests/zscore_restate.py states the
+ * exact expressions with fractions.  The squares are taken at a power-of-two scale, so values up to 2^1022 and down to the
+ * subnormals keep a finite, correctly scaled sd; a non-finite value among the listed cells makes all three results NaN.
+ * The `>= 0.8` decision is the caller's.  The host route (tumor_subclusters.zscore_outlier_genes) follows R's long-double
+ * sums, which round more than once: its mean, sd or a row mean may differ from these by an ulp.
+ * The order of every sum depends on (G, n_ref) and the order of the list alone: no atomics, the same bits on every run.  A cell
+ * listed twice counts twice.  ref_cells: HOST list, 0-based, any order.  mean_sd: HOST [2].  row_mean: DEVICE [G].
+ * ICNV_ERR_ARG before any launch, with the outputs untouched: a null pointer, dimensions outside 1 .. 2^31 - 1, ld < G,
+ * n_ref < 1, an entry that is not a cell.  Synchronises.  Timer names: "zscore_filter_pass", "zscore_filter_finish". */
+int icnv_zscore_gene_filter_dev(const double *x, int64_t ld, int64_t G, int64_t C, const int32_t *ref_cells, int64_t n_ref, double *mean_sd,
+                                double *row_mean, void *stream);
+
 /* ---- profiling hooks (used by bench.py) --------------------------------- */
 /* When enabled, every kernel launch is bracketed by hipEvents recorded on the
  * launch stream; icnv_timing_get() synchronises those events and returns the

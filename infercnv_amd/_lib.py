@@ -259,6 +259,7 @@ PROTOTYPES = {
     "icnv_median_filter_dev": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _i32, _ip, _ip, _i32, _i32, _vp]),
     "icnv_median_filter_na": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _i32, _ip, _ip, _i32, _i32, ct.POINTER(ct.c_int64)]),
     "icnv_median_filter_na_dev": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _i32, _ip, _ip, _i32, _i32, ct.POINTER(ct.c_int64), _vp]),
+    "icnv_zscore_gene_filter_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _i64, _dp, _vp, _vp]),
     "icnv_timing_enable": (None, [ct.c_int]),
     "icnv_timing_reset": (None, []),
     "icnv_timing_get": (ct.c_int, [ct.c_char_p, _dp, ct.POINTER(_i64)]),

@@ -18,7 +18,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import cnv_regions, device, hmm
-from .infercnv_object import InfercnvObject
+from .infercnv_object import DeviceMatrix, InfercnvObject
 from .tumor_subclusters import fnv1a64
 
 NA_INTEGER = np.iinfo(np.int32).min
@@ -146,15 +146,22 @@ class RegionTable:
         by_cell = by == "cell" and infercnv_obj.tumor_subclusters is not None
         perm, chr_start = infercnv_obj.chr_layout()
         chrs = np.asarray(infercnv_obj.gene_order.chr)
-        st = np.asarray(HMM_states)
-        st = np.asfortranarray(np.where(st < 0, 255, st).astype(np.uint8))
-        if perm is not None:                    # the kernels see contiguous chromosomes only
-            st, chrs = np.asfortranarray(st[perm]), chrs[perm]
-        if by_cell:
-            st = np.asfortranarray(np.where((st >= 1) & (st <= 6), st, 255).astype(np.uint8))
+        resident = isinstance(HMM_states, DeviceMatrix)     # (DESIGN K32: the states are on the device already)
+        if resident:
+            n_cells = HMM_states.shape[1]
+            if perm is not None:
+                chrs = chrs[perm]
+        else:
+            st = np.asarray(HMM_states)
+            st = np.asfortranarray(np.where(st < 0, 255, st).astype(np.uint8))
+            if perm is not None:                    # the kernels see contiguous chromosomes only
+                st, chrs = np.asfortranarray(st[perm]), chrs[perm]
+            if by_cell:
+                st = np.asfortranarray(np.where((st >= 1) & (st <= 6), st, 255).astype(np.uint8))
+            n_cells = st.shape[1]
         rec = np.zeros((6, 0), dtype=np.int64)
-        if st.shape[1] and groups:
-            dev_states = torch.from_numpy(st.T).cuda()
+        if n_cells and groups:
+            dev_states = cnv_regions._states_dev(HMM_states, perm, by_cell) if resident else torch.from_numpy(st.T).cuda()
             if by_cell:
                 mat, col_idx = dev_states, np.concatenate([g for _, g in groups]).astype(np.int32)
             else:
@@ -322,9 +329,8 @@ def inferCNVBayesNet(infercnv_obj: InfercnvObject, HMM_states, HMM_type="i6", by
         _attach_table(obj, RegionTable.from_states(infercnv_obj, HMM_states, by, normal))
         obj.group_id = obj.table.group_id(n_obs)
     else:
-        states = np.asarray(HMM_states)
         st_obj = infercnv_obj.copy()
-        st_obj.expr_data = states.astype(np.float64)
+        st_obj.expr_data = HMM_states if isinstance(HMM_states, DeviceMatrix) else np.asarray(HMM_states).astype(np.float64)
         groups = cnv_regions.get_predicted_CNV_regions(st_obj, by)
         cells_all = infercnv_obj.cells()
         col_of = {str(c): i for i, c in enumerate(cells_all)}
@@ -347,8 +353,12 @@ def inferCNVBayesNet(infercnv_obj: InfercnvObject, HMM_states, HMM_type="i6", by
     obj.mu, obj.sig = np.asarray(mu, dtype=np.float64), np.asarray(sig, dtype=np.float64)
     if obj.mu.size != (6 if HMM_type == "i6" else 3) or obj.sig.size != obj.mu.size:
         raise ValueError("mu and sig must have one entry per state")
-    obj.x_dev = x if x is not None else torch.from_numpy(
-        np.ascontiguousarray(np.asarray(infercnv_obj.expr_data, dtype=np.float64).T)).cuda()
+    if x is not None:
+        obj.x_dev = x
+    elif isinstance(infercnv_obj.expr_data, DeviceMatrix):
+        obj.x_dev = infercnv_obj.expr_data.tensor
+    else:
+        obj.x_dev = torch.from_numpy(np.ascontiguousarray(np.asarray(infercnv_obj.expr_data, dtype=np.float64).T)).cuda()
     return run_mcmc_table(obj) if route == "table" else run_mcmc(obj)
 
 
@@ -504,8 +514,13 @@ def _reassign_cnv(obj: MCMCInferCNV, st: _States):
 def filterHighPNormals(mcmc_obj: MCMCInferCNV, HMM_states, BayesMaxPNormal):
     """filterHighPNormals (R/inferCNV_BayesNet.R:1394-1440) -> (mcmc_obj, HMM_states).  HMM_states: genes x cells array, or a
     (cells, genes) CUDA tensor, which stays on the device and is rewritten there; a new array / tensor of the same kind comes
-    back.  The object passed in is not modified."""
+    back.  The object passed in is not modified.  A DeviceMatrix of states (DESIGN K32) is a uint8 CUDA tensor in a wrapper:
+    it is filtered as one and comes back wrapped."""
     import copy
+    if isinstance(HMM_states, DeviceMatrix):
+        t = HMM_states.tensor if HMM_states.kind == "states" else cnv_regions._states_dev(HMM_states)
+        obj, out = filterHighPNormals(mcmc_obj, t, BayesMaxPNormal)
+        return obj, DeviceMatrix(out.contiguous(), "states")
     if mcmc_obj.table is not None:
         return _filter_table(mcmc_obj, HMM_states, BayesMaxPNormal)
     obj = copy.copy(mcmc_obj)

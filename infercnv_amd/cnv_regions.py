@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, i32, pack_groups
-from .infercnv_object import InfercnvObject
+from .infercnv_object import DeviceMatrix, InfercnvObject
 
 log = logging.getLogger("infercnv_amd")
 REPORT_CHUNK = 256 << 20           # bytes of one chunk of the report bodies; ICNV_CNV_REPORT_CHUNK (developer switch) overrides it
@@ -35,6 +35,21 @@ LAST_REPORT_STATS = {}             # seconds and counts of the last generate_cnv
 def _states_u8(obj):
     st = np.asarray(obj.expr_data)
     return np.asfortranarray(np.where(st < 0, 255, st).astype(np.uint8))
+
+
+def _states_dev(states, perm=None, by_cell=False):
+    """The (C, G) uint8 CUDA tensor of a resident state matrix (DESIGN K32) as the kernels want it: 255 for what is no state,
+    the genes gathered by `perm` into per-chromosome blocks, and for by = "cell" every byte outside 1 .. 6 as the invalid
+    state.  Nothing crosses; the permutation and the masks are element-wise device operations on bytes."""
+    import torch
+    t = states.tensor
+    if states.kind != "states":
+        t = torch.where(t < 0, 255.0, t).to(torch.uint8)
+    if perm is not None:
+        t = t.index_select(1, torch.from_numpy(np.asarray(perm, dtype=np.int64)).to(t.device))
+    if by_cell:
+        t = torch.where((t >= 1) & (t <= 6), t, torch.full_like(t, 255))
+    return t.contiguous()
 
 
 def _consensus_u8(st, groups):
@@ -51,6 +66,12 @@ def _consensus_u8(st, groups):
 
 def state_consensus(infercnv_obj: InfercnvObject, groups):
     """(G, n_groups) consensus states (float, -1 where the consensus is the invalid state)."""
+    if isinstance(infercnv_obj.expr_data, DeviceMatrix):
+        from . import device
+        cons = device.state_consensus(_states_dev(infercnv_obj.expr_data), groups).cpu().numpy().T    # G x n_groups bytes
+        out = cons.astype(np.float64)
+        out[cons == 255] = -1.0
+        return out
     cons = _consensus_u8(_states_u8(infercnv_obj), groups)
     out = cons.astype(np.float64)
     out[cons == 255] = -1.0
@@ -60,6 +81,20 @@ def state_consensus(infercnv_obj: InfercnvObject, groups):
 def overwrite_with_consensus(infercnv_obj: InfercnvObject, groups) -> InfercnvObject:
     """expr.data[genes, group_cells] <- consensus state, the effect of R/inferCNV_HMM.R:473-483."""
     L = _lib.load()
+    if isinstance(infercnv_obj.expr_data, DeviceMatrix):
+        import torch
+        from . import device
+        t = _states_dev(infercnv_obj.expr_data)
+        _, out = device.state_consensus(t, groups, overwrite=True)
+        chrs = np.asarray(infercnv_obj.gene_order.chr)
+        for c in np.unique(chrs):                            # (see below: a chromosome of one gene keeps its states)
+            rows = np.nonzero(chrs == c)[0]
+            if rows.size < 2:
+                rt = torch.from_numpy(rows.astype(np.int64)).to(t.device)
+                out[:, rt] = t[:, rt]
+        new = infercnv_obj.copy()
+        new.expr_data = DeviceMatrix(out, "states")
+        return new
     st = _states_u8(infercnv_obj)
     G, C = st.shape
     idx, off = pack_groups(groups)
@@ -130,6 +165,25 @@ def predicted_cnv_runs(infercnv_obj: InfercnvObject, by="consensus", neutral=0, 
     n = chrs.size
     start = np.asarray(infercnv_obj.gene_order.start) if infercnv_obj.gene_order.start is not None else np.arange(n)
     stop = np.asarray(infercnv_obj.gene_order.stop) if infercnv_obj.gene_order.stop is not None else np.arange(n)
+    if isinstance(infercnv_obj.expr_data, DeviceMatrix):   # resident states: the same two kernels through their _dev entries
+        from . import device
+        t = _states_dev(infercnv_obj.expr_data, perm, by_cell)
+        if perm is not None:
+            chrs, start, stop = chrs[perm], start[perm], stop[perm]
+        chr_names = chrs[chr_start[:-1]]
+        rec, n_runs_dev = np.zeros((6, 0), dtype=np.int32), 0
+        if t.shape[0] and groups:
+            if by_cell:
+                r, n_runs_dev = device.cnv_runs(t, chr_start, neutral=neutral, K=K, col_idx=np.concatenate([g for _, g in groups]))
+            else:
+                r, n_runs_dev = device.cnv_runs(device.state_consensus(t, [g for _, g in groups]), chr_start, neutral=neutral, K=K)
+            rec = r.cpu().numpy()
+        col, chr_i, first, last, state, ordinal = (rec[k].astype(np.int64) for k in range(6))
+        state = np.where(state == 255, -1, state)
+        names = [f"{chr_names[c]}-region_{o}" for c, o in zip(chr_i, ordinal)]
+        return {"groups": groups, "chr_names": chr_names, "chr_start": chr_start, "perm": perm, "n_runs": n_runs_dev,
+                "col": col, "chr": chr_i, "gene_first": first, "gene_last": last, "state": state, "ordinal": ordinal, "name": names,
+                "start": _range_reduce(np.minimum, start, first, last), "end": _range_reduce(np.maximum, stop, first, last)}
     st = _states_u8(infercnv_obj)
     if perm is not None:                                   # the kernels see contiguous chromosomes only
         st, chrs, start, stop = np.asfortranarray(st[perm]), chrs[perm], start[perm], stop[perm]
@@ -380,19 +434,23 @@ def generate_cnv_region_reports(infercnv_obj: InfercnvObject, output_filename_pr
     by_cell = by == "cell" and infercnv_obj.tumor_subclusters is not None
     perm, chr_start = infercnv_obj.chr_layout()
     chrs, genes, cells = np.asarray(go.chr), infercnv_obj.genes(), infercnv_obj.cells()
-    st = _states_u8(infercnv_obj)
+    resident = isinstance(infercnv_obj.expr_data, DeviceMatrix)
+    st = None if resident else _states_u8(infercnv_obj)
     g_chrs, g_genes, g_start, g_stop = chrs, genes, start64, stop64
     if perm is not None:                                   # the kernels see contiguous chromosomes only
-        st, g_chrs, g_genes, g_start, g_stop = np.asfortranarray(st[perm]), chrs[perm], np.asarray(genes)[perm], start64[perm], stop64[perm]
+        g_chrs, g_genes, g_start, g_stop = chrs[perm], np.asarray(genes)[perm], start64[perm], stop64[perm]
+        if not resident:
+            st = np.asfortranarray(st[perm])
     chr_names = g_chrs[chr_start[:-1]]
-    if by_cell:
+    if by_cell and not resident:
         # what the consensus over one cell gave before: a byte outside 1 .. 6 is the invalid state (reported as -1)
         st = np.asfortranarray(np.where((st >= 1) & (st <= 6), st, 255).astype(np.uint8))
     stats = {"device_writer": True, "by": by}
-    G, C = st.shape
+    G, C = infercnv_obj.expr_data.shape if resident else st.shape
     rec = rec_all = torch.zeros((6, 0), dtype=torch.int32, device="cuda")
     if C and groups:
-        dev_states = torch.from_numpy(st.T).cuda()         # (C, G) rows = the columns of the (G, C) column-major matrix
+        # (C, G) rows = the columns of the (G, C) column-major matrix; a resident state matrix (DESIGN K32) is there already
+        dev_states = _states_dev(infercnv_obj.expr_data, perm, by_cell) if resident else torch.from_numpy(st.T).cuda()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         if by_cell:

@@ -557,6 +557,27 @@ def matrix_mean(x):
     return matrix_sum(x) / (x.shape[0] * x.shape[1])
 
 
+# ------------------------------------------------------------------ reference z-score gene filter (DESIGN K32)
+def zscore_gene_filter(x, ref_cells, row_mean=None):
+    """(mean, sd, row_mean) of the reference-based gene filter of the subclustering (icnv_zscore_gene_filter_dev, DESIGN K32):
+    mean and two-pass sd (n - 1) over all values of the listed cells of a (C, G) CUDA float64 matrix with contiguous rows, and
+    per gene the mean over those cells of |(x - mean) / sd|, as a (G,) CUDA tensor.  Double-double sums rounded once, in a
+    fixed order.  ref_cells: 0-based, any order, at least one.  Synchronises the stream."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(x)
+    idx, ip = i32(ref_cells)
+    if idx.ndim != 1:
+        raise ValueError("ref_cells must be an index vector")
+    if row_mean is None:
+        row_mean = torch.empty(G, dtype=torch.float64, device=x.device)
+    if not (isinstance(row_mean, torch.Tensor) and row_mean.is_cuda and row_mean.dtype == torch.float64 and row_mean.is_contiguous()
+            and tuple(row_mean.shape) == (G,)):
+        raise TypeError("row_mean must be a contiguous CUDA float64 tensor of G values")
+    out = (ct.c_double * 2)(float("nan"), float("nan"))
+    check(L.icnv_zscore_gene_filter_dev(_ptr(x), int(ld), G, C, ip, idx.size, out, _ptr(row_mean), _stream()))
+    return out[0], out[1], row_mean
+
+
 def _unquote(b):
     return b[1:-1] if len(b) >= 2 and b[:1] == b"\"" and b[-1:] == b"\"" else b
 

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import device
-from .infercnv_object import InfercnvObject
+from .infercnv_object import DeviceMatrix, InfercnvObject
 from .text_stream import stream_chunks
 from .tumor_subclusters import HClust
 
@@ -478,10 +478,12 @@ def _plot_cnv(infercnv_obj, x_dev, out_dir, title, obs_title, ref_title, cluster
         raise NotImplementedError("output_format 'pdf': only the PNG panels are produced")
     obj = infercnv_obj
     os.makedirs(out_dir, exist_ok=True)
-    if x_dev is None:
-        x = torch.from_numpy(np.ascontiguousarray(np.asarray(obj.expr_data, dtype=np.float64).T)).cuda()
-    else:
+    if x_dev is not None:
         x = x_dev
+    elif isinstance(obj.expr_data, DeviceMatrix):            # a resident object (DESIGN K32): drawn from where it lives
+        x = obj.expr_data.float_tensor()
+    else:
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(obj.expr_data, dtype=np.float64).T)).cuda()
     C, G = x.shape
     genes, cells = [str(g) for g in obj.genes()], [str(c) for c in obj.cells()]
     if x_center is None:

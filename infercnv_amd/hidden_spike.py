@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib, device, ops
 from .hmm import HSPIKE_CHR_INFO
-from .infercnv_object import GeneOrder, InfercnvObject
+from .infercnv_object import DeviceMatrix, GeneOrder, InfercnvObject
 from .smooth_spline import smooth_spline
 from .tumor_subclusters import fnv1a64
 
@@ -47,8 +47,10 @@ def _table_groups(infercnv_obj):
 
 
 def _device_matrix(expr):
-    """genes x cells host matrix -> the (C, G) CUDA tensor of the same bytes."""
+    """genes x cells host matrix -> the (C, G) CUDA tensor of the same bytes; a DeviceMatrix is there already."""
     import torch
+    if isinstance(expr, DeviceMatrix):
+        return expr.tensor
     return torch.from_numpy(np.ascontiguousarray(np.asarray(expr, dtype=np.float64).T)).cuda()
 
 
@@ -151,7 +153,11 @@ def build_and_add_hspike(infercnv_obj: InfercnvObject, sim_method="meanvar", agg
             dest[name] = np.arange(counter, counter + NUM_CELLS, dtype=np.int32)
             counter += NUM_CELLS
     sim = device.hspike_simulate(np.vstack(means), NUM_CELLS, var_spline, p0_spline, seed, tokens, device=x.device)
-    counts = np.asfortranarray(sim.reshape(-1, num_genes).cpu().numpy().T)        # genes x (2 n_types 100) cells
+    if isinstance(infercnv_obj.expr_data, DeviceMatrix):
+        # a resident object gets a resident spike-in: the simulated counts stay where the launch wrote them (DESIGN K32)
+        counts = DeviceMatrix(sim.reshape(-1, num_genes).contiguous())
+    else:
+        counts = np.asfortranarray(sim.reshape(-1, num_genes).cpu().numpy().T)    # genes x (2 n_types 100) cells
 
     hspike = InfercnvObject(expr_data=counts, count_data=counts, gene_order=GeneOrder(chrs, pos.copy(), pos.copy()),
                             reference_grouped_cell_indices=ref_idx, observation_grouped_cell_indices=obs_idx,

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64, i32, pack_groups
-from .infercnv_object import InfercnvObject
+from .infercnv_object import DeviceMatrix, InfercnvObject
 
 CNV_LEVELS = ("cnv:0.01", "cnv:0.5", "cnv:1", "cnv:1.5", "cnv:2", "cnv:3")
 
@@ -62,8 +62,9 @@ def get_spike_dists(hspike_obj: InfercnvObject, chr_info=HSPIKE_CHR_INFO):
     if hspike_obj is None:
         raise ValueError("get_spike_dists(hspike_obj): Error, hspike obj is null")
     L = _lib.load()
-    x = np.asfortranarray(hspike_obj.expr_data, dtype=np.float64)
-    G, C = x.shape
+    resident = _resident(hspike_obj)
+    x = hspike_obj.expr_data.tensor if resident else np.asfortranarray(hspike_obj.expr_data, dtype=np.float64)
+    G, C = hspike_obj.expr_data.shape
     cells = np.concatenate([np.asarray(v, dtype=np.int32) for v in hspike_obj.observation_grouped_cell_indices.values()])
     chrs = np.asarray(hspike_obj.gene_order.chr)
     genes_by_cnv = {}
@@ -77,7 +78,10 @@ def get_spike_dists(hspike_obj: InfercnvObject, chr_info=HSPIKE_CHR_INFO):
             continue
         ci, cp = i32(cells)
         buf = (ct.c_double * 2)()
-        check(L.icnv_block_mean_sd(x.ctypes.data_as(ct.c_void_p), G, C, gp, gi.size, cp, ci.size, buf))
+        if resident:
+            check(L.icnv_block_mean_sd_dev(ct.c_void_p(x.data_ptr()), G, C, gp, gi.size, cp, ci.size, buf, _stream()))
+        else:
+            check(L.icnv_block_mean_sd(x.ctypes.data_as(ct.c_void_p), G, C, gp, gi.size, cp, ci.size, buf))
         out[key] = {"mean": buf[0], "sd": buf[1]}
     return out
 
@@ -124,9 +128,14 @@ def get_hspike_cnv_mean_sd_trend_by_num_cells_fit(hspike_obj: InfercnvObject, se
     allo = np.ascontiguousarray(np.concatenate(list(draws.values())), dtype=np.int64)
     vals = np.empty(allo.size, dtype=np.float64)
     L = _lib.load()
-    x = np.asfortranarray(hspike_obj.expr_data, dtype=np.float64)
-    check(L.icnv_gather_values(x.ctypes.data_as(ct.c_void_p), x.shape[0], x.shape[1], allo.ctypes.data_as(ct.POINTER(ct.c_int64)),
-                               allo.size, vals.ctypes.data_as(ct.POINTER(ct.c_double))))
+    if _resident(hspike_obj):
+        t = hspike_obj.expr_data.tensor
+        check(L.icnv_gather_values_dev(ct.c_void_p(t.data_ptr()), t.numel(), allo.ctypes.data_as(ct.POINTER(ct.c_int64)), allo.size,
+                                       vals.ctypes.data_as(ct.POINTER(ct.c_double)), _stream()))
+    else:
+        x = np.asfortranarray(hspike_obj.expr_data, dtype=np.float64)
+        check(L.icnv_gather_values(x.ctypes.data_as(ct.c_void_p), x.shape[0], x.shape[1], allo.ctypes.data_as(ct.POINTER(ct.c_int64)),
+                                   allo.size, vals.ctypes.data_as(ct.POINTER(ct.c_double))))
     LD = np.longdouble
     fits, sds_all, pos = {}, {}, 0
     for level in offs:
@@ -162,7 +171,29 @@ def _median(v):
     return float(v[n // 2]) if n % 2 else float((v[n // 2 - 1] + v[n // 2]) * 0.5)
 
 
+def _resident(obj) -> bool:
+    return isinstance(obj.expr_data, DeviceMatrix)
+
+
+def _stream():
+    import torch
+    return ct.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _check_underflow(bad):
+    """The host-buffer entries' refusal of a sequence that underflowed, for the resident route (one int32 comes back)."""
+    n = int(bad.item())
+    if n:
+        raise _lib.IcnvError(_lib.ERR_UNDERFLOW, f"Problems With Underflow in {n} sequences")
+
+
 def _layout(obj):
+    """(perm, chr_start, matrix with the genes in per-chromosome blocks): F-ordered (G, C) NumPy for a host object, the (C, G)
+    tensor for a resident one (a non-identity perm is one device.gather_matrix)."""
+    if _resident(obj):
+        from .ops import _dev_layout
+        x, perm, chr_start = _dev_layout(obj)
+        return perm, chr_start, x
     perm, chr_start = obj.chr_layout()
     x = np.asfortranarray(obj.expr_data if perm is None else obj.expr_data[perm], dtype=np.float64)
     return perm, chr_start, x
@@ -184,6 +215,11 @@ def Viterbi_dthmm_adj(x, Pi, delta, mean, sd):
 
 
 def _viterbi_cells(x, chr_start, mean, sd_shared, Pi, delta):
+    if not isinstance(x, np.ndarray):                       # a resident matrix: (C, G) tensor in, (C, G) uint8 tensor out
+        from . import device
+        st, bad = device.viterbi_cells(x, chr_start, mean, sd_shared, _log(Pi), _log(delta))
+        _check_underflow(bad)
+        return st
     L = _lib.load()
     G, C = x.shape
     cs, cp = i32(chr_start)
@@ -197,6 +233,11 @@ def _viterbi_cells(x, chr_start, mean, sd_shared, Pi, delta):
 
 
 def _viterbi_groups(x, chr_start, groups, mean, sd_per_group, Pi, delta):
+    if not isinstance(x, np.ndarray):
+        from . import device
+        st, bad = device.viterbi_groups(x, chr_start, groups, mean, sd_per_group, _log(Pi), _log(delta))
+        _check_underflow(bad)
+        return st
     L = _lib.load()
     G, C = x.shape
     cs, cp = i32(chr_start)
@@ -215,7 +256,16 @@ def _viterbi_groups(x, chr_start, groups, mean, sd_per_group, Pi, delta):
 
 def _states_obj(obj, st, perm):
     """The reference stores states as numeric with -1 for untouched entries
-    (R/inferCNV_HMM.R:294-295)."""
+    (R/inferCNV_HMM.R:294-295).  A resident object gets the uint8 states as they are (255 = untouched), kind "states"."""
+    if not isinstance(st, np.ndarray):
+        if perm is not None:
+            import torch
+            inv = np.empty_like(perm)
+            inv[perm] = np.arange(perm.size)
+            st = st.index_select(1, torch.from_numpy(inv.astype(np.int64)).to(st.device))
+        new = obj.copy()
+        new.expr_data = DeviceMatrix(st.contiguous(), "states")
+        return new
     out = _unpermute(st, perm).astype(np.float64)
     out[out == 255] = -1.0
     new = obj.copy()
@@ -305,6 +355,25 @@ def predict_CNV_via_HMM_on_tumor_subclusters_per_chr(infercnv_obj, subclusters_p
     from .cnv_regions import overwrite_with_consensus
     hmm = _get_HMM(cnv_mean_sd, t)
     chrs = np.asarray(infercnv_obj.gene_order.chr)
+    if _resident(infercnv_obj):
+        import torch
+        from . import device
+        xt = infercnv_obj.expr_data.tensor
+        out = torch.full(xt.shape, 255, dtype=torch.uint8, device=xt.device)
+        for chr_name, groups in subclusters_per_chr.items():
+            rows = np.nonzero(chrs == chr_name)[0]
+            if rows.size == 0:
+                continue
+            groups = [np.asarray(g, dtype=np.int32) for g in (groups.values() if isinstance(groups, dict) else groups)]
+            sd = [_group_sd(len(g), cnv_mean_sd, cnv_level_to_mean_sd_fit) for g in groups]
+            st = _viterbi_groups(device.gather_matrix(xt, genes=rows), np.array([0, rows.size], dtype=np.int32), groups,
+                                 hmm["state_emission_params"]["mean"], sd, hmm["state_transitions"], hmm["delta"])
+            out[:, torch.from_numpy(rows.astype(np.int64)).to(xt.device)] = st
+        new = infercnv_obj.copy()
+        new.expr_data = DeviceMatrix(out, "states")
+        if infercnv_obj.tumor_subclusters is not None:
+            new = overwrite_with_consensus(new, _flatten_subclusters(infercnv_obj))
+        return new
     out = np.full(infercnv_obj.expr_data.shape, -1.0)
     for chr_name, groups in subclusters_per_chr.items():
         rows = np.nonzero(chrs == chr_name)[0]
@@ -424,10 +493,14 @@ def i3HMM_get_sd_trend(infercnv_obj: InfercnvObject, i3_p_val=0.05, seed=None, r
     idx = (infercnv_obj.get_reference_grouped_cell_indices() if infercnv_obj.has_reference_cells()
            else np.concatenate([np.asarray(v) for v in infercnv_obj.observation_grouped_cell_indices.values()]))
     L = _lib.load()
-    x = np.asfortranarray(infercnv_obj.expr_data, dtype=np.float64)
     ci, cp = i32(idx)
     buf = (ct.c_double * 2)()
-    check(L.icnv_cells_mean_sd(x.ctypes.data_as(ct.c_void_p), x.shape[0], x.shape[1], cp, ci.size, buf))   # mean / sd on the device
+    if _resident(infercnv_obj):
+        t = infercnv_obj.expr_data.tensor
+        check(L.icnv_cells_mean_sd_dev(ct.c_void_p(t.data_ptr()), t.shape[1], t.shape[0], cp, ci.size, buf, _stream()))
+    else:
+        x = np.asfortranarray(infercnv_obj.expr_data, dtype=np.float64)
+        check(L.icnv_cells_mean_sd(x.ctypes.data_as(ct.c_void_p), x.shape[0], x.shape[1], cp, ci.size, buf))   # mean / sd on the device
     mu, sigma = float(buf[0]), float(buf[1])
     ks = None
     if seed is not None or rng is not None:
@@ -477,6 +550,17 @@ def i3HMM_assign_HMM_states_to_proxy_expr_vals(infercnv_obj: InfercnvObject) -> 
 
 def _proxy(obj, K):
     L = _lib.load()
+    if _resident(obj):
+        # a states matrix in, an "expr" matrix out; what is not a state keeps its value, as below (255, untouched, reads -1)
+        import torch
+        from . import device
+        dm = obj.expr_data
+        st = dm.tensor if dm.kind == "states" else torch.where(dm.tensor < 0, 255.0, dm.tensor).to(torch.uint8)
+        out = device.states_to_proxy(st, K)
+        out = torch.where(torch.isnan(out), dm.float_tensor(), out)
+        new = obj.copy()
+        new.expr_data = DeviceMatrix(out)
+        return new
     st = np.asfortranarray(np.where(obj.expr_data < 0, 255, obj.expr_data).astype(np.uint8))
     out = np.empty(st.shape, dtype=np.float64, order="F")
     check(L.icnv_states_to_proxy(st.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), st.size, K))

@@ -22,9 +22,124 @@ class GeneOrder:
     stop: Optional[np.ndarray] = None
 
 
+class DeviceMatrix:
+    """A genes x cells matrix that lives where its tensor lives -- in HBM for a CUDA tensor -- in the slot `expr_data`
+    (DESIGN K32).  It wraps a contiguous (C cells, G genes) tensor, which is byte for byte R's column-major genes x cells
+    matrix (device.py), and reports R's shape: `.shape == (G, C)`.
+
+    kind "expr":   float64 values.
+    kind "states": uint8 HMM states, 255 = a cell no HMM touched (the state objects of hmm.py).
+
+    Nothing converts it silently: `__array__` raises TypeError, so NumPy code that has not been taught the type fails
+    loudly instead of pulling the matrix across PCIe.  `to_host()` is the one way out and `from_host()` the one way in;
+    both are counted (`DeviceMatrix.stats()`).  CPU tensors are accepted: the class works without a GPU, and then "across
+    PCIe" is a copy in host memory that is counted all the same."""
+
+    KINDS = {"expr": "float64", "states": "uint8"}
+    _stats = {"uploads": 0, "fetches": 0, "bytes_up": 0, "bytes_down": 0}
+
+    def __init__(self, tensor, kind: str = "expr"):
+        import torch
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be one of {sorted(self.KINDS)}, not {kind!r}")
+        want = getattr(torch, self.KINDS[kind])
+        if not (isinstance(tensor, torch.Tensor) and tensor.dim() == 2 and tensor.dtype == want and tensor.is_contiguous()):
+            raise TypeError(f"a {kind!r} DeviceMatrix wraps a contiguous {want} tensor of shape (cells, genes)")
+        self._t = tensor
+        self.kind = kind
+
+    # ---- what the object code reads ----------------------------------------
+    @property
+    def tensor(self):
+        return self._t
+
+    @property
+    def shape(self):
+        return (int(self._t.shape[1]), int(self._t.shape[0]))
+
+    ndim = 2
+
+    @property
+    def size(self):
+        return int(self._t.numel())
+
+    @property
+    def nbytes(self):
+        return int(self._t.numel() * self._t.element_size())
+
+    @property
+    def device(self):
+        return self._t.device
+
+    def float_tensor(self):
+        """The values as the host route's float64 matrix holds them, on the tensor's device: the tensor itself for "expr"; for
+        "states" a float64 copy with -1 for the untouched cells (what plot_cnv and the proxy steps read)."""
+        if self.kind == "expr":
+            return self._t
+        import torch
+        out = self._t.to(torch.float64)
+        out[self._t == 255] = -1.0
+        return out
+
+    def __repr__(self):
+        return f"DeviceMatrix(kind={self.kind!r}, shape={self.shape}, device={str(self._t.device)!r})"
+
+    def __array__(self, *args, **kwargs):
+        raise TypeError("a DeviceMatrix does not convert to a NumPy array by itself: this code path has not been wired for "
+                        "device-resident objects.  Call to_host() on the matrix (or on the InfercnvObject) to fetch it.")
+
+    # ---- the two counted crossings -----------------------------------------
+    @classmethod
+    def from_host(cls, array, kind: str = "expr", device=None):
+        """Upload the (G, C) host matrix an object holds.  States: float64 with -1 for untouched cells (hmm._states_obj)
+        or uint8 with 255."""
+        import torch
+        a = np.asarray(array)
+        if a.ndim != 2:
+            raise ValueError("expected a genes x cells matrix")
+        if kind == "states":
+            if a.dtype != np.uint8:
+                a = np.where(a < 0, 255, a).astype(np.uint8)
+        else:
+            a = a.astype(np.float64, copy=False)
+        host = torch.from_numpy(np.ascontiguousarray(a.T))
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        t = host.to(device).clone() if torch.device(device).type == "cpu" else host.to(device)
+        cls._stats["uploads"] += 1
+        cls._stats["bytes_up"] += int(t.numel() * t.element_size())
+        return cls(t, kind)
+
+    def to_host(self):
+        """The F-ordered (G, C) float64 array the host route holds in this slot; for states 255 becomes -1."""
+        cls = type(self)
+        cls._stats["fetches"] += 1
+        cls._stats["bytes_down"] += self.nbytes
+        a = self._t.cpu().numpy()                               # (C, G), C-contiguous
+        if self.kind == "states":
+            out = a.astype(np.float64)
+            out[a == 255] = -1.0
+            return out.T
+        return (a.copy() if self._t.device.type == "cpu" else a).T
+
+    @classmethod
+    def stats(cls, reset: bool = False):
+        """{"uploads", "fetches", "bytes_up", "bytes_down"} of every DeviceMatrix since the last reset."""
+        out = dict(cls._stats)
+        if reset:
+            for k in cls._stats:
+                cls._stats[k] = 0
+        return out
+
+
+def is_resident(infercnv_obj) -> bool:
+    """Does the object carry its matrix as a DeviceMatrix?"""
+    return isinstance(infercnv_obj.expr_data, DeviceMatrix)
+
+
 @dataclass
 class InfercnvObject:
-    expr_data: np.ndarray                                   # genes x cells, float64
+    expr_data: np.ndarray                                   # genes x cells, float64 -- or a DeviceMatrix (to_device())
     gene_order: GeneOrder
     reference_grouped_cell_indices: Dict[str, np.ndarray] = field(default_factory=dict)
     observation_grouped_cell_indices: Dict[str, np.ndarray] = field(default_factory=dict)
@@ -78,6 +193,31 @@ class InfercnvObject:
 
     def copy(self) -> "InfercnvObject":
         return copy.copy(self)
+
+    # ---- device residency (DESIGN K32) --------------------------------------
+    def is_resident(self) -> bool:
+        return isinstance(self.expr_data, DeviceMatrix)
+
+    def to_device(self, device=None) -> "InfercnvObject":
+        """A copy of the object whose expr_data -- and the hspike's with it -- is a DeviceMatrix on `device` (default: the
+        current CUDA device).  count_data and all metadata stay where they are.  A resident object is returned as it is."""
+        new = self.copy()
+        if not isinstance(self.expr_data, DeviceMatrix):
+            new.expr_data = DeviceMatrix.from_host(self.expr_data, "expr", device)
+        if self.hspike is not None:
+            new.hspike = self.hspike.to_device(device)
+        return new
+
+    def to_host(self) -> "InfercnvObject":
+        """The inverse of to_device(): expr_data (and the hspike's) as the F-ordered float64 host array."""
+        new = self.copy()
+        if isinstance(self.expr_data, DeviceMatrix):
+            new.expr_data = self.expr_data.to_host()
+        if isinstance(self.count_data, DeviceMatrix):           # (the counts of a spike-in that was simulated on the device)
+            new.count_data = self.count_data.to_host()
+        if self.hspike is not None:
+            new.hspike = self.hspike.to_host()
+        return new
 
     def validate(self):
         """validate_infercnv_obj (R/inferCNV.R:471-505), the checks relevant here."""

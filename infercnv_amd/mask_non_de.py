@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import device
-from .infercnv_object import InfercnvObject
+from .infercnv_object import DeviceMatrix, InfercnvObject
 
 MIN_CLUSTER_SIZE_MASK = 5   # .mask_DE_genes(min_cluster_size_mask = 5)
 
@@ -66,7 +66,10 @@ def get_DE_genes_basic(obj: InfercnvObject, p_val_thresh=0.05, test_use="wilcoxo
     p-values; they match no gene and are left out)."""
     import torch
     _check_test(test_use)
-    x = torch.from_numpy(np.ascontiguousarray(np.asarray(obj.expr_data, dtype=np.float64).T)).cuda()
+    if isinstance(obj.expr_data, DeviceMatrix):
+        x = obj.expr_data.tensor
+    else:
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(obj.expr_data, dtype=np.float64).T)).cuda()
     _, _, padj, entries = _tests(x, obj, test_use, seed, jitter)
     genes = np.asarray(obj.genes())
     out = {}
@@ -126,6 +129,9 @@ def mask_non_DE_genes_basic(obj: InfercnvObject, p_val_thresh=0.05, test_use="wi
     _check_test(test_use)
     if require_DE_all_normals not in device.DE_RULES:
         raise ValueError(f"Error, not recognizing require_DE_all_normals={require_DE_all_normals}")
+    if isinstance(obj.expr_data, DeviceMatrix):              # resident (DESIGN K32): a new tensor, the input object keeps its own
+        out, _ = mask_non_de_device(obj.expr_data.tensor, obj, p_val_thresh, test_use, center_val, require_DE_all_normals, seed, jitter)
+        return _with_expr(obj, DeviceMatrix(out))
     x = torch.from_numpy(np.ascontiguousarray(np.asarray(obj.expr_data, dtype=np.float64).T)).cuda()
     out, _ = mask_non_de_device(x, obj, p_val_thresh, test_use, center_val, require_DE_all_normals, seed, jitter, out=x)
     return _with_expr(obj, out.cpu().numpy().T.copy())

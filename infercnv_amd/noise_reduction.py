@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, i32, pack_groups
-from .infercnv_object import InfercnvObject
+from .infercnv_object import DeviceMatrix, InfercnvObject
 
 log = logging.getLogger("infercnv_amd")
 
@@ -26,6 +26,16 @@ def apply_median_filtering(infercnv_obj: InfercnvObject, window_size=7, on_obser
     if on_references:     # :75-86: each whole reference group
         for idx in infercnv_obj.reference_grouped_cell_indices.values():
             tiles.append(np.asarray(idx, dtype=np.int32))
+    if isinstance(infercnv_obj.expr_data, DeviceMatrix):   # resident (DESIGN K32): the same filter through its _dev entry
+        import torch
+        from . import device
+        from .ops import _dev_layout, _dev_unpermute
+        xt, perm, chr_start = _dev_layout(infercnv_obj)
+        out = device.median_filter(xt, chr_start, tiles, window_size=int(window_size), na_aware=bool(torch.isnan(xt).any()))
+        torch.cuda.current_stream().synchronize()
+        new = infercnv_obj.copy()
+        new.expr_data = DeviceMatrix(_dev_unpermute(out, perm))
+        return new
     L = _lib.load()
     perm, chr_start = infercnv_obj.chr_layout()
     x = np.asfortranarray(infercnv_obj.expr_data if perm is None else infercnv_obj.expr_data[perm], dtype=np.float64)

@@ -5,7 +5,10 @@ returns a new InfercnvObject whose `expr_data` was replaced -- and mirrors
 itself onto `hspike` where the reference does.
 
 These wrappers take host (numpy) matrices, like the R shim would hand over
-`expr.data`; use `infercnv_amd.device` for device-resident tensors.
+`expr.data`.  An object whose `expr_data` is a DeviceMatrix (InfercnvObject.to_device(),
+DESIGN K32) takes the same steps through the `_dev` entries of the library and comes
+back resident: host in, host out; device in, device out; nothing of the matrix's size
+crosses in between.
 """
 from __future__ import annotations
 
@@ -16,15 +19,70 @@ import numpy as np
 
 from . import _lib, smooth_windows as _sw
 from ._lib import Cfg, check
-from .infercnv_object import InfercnvObject
+from .infercnv_object import DeviceMatrix, InfercnvObject
 
 
 def _as_f(a):
     return np.asfortranarray(a, dtype=np.float64)
 
 
+# ------------------------------------------------------------------ device-resident objects (DESIGN K32)
+def _resident(obj) -> bool:
+    return isinstance(obj.expr_data, DeviceMatrix)
+
+
+def _vp(t):
+    return ct.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream():
+    import torch
+    return ct.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _dev_layout(obj):
+    """(the (C, G) tensor with the genes gathered into per-chromosome blocks, perm, chr_start) of a resident object: the
+    tensor itself when the object is already ordered, else one device.gather_matrix."""
+    from . import device
+    perm, chr_start = obj.chr_layout()
+    x = obj.expr_data.tensor
+    if perm is not None:
+        x = device.gather_matrix(x, genes=perm)
+    return x, perm, chr_start
+
+
+def _dev_unpermute(t, perm):
+    from . import device
+    if perm is None or t is None:
+        return t
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(perm.size)
+    return device.gather_matrix(t, genes=inv)
+
+
+def _run_chain_dev(obj, stage_mask, window_length, max_thresh, use_bounds, sd_amplifier, noise_filter, want_pre_denoise, inv_log,
+                   noise_logistic):
+    import torch
+    L = _lib.load()
+    x, perm, chr_start = _dev_layout(obj)
+    C, G = x.shape
+    if bool(torch.isnan(x).any()):
+        stage_mask = int(stage_mask) | _lib.ST_NA_AWARE
+    cfg = Cfg(G, C, chr_start, obj.ref_groups_or_proxy(), window_length, max_thresh, use_bounds, sd_amplifier,
+              noise_filter, stage_mask, inv_log, noise_logistic)
+    out = torch.empty_like(x)
+    pre = torch.empty_like(x) if want_pre_denoise else None
+    check(L.icnv_smooth_chain_dev(_vp(x), _vp(out), _vp(pre), cfg.ptr(), _stream()))
+    torch.cuda.current_stream().synchronize()
+    out, pre = _dev_unpermute(out, perm), _dev_unpermute(pre, perm)
+    return DeviceMatrix(out), (DeviceMatrix(pre) if pre is not None else None)
+
+
 def _run_chain(obj: InfercnvObject, stage_mask, *, window_length=101, max_thresh=None, use_bounds=True,
                sd_amplifier=1.5, noise_filter=None, want_pre_denoise=False, inv_log=False, noise_logistic=False):
+    if _resident(obj):
+        return _run_chain_dev(obj, stage_mask, window_length, max_thresh, use_bounds, sd_amplifier, noise_filter, want_pre_denoise,
+                              inv_log, noise_logistic)
     L = _lib.load()
     perm, chr_start = obj.chr_layout()
     x = _as_f(obj.expr_data if perm is None else obj.expr_data[perm])
@@ -57,6 +115,14 @@ def _with_expr(obj, expr, hspike=None):
 def _gene_stats(infercnv_obj):
     """(rowSums(expr), per-gene number of cells with expr > 0) from the HIP path."""
     L = _lib.load()
+    if _resident(infercnv_obj):
+        import torch
+        x = infercnv_obj.expr_data.tensor
+        C, G = x.shape
+        sums = torch.empty(G, dtype=torch.float64, device=x.device)
+        nnz = torch.empty(G, dtype=torch.int32, device=x.device)
+        check(L.icnv_gene_stats_dev(_vp(x), G, C, _vp(sums), _vp(nnz), _stream()))
+        return sums.cpu().numpy(), nnz.cpu().numpy()          # two vectors of G entries
     x = _as_f(infercnv_obj.expr_data)
     G, C = x.shape
     sums = np.empty(G, dtype=np.float64)
@@ -71,7 +137,11 @@ def _keep_gene_rows(infercnv_obj, keep):
     new = infercnv_obj.copy()
     if infercnv_obj.count_data is not None:
         cd = infercnv_obj.count_data                                   # a scipy sparse matrix (CreateInfercnvObject's sparse route) stays one
-        new.count_data = cd[keep] if hasattr(cd, "tocsc") else np.asarray(cd)[keep]
+        if isinstance(cd, DeviceMatrix):                              # (the counts of a spike-in simulated on the device)
+            from . import device
+            new.count_data = DeviceMatrix(device.gather_matrix(cd.tensor, genes=keep))
+        else:
+            new.count_data = cd[keep] if hasattr(cd, "tocsc") else np.asarray(cd)[keep]
     go = infercnv_obj.gene_order
     new.gene_order = type(go)(np.asarray(go.chr)[keep], None if go.start is None else np.asarray(go.start)[keep],
                               None if go.stop is None else np.asarray(go.stop)[keep])
@@ -84,6 +154,20 @@ def remove_genes(infercnv_obj: InfercnvObject, gene_indices_to_remove) -> Inferc
     """remove_genes (R/inferCNV.R:445-457): drops the rows (0-based here) from expr.data (on the device),
     count.data and gene_order."""
     L = _lib.load()
+    if _resident(infercnv_obj):
+        import torch
+        x = infercnv_obj.expr_data.tensor
+        C, G = x.shape
+        drop = np.zeros(G, dtype=bool)
+        drop[np.asarray(gene_indices_to_remove, dtype=np.int64)] = True
+        keep = np.nonzero(~drop)[0].astype(np.int32)
+        out = torch.empty((C, keep.size), dtype=torch.float64, device=x.device)
+        if keep.size:
+            check(L.icnv_select_genes_dev(_vp(x), G, C, keep.ctypes.data_as(ct.POINTER(ct.c_int32)), keep.size, _vp(out), _stream()))
+        new = _keep_gene_rows(infercnv_obj, keep)
+        new.expr_data = DeviceMatrix(out)
+        new.validate()
+        return new
     x = _as_f(infercnv_obj.expr_data)
     G, C = x.shape
     drop = np.zeros(G, dtype=bool)
@@ -121,11 +205,15 @@ def require_above_min_cells_ref(infercnv_obj: InfercnvObject, min_cells_per_gene
 # ------------------------------------------------------------------ steps 3 / 4 (ingest)
 def _normalize_log2(infercnv_obj, normalize_factor, do_norm, do_log):
     L = _lib.load()
+    nf = float("nan") if normalize_factor is None or (isinstance(normalize_factor, float) and math.isnan(normalize_factor)) \
+        else float(normalize_factor)
+    if _resident(infercnv_obj):
+        from . import device
+        return DeviceMatrix(device.normalize_log2(infercnv_obj.expr_data.tensor, normalize_factor=None if math.isnan(nf) else nf,
+                                                  do_normalize=do_norm, do_log2=do_log))
     x = _as_f(infercnv_obj.expr_data)
     out = np.empty_like(x, order="F")
     used = ct.c_double()
-    nf = float("nan") if normalize_factor is None or (isinstance(normalize_factor, float) and math.isnan(normalize_factor)) \
-        else float(normalize_factor)
     check(L.icnv_normalize_log2(x.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), x.shape[0], x.shape[1],
                                 nf, int(do_norm), int(do_log), ct.byref(used)))
     return out
@@ -151,6 +239,20 @@ def ingest_counts(infercnv_obj: InfercnvObject, min_mean_expr_cutoff=None, min_c
     bit.  Returns (object with the log-scale matrix of the kept genes, bytes uploaded)."""
     L = _lib.load()
     x = infercnv_obj.expr_data
+    if _resident(infercnv_obj):
+        # the counts are float64 on the device: checked and narrowed to int32 there, then the same fused entry; nothing is uploaded
+        import torch
+        from . import device
+        t = x.tensor
+        if not bool(torch.equal(t, torch.round(t))):
+            raise ValueError("ingest_counts wants integer counts")
+        G, C = x.shape
+        expr, keep, _ = device.ingest_counts(device.DeviceCounts(G, C, dense=t.to(torch.int32)), min_mean_expr_cutoff,
+                                             min_cells_per_gene, normalize_factor)
+        torch.cuda.current_stream().synchronize()
+        new = _keep_gene_rows(infercnv_obj, keep)
+        new.expr_data = DeviceMatrix(expr.contiguous())
+        return new, 0
     is_sparse = hasattr(x, "tocsc")
     if sparse is None:
         sparse = is_sparse
@@ -204,6 +306,9 @@ def subtract_ref_expr_from_obs(infercnv_obj: InfercnvObject, inv_log=False, use_
 def get_average_bounds(infercnv_obj: InfercnvObject):
     """R/inferCNV_ops.R:2723-2742 -> (lower, upper)."""
     L = _lib.load()
+    if _resident(infercnv_obj):
+        from . import device
+        return device.average_bounds(infercnv_obj.expr_data.tensor)
     x = _as_f(infercnv_obj.expr_data)
     out = (ct.c_double * 2)()
     check(L.icnv_average_bounds(x.ctypes.data_as(ct.c_void_p), x.shape[0], x.shape[1], out))
@@ -213,9 +318,16 @@ def get_average_bounds(infercnv_obj: InfercnvObject):
 def scale_infercnv_expr(infercnv_obj: InfercnvObject) -> InfercnvObject:
     """Step 5 of run() (scale_data, off by default; R/inferCNV_ops.R:3174-3185): t(scale(t(expr.data))), mirrored on the hspike."""
     L = _lib.load()
-    x = _as_f(infercnv_obj.expr_data)
-    out = np.empty_like(x, order="F")
-    check(L.icnv_scale_genes(x.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), x.shape[0], x.shape[1]))
+    if _resident(infercnv_obj):
+        import torch
+        x = infercnv_obj.expr_data.tensor
+        out = torch.empty_like(x)
+        check(L.icnv_scale_genes_dev(_vp(x), _vp(out), x.shape[1], x.shape[0], _stream()))
+        out = DeviceMatrix(out)
+    else:
+        x = _as_f(infercnv_obj.expr_data)
+        out = np.empty_like(x, order="F")
+        check(L.icnv_scale_genes(x.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), x.shape[0], x.shape[1]))
     hs = scale_infercnv_expr(infercnv_obj.hspike) if infercnv_obj.hspike is not None else None
     return _with_expr(infercnv_obj, out, hs)
 
@@ -284,10 +396,18 @@ def remove_outliers_norm(infercnv_obj: InfercnvObject, out_method="average_bound
             raise ValueError("please provide an approved method for outlier removal")    # stop(991)
         lower_bound = upper_bound = float("nan")
     L = _lib.load()
-    x = _as_f(infercnv_obj.expr_data)
-    out = np.empty_like(x, order="F")
-    check(L.icnv_remove_outliers(x.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), x.shape[0], x.shape[1],
-                                 float(lower_bound), float(upper_bound), None))
+    if _resident(infercnv_obj):
+        import torch
+        x = infercnv_obj.expr_data.tensor
+        out = torch.empty_like(x)
+        check(L.icnv_remove_outliers_dev(_vp(x), _vp(out), x.shape[1], x.shape[0], float(lower_bound), float(upper_bound), None, _stream()))
+        torch.cuda.current_stream().synchronize()
+        out = DeviceMatrix(out)
+    else:
+        x = _as_f(infercnv_obj.expr_data)
+        out = np.empty_like(x, order="F")
+        check(L.icnv_remove_outliers(x.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), x.shape[0], x.shape[1],
+                                     float(lower_bound), float(upper_bound), None))
     hs = None
     if infercnv_obj.hspike is not None:
         hs = remove_outliers_norm(infercnv_obj.hspike, out_method, None if math.isnan(lower_bound) else lower_bound,
@@ -326,6 +446,11 @@ def smooth_by_chromosome(infercnv_obj: InfercnvObject, window_length, smooth_end
 def _smooth_windows(obj: InfercnvObject, smooth_method, window_length):
     """The window operator (icnv_smooth_windows, DESIGN K16) on obj.expr_data with the table of `smooth_method`."""
     L = _lib.load()
+    if _resident(obj):
+        from . import device
+        x, perm, _ = _dev_layout(obj)
+        table = _sw.table_for(obj, smooth_method, window_length)
+        return DeviceMatrix(_dev_unpermute(device.smooth_windows(x, table), perm))
     perm, _ = obj.chr_layout()
     table = _sw.table_for(obj, smooth_method, window_length)
     x = _as_f(obj.expr_data if perm is None else obj.expr_data[perm])

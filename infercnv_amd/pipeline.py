@@ -19,7 +19,7 @@ import os
 
 import numpy as np
 
-from .infercnv_object import InfercnvObject
+from .infercnv_object import DeviceMatrix, InfercnvObject
 
 log = logging.getLogger("infercnv_amd")
 
@@ -85,6 +85,9 @@ def states_not_constant(states) -> bool:
       - otherwise: a list with one entry per cell; the entries differ in length, so `unique` keeps at least two.
     Only the first case can give 1, and it does when the whole matrix holds a single value: the gate is "the state matrix is
     not constant"."""
+    if isinstance(states, DeviceMatrix):   # a resident state matrix (DESIGN K32): one comparison on the device, one flag back
+        t = states.tensor.reshape(-1)
+        return True if t.numel() == 0 else bool((t != t[0]).any())
     s = np.asarray(states)
     if s.size == 0:
         return True           # length(unique(list())) is 0, and 0 != 1
@@ -316,6 +319,9 @@ def check_arguments(a):
 
 
 def _integral(x):
+    if isinstance(x, DeviceMatrix):
+        import torch
+        return bool(torch.equal(x.tensor, torch.round(x.tensor)))
     if hasattr(x, "tocsc"):
         x = x.data
     x = np.asarray(x)

@@ -93,7 +93,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .infercnv_object import GeneOrder, InfercnvObject
+from .infercnv_object import DeviceMatrix, GeneOrder, InfercnvObject
 
 WRITER_VERSION = 0x00040000
 MIN_READER_VERSION = 0x00030500
@@ -1117,6 +1117,8 @@ def _names(a):
 
 def _matrix_value(m, genes, cells, x_dev=None):
     dimnames = {"dimnames": [genes, cells]}
+    if x_dev is None and isinstance(m, DeviceMatrix):       # a resident object (DESIGN K32) is encoded from where it lives
+        x_dev = m.float_tensor()
     if x_dev is not None:
         if tuple(x_dev.shape) != (len(cells), len(genes)):
             raise ValueError(f"x_dev has the shape {tuple(x_dev.shape)}, the object's matrix is (cells, genes) = {(len(cells), len(genes))}")

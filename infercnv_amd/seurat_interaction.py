@@ -20,7 +20,7 @@ from decimal import Decimal
 import numpy as np
 
 from .cnv_regions import _cell_groups, _fmt, _range_reduce
-from .infercnv_object import InfercnvObject
+from .infercnv_object import DeviceMatrix, InfercnvObject
 
 CENTER_STATE = {"i6": 3, "i3": 2}
 N_STATES = {"i6": 6, "i3": 3}
@@ -140,6 +140,11 @@ def device_pass(infercnv_obj: InfercnvObject, hmm_obj, HMM_type="i6", by_cells=F
             raise ValueError("the state matrix and the final object differ in shape")
         if perm is not None:
             states = states[:, torch.as_tensor(perm, device=states.device)].contiguous()
+    elif isinstance(hmm_obj.expr_data, DeviceMatrix):       # a resident state object (DESIGN K32): its bytes as they lie
+        from .cnv_regions import _states_dev
+        if hmm_obj.expr_data.shape != infercnv_obj.expr_data.shape:
+            raise ValueError("the state object and the final object differ in shape")
+        states = _states_dev(hmm_obj.expr_data, perm)
     else:
         st = np.asarray(hmm_obj.expr_data)
         if st.shape != infercnv_obj.expr_data.shape:

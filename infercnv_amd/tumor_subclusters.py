@@ -27,7 +27,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib, device
-from .infercnv_object import InfercnvObject
+from .infercnv_object import DeviceMatrix, InfercnvObject
 from .loess_fit import loess_fit, window_points
 
 log = logging.getLogger("infercnv_amd")
@@ -42,9 +42,7 @@ def parallelDist(infercnv_obj: InfercnvObject, cells, as_dist: bool = True):
     cells = np.asarray(cells, dtype=np.int32)
     if cells.ndim != 1 or cells.size < 1:
         raise ValueError("cells must be a non-empty index vector")
-    x = infercnv_obj.expr_data
-    xd = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64).T)).cuda()
-    d = device.cell_distances(xd, cells).cpu().numpy()
+    d = device.cell_distances(_to_device(infercnv_obj), cells).cpu().numpy()
     if not as_dist:
         return d
     iu = np.triu_indices(cells.size, k=1)
@@ -73,9 +71,16 @@ def zscore_outlier_genes(infercnv_obj: InfercnvObject, z_score_filter: float = 0
     """The reference-based gene filter of define_signif_tumor_subclusters (R/inferCNV_tumor_subclusters.R:45-71): with
     z_score_filter > 0 and reference cells, z = (ref - mean(ref)) / sd(ref) over the whole reference matrix and the genes
     whose mean |z| is >= 0.8 (the literal; z_score_filter only switches the filter on).  Returns the outliers' 0-based
-    row numbers (ascending), or None when the filter does not apply."""
+    row numbers (ascending), or None when the filter does not apply.
+    A device-resident object (DeviceMatrix) takes the statistics from the device (device.zscore_gene_filter, DESIGN K32:
+    double-double sums rounded once, where this host code follows R's long-double sums -- a row mean may differ by an ulp);
+    only the G-byte decision crosses."""
     if not (z_score_filter > 0 and infercnv_obj.has_reference_cells()):
         return None
+    if isinstance(infercnv_obj.expr_data, DeviceMatrix):
+        import torch
+        _, _, row_mean = device.zscore_gene_filter(infercnv_obj.expr_data.tensor, infercnv_obj.get_reference_grouped_cell_indices())
+        return torch.nonzero(row_mean >= 0.8).flatten().cpu().numpy().astype(np.int64)
     x = np.asarray(infercnv_obj.expr_data, dtype=np.float64)
     ref = x[:, infercnv_obj.get_reference_grouped_cell_indices()]
     m, s = _r_mean(ref), _r_sd(ref)
@@ -87,7 +92,7 @@ def zscore_outlier_genes(infercnv_obj: InfercnvObject, z_score_filter: float = 0
 def zscore_kept_genes(infercnv_obj: InfercnvObject, z_score_filter: float = 0.8):
     """The rows of expr.data the subclustering goes on with (R/inferCNV_tumor_subclusters.R:45-71).  When the filter applies
     and finds no outlier, R's `expr.data[-outliers, ]` with `outliers = integer(0)` keeps NO row: mirrored as such."""
-    G = np.asarray(infercnv_obj.expr_data).shape[0]
+    G = infercnv_obj.expr_data.shape[0]
     out = zscore_outlier_genes(infercnv_obj, z_score_filter)
     if out is None:
         return np.arange(G, dtype=np.int64)
@@ -98,6 +103,8 @@ def zscore_kept_genes(infercnv_obj: InfercnvObject, z_score_filter: float = 0.8)
 
 def _to_device(infercnv_obj):
     import torch
+    if isinstance(infercnv_obj.expr_data, DeviceMatrix):       # resident: the tensor itself, nothing crosses (states: as float64)
+        return infercnv_obj.expr_data.float_tensor()
     x = np.asarray(infercnv_obj.expr_data, dtype=np.float64)
     return torch.from_numpy(np.ascontiguousarray(x.T)).cuda()
 
@@ -107,7 +114,7 @@ def nn2(infercnv_obj: InfercnvObject, cells, k: int, genes=None):
     Returns (nn_idx, nn_dists) as numpy arrays of shape (len(cells), k); nn_idx holds 0-based positions in `cells`
     (R's nn.idx is 1-based).  Exactly equal distances are ordered by position (RANN's order among them is its tree walk)."""
     cells = np.asarray(cells, dtype=np.int32)
-    G = np.asarray(infercnv_obj.expr_data).shape[0]
+    G = infercnv_obj.expr_data.shape[0]
     genes = np.arange(G, dtype=np.int32) if genes is None else np.asarray(genes, dtype=np.int32)
     if cells.ndim != 1 or genes.ndim != 1:
         raise ValueError("cells and genes must be index vectors")
@@ -188,7 +195,7 @@ def hclust(infercnv_obj: InfercnvObject, cells, method: str = "ward.D2", genes=N
     genes: 0-based rows (default all; the z-score-filtered genes of :45-71 come from `zscore_kept_genes`).  labels are the
     cells' column names (InfercnvObject.cells())."""
     cells = np.asarray(cells, dtype=np.int32)
-    G = np.asarray(infercnv_obj.expr_data).shape[0]
+    G = infercnv_obj.expr_data.shape[0]
     genes = np.arange(G, dtype=np.int32) if genes is None else np.asarray(genes, dtype=np.int32)
     if cells.ndim != 1 or genes.ndim != 1:
         raise ValueError("cells and genes must be index vectors")
@@ -207,7 +214,7 @@ def redo_hierarchical_clustering(infercnv_obj: InfercnvObject, hclust_method) ->
     for g, c in groups.items():
         if c.size < 2:   # R's hclust stops: "must have n >= 2 objects to cluster"
             raise ValueError(f"group {g!r} has {c.size} cell(s): must have n >= 2 objects to cluster")
-    genes = np.arange(np.asarray(infercnv_obj.expr_data).shape[0], dtype=np.int32)
+    genes = np.arange(infercnv_obj.expr_data.shape[0], dtype=np.int32)
     res = device.hclust_cells(_to_device(infercnv_obj), [(genes, c.astype(np.int32)) for c in groups.values()], hclust_method)
     cell_names = np.asarray(infercnv_obj.cells())
     out = infercnv_obj.copy()
@@ -341,7 +348,7 @@ def define_signif_tumor_subclusters_via_random_smooothed_trees(infercnv_obj: Inf
 
     def clade_fn(clades):
         if not x:
-            x.append(torch.from_numpy(np.ascontiguousarray(np.asarray(sub.expr_data, dtype=np.float64).T)).cuda())
+            x.append(_to_device(sub))
         trees, rand = device.random_trees(x[0], [c for _, c in clades], [fnv1a64(n) for n, _ in clades], window_size,
                                           RANDOM_TREES_ITERATIONS, seed, hclust_method)
         rand = rand.cpu().numpy()
@@ -397,7 +404,7 @@ def leiden_simple_snn(infercnv_obj: InfercnvObject, cells, k_nn, resolution_para
     """.leiden_simple_snn(expr.data[genes, cells], k_nn, resolution_parameter, objective_function)
     (R/inferCNV_tumor_subclusters.R:725-741): the exact kNN (K8) and the Leiden partition (K11), both on the GPU."""
     cells = np.asarray(cells, dtype=np.int32)
-    G = np.asarray(infercnv_obj.expr_data).shape[0]
+    G = infercnv_obj.expr_data.shape[0]
     genes = np.arange(G, dtype=np.int32) if genes is None else np.asarray(genes, dtype=np.int32)
     idx, _ = device.knn(_to_device(infercnv_obj), [(genes, cells)], k_nn)
     return cluster_leiden(idx, resolution_parameter, objective_function, seed=seed, token=token)
@@ -577,7 +584,7 @@ def leiden_seurat_preprocess_routine(infercnv_obj: InfercnvObject, cells, k_nn, 
     (R/inferCNV_tumor_subclusters.R:699-723) for one problem, by the library's contract (include/icnv.h, K18): a 1-based numpy
     int32 membership.  Falls back to `leiden_simple_snn` where the reference's FindVariableFeatures would warn."""
     cells = np.asarray(cells, dtype=np.int32)
-    G = np.asarray(infercnv_obj.expr_data).shape[0]
+    G = infercnv_obj.expr_data.shape[0]
     genes = np.arange(G, dtype=np.int32) if genes is None else np.asarray(genes, dtype=np.int32)
     return _leiden_problems(_to_device(infercnv_obj), [genes], [(cells, token)], k_nn, "PCA", objective_function, resolution_parameter,
                             _device_leiden(seed), _device_leiden_graph(seed))[0]
@@ -718,7 +725,7 @@ def _leiden_per_chr(infercnv_obj, x, kept, groups, k_nn, leiden_method, objectiv
     _, first = np.unique(chr_all, return_index=True)
     levels = chr_all[np.sort(first)]
     present = set(chrs.tolist())
-    C = np.asarray(infercnv_obj.expr_data).shape[1]
+    C = infercnv_obj.expr_data.shape[1]
     out = {c: {} for c in levels}
     problems, genes, keys = [], [], []
     for c in levels:
