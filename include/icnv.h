@@ -883,6 +883,49 @@ int icnv_mcmc_diag_dev(const double *theta_samples, int32_t n_regions, int32_t n
 int icnv_mcmc_diag(const double *theta_samples, int32_t n_regions, int32_t n_chains, int32_t n_keep, int32_t K, double *chain_stats,
                    double *pooled);
 
+/* ---- Probability heatmaps and tables of the Bayesian filter (K33) ---------------------------------------------------------
+ * The numbers under postProbNormal's heatmaps and plotProbabilities' PDFs (R/inferCNV_BayesNet.R:757-844, 1110-1190).  The
+ * pages, axes and text stay in R.  Not bound in the R shim.
+ *
+ * icnv_paint_regions_dev: postProbNormal's matrix -- expr.data[,] <- 0, then for region r in order
+ * expr.data[Genes_r, Cells_r] <- value[r] -- for every region of a run at once.  The float64 sibling of
+ * icnv_state_fill_regions_dev, with its argument conventions: out is DEVICE doubles, element (gene g, cell c) at
+ * out[c * ld + g], ld >= G; gene_first, gene_count (int32), cell_off (int64, n_regions + 1, from 0, monotone), cell_idx
+ * (int32, n_idx entries, cell_off[n_regions] <= n_idx) and value (doubles) are DEVICE arrays.  Region r covers the genes
+ * gene_first[r] .. + gene_count[r] - 1 of the cells cell_idx[cell_off[r] .. cell_off[r + 1] - 1].  Afterwards, for g < G:
+ *   out[c * ld + g] = +0.0 where no region covers (g, c), else value[r] of the HIGHEST r that covers it (R's loop: the last
+ *   writer wins), with value[r]'s bits as they are (-0.0, NaN).  Regions may overlap and may list a cell twice.
+ *   The padding columns g >= G are not touched.  gene_count[r] == 0 or an empty cell list paints nothing; n_regions == 0
+ *   gives the zero matrix (the region arrays may then be null).
+ * Every index is checked on the device before a byte of out is written (0 <= gene_first, 0 <= gene_count, gene_first +
+ * gene_count <= G, 0 <= cell < C, the offsets' rules above): ICNV_ERR_ARG leaves out untouched.  The result does not depend on
+ * the launch geometry and no floating-point atomic is used: on the zeroed matrix every covered element takes the unsigned
+ * 64-bit integer maximum of r + 1 over its regions, and a second pass replaces every non-zero owner o by value[o - 1].  The
+ * check synchronises the stream; the paint itself is left running on it.  Timer names: "paint_check", "paint_regions". */
+int icnv_paint_regions_dev(double *out, int64_t G, int64_t C, int64_t ld, int32_t n_regions, const int32_t *gene_first,
+                           const int32_t *gene_count, const int64_t *cell_off, const int32_t *cell_idx, int64_t n_idx,
+                           const double *value, void *stream);
+
+/* icnv_theta_box_dev: the box statistics of plot_cnv_prob's box plot, per (region, state) over the pooled kept theta draws.
+ * The library's own contract, modelled on ggplot2's stat_boxplot (coef = 1.5): believed, not verified against ggplot2.
+ * Restated sequentially in tests/bayes_probs_restate.py.
+ * theta_samples: DEVICE doubles [n_regions, n_chains, n_keep, K] exactly as icnv_bayes_sample_dev lays them out.
+ * box: DEVICE doubles [n_regions, K, 7] = ymin, lower, middle, upper, ymax, n_low, n_high.
+ * Over the N = n_chains n_keep draws y of a (region, state), ascending with -0.0 counted as +0.0:
+ *   lower, middle, upper = quantile(type = 7) at 0.25, 0.5, 0.75 in the operation order of icnv_quantiles_excluding, as the
+ *     pooled quantiles of icnv_mcmc_diag_dev (stat_boxplot's quantiles at 0 and 1 are the extremes, which it then replaces by
+ *     ymin and ymax below: they are not formed);
+ *   iqr = upper - lower;  lo = lower - 1.5 * iqr;  hi = upper + 1.5 * iqr   (every operation rounded by itself, no FMA);
+ *   n_low = #{y < lo}, n_high = #{y > hi} (strict comparisons; stored as doubles);
+ *   ymin, ymax = the smallest and the largest draw inside [lo, hi] (NaN if there is none, which needs infinite draws).
+ * A (region, state) with a NaN draw -- a region without cells -- gives NaN in all seven fields.  A constant series gives five
+ * equal numbers and no outliers.
+ * Refusals before any launch: a null pointer, n_regions < 0, n_keep < 1, K or n_chains outside 2 .. 8: ICNV_ERR_ARG.
+ * N > 8192 (the draws are sorted in LDS by the sort of icnv_mcmc_diag_dev; no memory fallback) or more than 2^31 - 1 (region,
+ * state) pairs: ICNV_ERR_UNSUPPORTED.  n_regions == 0 does nothing.  Synchronises.  Timer name: "theta_box". */
+int icnv_theta_box_dev(const double *theta_samples, int32_t n_regions, int32_t n_chains, int32_t n_keep, int32_t K, double *box,
+                       void *stream);
+
 /* ---- per-cell CNV features and run-length segmentation (K14) -------------------------------------------------------------
  * The numbers behind add_to_seurat's map_metadata_from_infercnv.txt (.get_features, R/seurat_interaction.R:244-353) and the
  * segmentation of state columns into CNV regions (.define_cnv_gene_regions, R/inferCNV_HMM.R:1005-1057, called per cell

@@ -170,6 +170,8 @@ PROTOTYPES = {
     "icnv_mcmc_diag_dev": (ct.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "icnv_mcmc_diag": (ct.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "icnv_state_fill_regions_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "icnv_paint_regions_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "icnv_theta_box_dev": (ct.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "icnv_cnv_features_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _i32, _i32, _i32, _vp, _vp, _vp]),
     "icnv_cnv_features": (ct.c_int, [_vp, _i64, _i64, _ip, _i32, _i32, _i32, _vp, _vp]),
     "icnv_cnv_runs_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _i32, _ip, _i64, _i32, _i32, _vp, _i32, _i64, _vp, _i64p, _i64p, _vp]),

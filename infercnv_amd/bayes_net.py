@@ -4,7 +4,8 @@ inferCNVBayesNet / filterHighPNormals (R/inferCNV_BayesNet.R) on the GPU sampler
 The reference fits one JAGS mixture model per region; here every region of a run goes through ONE likelihood pass and ONE
 sampler launch (device.bayes_loglik / device.bayes_sample, contract in include/icnv.h).  The posterior is the same, the random
 stream is this library's own (seeded, per draw), so probabilities agree with JAGS up to Monte-Carlo error, not bit for bit.
-Plotting (postProbNormal, plotProbabilities, mcmcDiagnosticPlots) stays out; the numbers under mcmcDiagnosticPlots' plots
+The pages R draws stay in R; what is under them is built here: postProbNormal's heatmaps go through heatmap.plot_cnv and
+plotProbabilities' stacked bars and box plots are written as tables (DESIGN K33); the numbers under mcmcDiagnosticPlots' plots
 and table are mcmc_diagnostics (DESIGN K31).  Index vectors are 0-based (R: 1-based); states keep R's numbering 1..K."""
 from __future__ import annotations
 
@@ -36,7 +37,8 @@ class MCMCInferCNV:
     mu / sig: state means and PRECISIONS (1 / sd^2, MeanSD :148-198); group_id: per cell the 1-based number of its cell
     group (NA_INTEGER elsewhere); cnv_probabilities: per region the kept theta samples (K n_keep x K) when they were asked
     for, else None; cnv_means: K x regions, their column means (what the reference takes from them); cell_probabilities:
-    per region the K x |Cells| state frequencies of eps; args: the arguments of the call."""
+    per region the K x |Cells| state frequencies of eps; args: the arguments of the call.  cell_prob_rows (table route):
+    every region's cell_probabilities transposed and stacked, (cell_off[-1], K), the rows of region r at table.cell_off[r]."""
     infercnv_obj: InfercnvObject
     cnv_regions: List[str] = field(default_factory=list)
     cell_gene: List[dict] = field(default_factory=list)
@@ -49,6 +51,7 @@ class MCMCInferCNV:
     args: dict = field(default_factory=dict)
     x_dev: object = None                      # the (C, G) CUDA matrix the sampler reads
     table: object = None                      # route="table": the RegionTable behind the four per-region sequences
+    cell_prob_rows: Optional[np.ndarray] = None
 
 
 # ---- the table route (DESIGN K25) ---------------------------------------------------------------------------------------
@@ -239,6 +242,7 @@ def run_mcmc_table(obj: "MCMCInferCNV") -> "MCMCInferCNV":
     R = len(t)
     if R == 0:
         obj.cnv_probabilities, obj.cell_probabilities, obj.cnv_means = _LazySeq(0, None), _LazySeq(0, None), np.zeros((K, 0))
+        obj.cell_prob_rows = np.zeros((0, K))
         return obj
     _, L, off = device.bayes_loglik_arrays(obj.x_dev, t.row_first, t.gene_count, t.cell_idx, t.cell_off, obj.mu, obj.sig)
     theta_sum, samples, freq = device.bayes_sample(L, off, t.token, a["n_adapt"], a["n_burn"], a["n_keep"], a["seed"],
@@ -252,7 +256,9 @@ def run_mcmc_table(obj: "MCMCInferCNV") -> "MCMCInferCNV":
     obj.cnv_means = (tot / n).T.copy()
     samples = samples.cpu().numpy() if samples is not None else None
     obj.cnv_probabilities = _LazySeq(R, (lambda r: samples[r].reshape(-1, K)) if samples is not None else (lambda r: None))
-    obj.cell_probabilities = _LazySeq(R, lambda r: (freq[off[r]:off[r + 1]].astype(np.float64) / n).T.copy())
+    rows = freq.astype(np.float64) / n
+    obj.cell_prob_rows = rows
+    obj.cell_probabilities = _LazySeq(R, lambda r: rows[off[r]:off[r + 1]].T.copy())
     return obj
 
 
@@ -363,6 +369,16 @@ def inferCNVBayesNet(infercnv_obj: InfercnvObject, HMM_states, HMM_type="i6", by
 
 
 # ---- step 19 ----------------------------------------------------------------------------------------------------------
+class _NoStates:
+    """kept_regions' stand-in for _States: the filter's decisions are taken and no matrix is rewritten."""
+
+    def fill(self, genes, cells, value):
+        pass
+
+    def result(self):
+        return None
+
+
 class _States:
     """The state matrix where the caller holds it: a (cells, genes) CUDA tensor stays on the device and its rectangles are
     rewritten there; a genes x cells host array is rewritten on the host.  Either way the input itself is left alone."""
@@ -391,8 +407,9 @@ class _States:
         return self.m
 
 
-def _remove_cnv(obj: MCMCInferCNV, st: _States):
-    """removeCNV (R/inferCNV_BayesNet.R:562-630): strictly above the threshold; a region without cells (NaN) stays."""
+def _remove_cnv(obj: MCMCInferCNV, st: _States, write=True):
+    """removeCNV (R/inferCNV_BayesNet.R:562-630): strictly above the threshold; a region without cells (NaN) stays.
+    write: also rewrite CNV_State_Probabilities.dat (kept_regions leaves the file to the filter)."""
     normal = _normal_state(obj.args["HMM_type"])
     thr = obj.args["BayesMaxPNormal"]
     p_normal = obj.cnv_means[normal - 1] if obj.cnv_means.size else np.zeros(0)
@@ -409,7 +426,8 @@ def _remove_cnv(obj: MCMCInferCNV, st: _States):
     obj.cell_probabilities = [obj.cell_probabilities[i] for i in keep]
     obj.cnv_probabilities = [obj.cnv_probabilities[i] for i in keep]
     obj.cnv_means = obj.cnv_means[:, keep]
-    _write_state_probabilities(obj.args.get("out_dir"), [cg["cnv_regions"] for cg in obj.cell_gene], obj.cnv_means)
+    if write:
+        _write_state_probabilities(obj.args.get("out_dir"), [cg["cnv_regions"] for cg in obj.cell_gene], obj.cnv_means)
     return obj
 
 
@@ -423,23 +441,19 @@ def _write_state_probabilities(out_dir, names, cnv_means):
             fh.write("\t".join([f"State:{k + 1}"] + [cnv_regions._fmt(float(v)) if v == v else "NaN" for v in cnv_means[k]]) + "\n")
 
 
-def _filter_table(mcmc_obj: MCMCInferCNV, HMM_states, BayesMaxPNormal):
-    """filterHighPNormals on the table route: removeCNV's and reassignCNV's decisions as array expressions -- strictly above
-    the threshold, a NaN column stays and keeps its HMM state, the first maximum is the new state -- and ONE
-    device.fill_regions call for every rectangle: the normal state for the removed regions, the new state for the kept ones
-    when reassignCNVs is set, 0 (leave alone) otherwise."""
+def _decide_table(mcmc_obj: MCMCInferCNV, BayesMaxPNormal, write=True):
+    """The decisions of filterHighPNormals on the table route, as array expressions: removeCNV's -- strictly above the
+    threshold, a NaN column stays and keeps its HMM state -- and reassignCNV's -- the first maximum is the new state.
+    -> (the filtered object, value): value[r] is the byte device.fill_regions writes over region r of mcmc_obj.table -- the
+    normal state for the removed regions, the new state for the kept ones when reassignCNVs is set, 0 (leave alone) otherwise;
+    None when there is no postMcmcMethod.  write: also rewrite CNV_State_Probabilities.dat when a region was removed."""
     import copy
-    import torch
     obj = copy.copy(mcmc_obj)
     obj.args = dict(mcmc_obj.args, BayesMaxPNormal=BayesMaxPNormal)
     t = mcmc_obj.table
-    on_device = isinstance(HMM_states, torch.Tensor)
-    if on_device and (not HMM_states.is_cuda or HMM_states.dim() != 2):
-        raise TypeError("HMM_states: a genes x cells array or a (cells, genes) CUDA tensor")
-    host = None if on_device else np.asarray(HMM_states)
     method = obj.args.get("postMcmcMethod")
     if method is None:
-        return obj, (HMM_states.clone() if on_device else np.array(host))
+        return obj, None
     if method != "removeCNV":
         raise ValueError('postMcmcMethod = "removeCells" is not built on the table route')
     normal = _normal_state(obj.args["HMM_type"])
@@ -459,8 +473,25 @@ def _filter_table(mcmc_obj: MCMCInferCNV, HMM_states, BayesMaxPNormal):
     cell_p, cnv_p = mcmc_obj.cell_probabilities, mcmc_obj.cnv_probabilities
     obj.cell_probabilities = _LazySeq(kept.size, lambda i: cell_p[int(kept[i])])
     obj.cnv_probabilities = _LazySeq(kept.size, lambda i: cnv_p[int(kept[i])])
-    if remove.any():
+    if mcmc_obj.cell_prob_rows is not None:
+        obj.cell_prob_rows = mcmc_obj.cell_prob_rows[_ranges(t.cell_off[:-1][kept], np.diff(t.cell_off)[kept])]
+    if write and remove.any():
         _write_state_probabilities(obj.args.get("out_dir"), list(obj.cnv_regions), obj.cnv_means)
+    return obj, value
+
+
+def _filter_table(mcmc_obj: MCMCInferCNV, HMM_states, BayesMaxPNormal):
+    """filterHighPNormals on the table route: the decisions of _decide_table and ONE device.fill_regions call for every
+    rectangle."""
+    import torch
+    t = mcmc_obj.table
+    on_device = isinstance(HMM_states, torch.Tensor)
+    if on_device and (not HMM_states.is_cuda or HMM_states.dim() != 2):
+        raise TypeError("HMM_states: a genes x cells array or a (cells, genes) CUDA tensor")
+    host = None if on_device else np.asarray(HMM_states)
+    obj, value = _decide_table(mcmc_obj, BayesMaxPNormal)
+    if value is None:
+        return obj, (HMM_states.clone() if on_device else np.array(host))
 
     def fill(m):
         if value.any():
@@ -516,24 +547,39 @@ def filterHighPNormals(mcmc_obj: MCMCInferCNV, HMM_states, BayesMaxPNormal):
     (cells, genes) CUDA tensor, which stays on the device and is rewritten there; a new array / tensor of the same kind comes
     back.  The object passed in is not modified.  A DeviceMatrix of states (DESIGN K32) is a uint8 CUDA tensor in a wrapper:
     it is filtered as one and comes back wrapped."""
-    import copy
     if isinstance(HMM_states, DeviceMatrix):
         t = HMM_states.tensor if HMM_states.kind == "states" else cnv_regions._states_dev(HMM_states)
         obj, out = filterHighPNormals(mcmc_obj, t, BayesMaxPNormal)
         return obj, DeviceMatrix(out.contiguous(), "states")
     if mcmc_obj.table is not None:
         return _filter_table(mcmc_obj, HMM_states, BayesMaxPNormal)
+    st = _States(HMM_states)
+    return _filter_dict(mcmc_obj, st, BayesMaxPNormal), st.result()
+
+
+def _filter_dict(mcmc_obj: MCMCInferCNV, st, BayesMaxPNormal, write=True):
+    """filterHighPNormals' decisions on the dict route; the rectangles go to st (a _States, or _NoStates)."""
+    import copy
     obj = copy.copy(mcmc_obj)
     obj.cell_gene = [dict(cg) for cg in mcmc_obj.cell_gene]
     obj.cnv_regions = list(mcmc_obj.cnv_regions)
     obj.args = dict(mcmc_obj.args, BayesMaxPNormal=BayesMaxPNormal)
-    st = _States(HMM_states)
     method = obj.args.get("postMcmcMethod")
     if method is not None:
-        obj = _remove_cnv(obj, st) if method == "removeCNV" else _remove_cells(obj, st)
+        obj = _remove_cnv(obj, st, write) if method == "removeCNV" else _remove_cells(obj, st)
         if obj.args.get("reassignCNVs"):
             obj = _reassign_cnv(obj, st)
-    return obj, st.result()
+    return obj
+
+
+def kept_regions(mcmc_obj: MCMCInferCNV, BayesMaxPNormal) -> MCMCInferCNV:
+    """The MCMC object filterHighPNormals(mcmc_obj, states, BayesMaxPNormal)[0] returns -- the regions that stay, cell_gene with
+    the reassigned State, their means and cell probabilities, args with the threshold -- derived without a state matrix
+    (DESIGN K33): run() hands an on_step hook the MCMC object at step 18 and only the filtered HMM object at step 19.  Nothing
+    is written; the object passed in is not modified."""
+    if mcmc_obj.table is not None:
+        return _decide_table(mcmc_obj, BayesMaxPNormal, write=False)[0]
+    return _filter_dict(mcmc_obj, _NoStates(), BayesMaxPNormal, write=False)
 
 
 # ---- convergence diagnostics of the chains (DESIGN K31) -----------------------------------------------------------------
@@ -569,17 +615,21 @@ def write_mcmc_diagnostics(diag: McmcDiagnostics, out_dir, device_rows=MCMC_DEVI
     """CNV_MCMC_Diagnostics.dat in out_dir: write.table(sep = "\\t", quote = FALSE) of diag.table() with R's number formatting.
     A small table goes through heatmap.write_table; from device_rows rows on the numbers are formatted on the device and
     streamed (heatmap.write_matrix, DESIGN K20): the bytes are the same."""
+    os.makedirs(out_dir, exist_ok=True)
+    return _write_tsv(os.path.join(out_dir, MCMC_TABLE_FILE), diag.table(), diag.row_names(), MCMC_TABLE_COLUMNS, device_rows)
+
+
+def _write_tsv(path, tab, names, columns, device_rows):
+    """write.table(sep = "\\t", quote = FALSE) of the matrix tab with R's number formatting: through heatmap.write_table, and
+    from device_rows rows on formatted on the device and streamed (heatmap.write_matrix, DESIGN K20).  The bytes are the same."""
     import torch
     from . import heatmap
-    os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, MCMC_TABLE_FILE)
-    tab, names = diag.table(), diag.row_names()
     if 0 < device_rows <= tab.shape[0]:
         x = torch.from_numpy(np.ascontiguousarray(tab)).cuda()
         heatmap.write_matrix(path, x, np.arange(tab.shape[0], dtype=np.int32), "cell_rows", row_names=names,
-                             col_names=MCMC_TABLE_COLUMNS, quote=False, sep="\t")
+                             col_names=columns, quote=False, sep="\t")
     else:
-        heatmap.write_table(path, tab.tolist(), row_names=names, col_names=MCMC_TABLE_COLUMNS, quote=False, sep="\t")
+        heatmap.write_table(path, tab.tolist(), row_names=names, col_names=columns, quote=False, sep="\t")
     return path
 
 
@@ -602,6 +652,24 @@ def _resample(obj: MCMCInferCNV, lo, hi):
     return device.bayes_sample(L, off, tokens, a["n_adapt"], a["n_burn"], a["n_keep"], a["seed"], want_samples=True)[1]
 
 
+def _sample_batches(mcmc_obj: MCMCInferCNV, max_sample_bytes):
+    """(lo, hi, samples) over the object's regions in order: the kept theta samples of the regions lo .. hi - 1 as a
+    (hi - lo, K, n_keep, K) CUDA tensor, in batches that fit max_sample_bytes (K n_keep K doubles per region; at least one
+    region per batch).  The held samples of a keep_samples = True object are uploaded; else the regions are sampled again
+    (_resample).  The caller drops a batch before it asks for the next."""
+    import torch
+    K, n_keep, R = len(mcmc_obj.mu), int(mcmc_obj.args["n_keep"]), len(mcmc_obj.cnv_regions)
+    batch = max(1, int(max_sample_bytes) // (K * n_keep * K * 8))
+    held = R > 0 and mcmc_obj.cnv_probabilities[0] is not None
+    for lo in range(0, R, batch):
+        hi = min(R, lo + batch)
+        if held:
+            host = np.stack([np.asarray(mcmc_obj.cnv_probabilities[r], dtype=np.float64).reshape(K, n_keep, K) for r in range(lo, hi)])
+            yield lo, hi, torch.from_numpy(host).to(mcmc_obj.x_dev.device)
+        else:
+            yield lo, hi, _resample(mcmc_obj, lo, hi)
+
+
 def mcmc_diagnostics(mcmc_obj: MCMCInferCNV, *, max_sample_bytes=2 << 30, out_dir=None) -> McmcDiagnostics:
     """Convergence diagnostics of every region's chains (DESIGN K31): R-hat, effective sample size, Geweke scores,
     autocorrelations and the pooled quantiles, as a table one can filter -- the data under mcmcDiagnosticPlots' PDFs.
@@ -609,20 +677,10 @@ def mcmc_diagnostics(mcmc_obj: MCMCInferCNV, *, max_sample_bytes=2 << 30, out_di
     regions are sampled again in batches whose kept samples fit max_sample_bytes (K n_keep K doubles per region; at least one
     region per batch), and device.mcmc_diag runs on each batch; the result does not depend on the batching.  An object that
     holds its samples (keep_samples = True) is not sampled again.  out_dir: also write CNV_MCMC_Diagnostics.dat there."""
-    import torch
-    a = mcmc_obj.args
-    K, n_keep, R = len(mcmc_obj.mu), int(a["n_keep"]), len(mcmc_obj.cnv_regions)
+    K, R = len(mcmc_obj.mu), len(mcmc_obj.cnv_regions)
     cs = np.empty((R, K, K, len(device.MCMC_CHAIN_FIELDS)))
     po = np.empty((R, K, len(device.MCMC_POOLED_FIELDS)))
-    batch = max(1, int(max_sample_bytes) // (K * n_keep * K * 8))
-    held = R > 0 and mcmc_obj.cnv_probabilities[0] is not None
-    for lo in range(0, R, batch):
-        hi = min(R, lo + batch)
-        if held:
-            host = np.stack([np.asarray(mcmc_obj.cnv_probabilities[r], dtype=np.float64).reshape(K, n_keep, K) for r in range(lo, hi)])
-            samples = torch.from_numpy(host).to(mcmc_obj.x_dev.device)
-        else:
-            samples = _resample(mcmc_obj, lo, hi)
+    for lo, hi, samples in _sample_batches(mcmc_obj, max_sample_bytes):
         c, p = device.mcmc_diag(samples)
         cs[lo:hi], po[lo:hi] = c.cpu().numpy(), p.cpu().numpy()
         del samples
@@ -636,3 +694,156 @@ def mcmc_diagnostics(mcmc_obj: MCMCInferCNV, *, max_sample_bytes=2 << 30, out_di
     if out_dir is not None:
         write_mcmc_diagnostics(diag, out_dir)
     return diag
+
+
+# ---- the probability heatmaps and tables (DESIGN K33) -------------------------------------------------------------------
+def _region_arrays(obj: MCMCInferCNV):
+    """(first row, row count, cell_off, cell_idx) of the object's regions in the object's own gene order, as arrays."""
+    if obj.table is not None:
+        t = obj.table
+        return t.row_first, t.gene_count, t.cell_off, t.cell_idx
+    runs = [_gene_run(cg["Genes"], cg["cnv_regions"]) for cg in obj.cell_gene]
+    cells = [np.asarray(cg["Cells"], dtype=np.int32).ravel() for cg in obj.cell_gene]
+    off = np.concatenate([[0], np.cumsum([c.size for c in cells])]).astype(np.int64)
+    return (np.array([r[0] for r in runs], dtype=np.int32), np.array([r[1] for r in runs], dtype=np.int32), off,
+            np.concatenate(cells) if cells else np.zeros(0, dtype=np.int32))
+
+
+def _region_names(obj: MCMCInferCNV):
+    """The region names as one array of strings (the table route's are put together chromosome-wise, not one by one)."""
+    if obj.table is not None:
+        t = obj.table
+        if len(t) == 0:
+            return np.zeros(0, dtype=str)
+        return np.char.add(np.char.add(np.asarray(t.chr_names).astype(str)[t.chr], "-region_"), t.ordinal.astype(str))
+    return np.array([str(n) for n in obj.cnv_regions], dtype=str)
+
+
+def normal_probability_matrix(mcmc_obj: MCMCInferCNV):
+    """postProbNormal's matrix (R/inferCNV_BayesNet.R:763-774) as a (C, G) CUDA float64 tensor: 0 everywhere, then
+    1 - cnv_means[normal state, r] (one rounded subtraction) over region r's genes x cells, regions in order -- where two
+    overlap the later one stays -- in one device.paint_regions call (DESIGN K33)."""
+    import torch
+    normal = _normal_state(mcmc_obj.args["HMM_type"])
+    means = np.asarray(mcmc_obj.cnv_means, dtype=np.float64)
+    value = 1.0 - means[normal - 1] if means.size else np.zeros(0)
+    G, C = mcmc_obj.infercnv_obj.expr_data.shape
+    dev = mcmc_obj.x_dev.device if mcmc_obj.x_dev is not None else "cuda"
+    out = torch.empty((C, G), dtype=torch.float64, device=dev)
+    g0, ng, off, idx = _region_arrays(mcmc_obj)
+    return device.paint_regions(out, g0, ng, off, idx, value)
+
+
+def _plots_off(args):
+    return bool(args.get("no_plot")) or args.get("plotingProbs") is False
+
+
+def postProbNormal(mcmc_obj: MCMCInferCNV, title, output_filename, out_dir=None, useRaster=True):
+    """postProbNormal (R/inferCNV_BayesNet.R:757-788): the heatmap of 1 - P(normal) of every region, through heatmap.plot_cnv
+    on a copy of the object's infercnv object whose expr_data is normal_probability_matrix() as a DeviceMatrix, with R's
+    arguments (k_obs_groups and cluster_by_groups from the object's args, write_expr_matrix = FALSE, x.center = 0,
+    x.range = c(0, 1)).  out_dir defaults to the object's args["out_dir"].  Writes what plot_cnv writes for them and returns
+    its settings; writes nothing and returns None when the object's args hold no_plot (or plotingProbs = False)."""
+    from . import heatmap
+    a = mcmc_obj.args
+    if _plots_off(a):
+        return None
+    out_dir = a.get("out_dir") if out_dir is None else out_dir
+    if out_dir is None:
+        raise ValueError("postProbNormal: no out_dir, neither given nor in the object's args")
+    plot_obj = mcmc_obj.infercnv_obj.copy()
+    plot_obj.expr_data = DeviceMatrix(normal_probability_matrix(mcmc_obj), "expr")
+    return heatmap.plot_cnv(plot_obj, out_dir=out_dir, k_obs_groups=a.get("k_obs_groups", 1),
+                            cluster_by_groups=a.get("cluster_by_groups", True), title=title, output_filename=output_filename,
+                            write_expr_matrix=False, x_center=0, x_range=(0, 1), useRaster=useRaster)
+
+
+BOX_TABLE_COLUMNS = device.BOX_FIELDS
+
+
+def _r_threshold(v):
+    """sprintf("%s", BayesMaxPNormal)."""
+    if isinstance(v, (bool, np.bool_)):
+        return "TRUE" if v else "FALSE"
+    if isinstance(v, (float, np.floating)):
+        return "%.15g" % v
+    return str(v)
+
+
+@dataclass
+class CnvProbabilities:
+    """What plotProbabilities (R/inferCNV_BayesNet.R:808-844) draws, as numbers.  regions: the region names; box: (regions, K,
+    7) host array, device.BOX_FIELDS of the pooled kept theta draws per region and state (plot_cnv_prob's box plot;
+    device.theta_box: the library's own contract, modelled on ggplot2's stat_boxplot: believed, not verified against it);
+    cell_off / cell_idx: region r's cells are cell_idx[cell_off[r] : cell_off[r + 1]] in the region's order; cell_probs:
+    (cell_off[-1], K), per (region, cell) its state frequencies over all chains' kept draws (plot_cell_prob's stacked bar);
+    cell_names: the names of all cells of the object; threshold: the object's BayesMaxPNormal (None: unset).  States keep R's
+    numbering: index k is state k + 1."""
+    regions: Sequence
+    box: np.ndarray
+    cell_off: np.ndarray
+    cell_idx: np.ndarray
+    cell_probs: np.ndarray
+    cell_names: np.ndarray
+    threshold: object = None
+    box_fields: tuple = device.BOX_FIELDS
+
+    def file_names(self):
+        """(cnvProbs.<p>.dat, cellProbs.<p>.dat): R's PDF names (:819-836) with the tables' extension."""
+        p = "" if self.threshold is None else "." + _r_threshold(self.threshold)
+        return f"cnvProbs{p}.dat", f"cellProbs{p}.dat"
+
+    def cnv_table(self):
+        R, K = self.box.shape[:2]
+        return self.box.reshape(R * K, -1)
+
+    def cnv_row_names(self):
+        K = self.box.shape[1]
+        state = np.char.add(":State:", np.arange(1, K + 1).astype(str))
+        return np.char.add(np.repeat(np.asarray(self.regions, dtype=str), K), np.tile(state, len(self.regions)))
+
+    def cell_columns(self):
+        return tuple(f"State:{k + 1}" for k in range(self.cell_probs.shape[1]))
+
+    def cell_row_names(self):
+        region = np.repeat(np.asarray(self.regions, dtype=str), np.diff(self.cell_off))
+        return np.char.add(np.char.add(region, ":"), np.asarray(self.cell_names).astype(str)[self.cell_idx])
+
+
+def write_cnv_probabilities(probs: CnvProbabilities, out_dir, device_rows=MCMC_DEVICE_TABLE_ROWS):
+    """cnvProbs.<p>.dat -- one row <region>:State:<k> per (region, state), columns device.BOX_FIELDS -- and cellProbs.<p>.dat --
+    one row <region>:<cell name> per (region, cell), columns State:1 .. State:K -- in out_dir, tab-separated with R's number
+    formatting, through the writers of write_mcmc_diagnostics.  Returns the two paths."""
+    os.makedirs(out_dir, exist_ok=True)
+    cnv_name, cell_name = probs.file_names()
+    return (_write_tsv(os.path.join(out_dir, cnv_name), probs.cnv_table(), probs.cnv_row_names(), BOX_TABLE_COLUMNS, device_rows),
+            _write_tsv(os.path.join(out_dir, cell_name), probs.cell_probs, probs.cell_row_names(), probs.cell_columns(), device_rows))
+
+
+def plotProbabilities(mcmc_obj: MCMCInferCNV, out_dir=None, *, max_sample_bytes=2 << 30,
+                      device_rows=MCMC_DEVICE_TABLE_ROWS) -> CnvProbabilities:
+    """plotProbabilities (R/inferCNV_BayesNet.R:808-844) as data (DESIGN K33): per region the box statistics of every state's
+    pooled kept theta draws (device.theta_box) and every cell's state probabilities.  mcmc_obj: what inferCNVBayesNet returned
+    (either route), or a filtered object (kept_regions, filterHighPNormals) -- R plots the filtered one.  The samples come as
+    mcmc_diagnostics gets them: the held ones of a keep_samples = True object, else the regions are sampled again in batches
+    that fit max_sample_bytes; the result does not depend on the batching.  out_dir: also write cnvProbs.<p>.dat and
+    cellProbs.<p>.dat there (write_cnv_probabilities; nothing is written when the object's args hold no_plot).  The PDFs stay
+    in R."""
+    K, R = len(mcmc_obj.mu), len(mcmc_obj.cnv_regions)
+    box = np.empty((R, K, len(device.BOX_FIELDS)))
+    for lo, hi, samples in _sample_batches(mcmc_obj, max_sample_bytes):
+        box[lo:hi] = device.theta_box(samples).cpu().numpy()
+        del samples
+    _, _, off, idx = _region_arrays(mcmc_obj)
+    if mcmc_obj.table is not None and mcmc_obj.cell_prob_rows is not None:
+        cell_probs = mcmc_obj.cell_prob_rows
+    else:
+        parts = [np.asarray(mcmc_obj.cell_probabilities[r], dtype=np.float64).T for r in range(R)]
+        cell_probs = np.concatenate(parts) if parts else np.zeros((0, K))
+    probs = CnvProbabilities(regions=_region_names(mcmc_obj), box=box, cell_off=np.asarray(off, dtype=np.int64),
+                             cell_idx=np.asarray(idx, dtype=np.int64), cell_probs=np.ascontiguousarray(cell_probs),
+                             cell_names=np.asarray(mcmc_obj.infercnv_obj.cells()), threshold=mcmc_obj.args.get("BayesMaxPNormal"))
+    log.info("CNV and cell probabilities: %d regions, %d (region, cell) rows", R, probs.cell_probs.shape[0])
+    if out_dir is not None and not _plots_off(mcmc_obj.args):
+        write_cnv_probabilities(probs, out_dir, device_rows)
+    return probs

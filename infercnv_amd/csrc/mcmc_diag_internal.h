@@ -212,6 +212,26 @@ MCMC_HD inline void mcmc_pooled_stats(const double *x, const double *sorted, boo
 }
 
 #if defined(__HIPCC__)
+// The LDS sort of the pooled draws, shared by the diagnostics (K31) and the box statistics (K33): buf[0 .. N - 1] become
+// ascending with -0.0 as +0.0, buf[N .. n_pad - 1] (n_pad a power of two >= N) +inf.  Bitonic, in place; every thread of the
+// workgroup calls it (tid of nt), after a barrier that made buf visible; it ends on a barrier.  No draw may be NaN.
+__device__ inline void mcmc_lds_sort(double *buf, int N, int n_pad, int tid, int nt) {
+    for (int q = tid; q < n_pad; q += nt) {
+        if (q >= N) buf[q] = __builtin_inf();
+        else if (buf[q] == 0.0) buf[q] = 0.0;
+    }
+    __syncthreads();
+    for (int kk = 2; kk <= n_pad; kk <<= 1)
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int p = tid; p < (n_pad >> 1); p += nt) {
+                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
+                const double u = buf[i], v = buf[l];
+                if (((i & kk) == 0) ? (u > v) : (u < v)) { buf[i] = v; buf[l] = u; }
+            }
+            __syncthreads();
+        }
+}
+
 struct McmcDiagArgs {
     const double *samples;     // [n_regions, n_chains, n_keep, K]
     double *chain_stats;       // [n_regions, K, n_chains, 9]

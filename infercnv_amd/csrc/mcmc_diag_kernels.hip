@@ -123,21 +123,7 @@ __global__ void __launch_bounds__(MCMC_NT_MAX) mcmc_diag_kernel(McmcDiagArgs a) 
 
     // the pooled draws ascending, -0.0 as +0.0 (a NaN among them: no order, the quantiles are NaN)
     if (!any_nan) {
-        const int n_pad = a.n_pad;
-        for (int q = tid; q < n_pad; q += nt) {
-            if (q >= N) buf[q] = __builtin_inf();
-            else if (buf[q] == 0.0) buf[q] = 0.0;
-        }
-        __syncthreads();
-        for (int kk = 2; kk <= n_pad; kk <<= 1)
-            for (int j = kk >> 1; j > 0; j >>= 1) {
-                for (int p = tid; p < (n_pad >> 1); p += nt) {
-                    const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
-                    const double u = buf[i], v = buf[l];
-                    if (((i & kk) == 0) ? (u > v) : (u < v)) { buf[i] = v; buf[l] = u; }
-                }
-                __syncthreads();
-            }
+        mcmc_lds_sort(buf, N, a.n_pad, tid, nt);
     } else {
         __syncthreads();
     }

@@ -1865,6 +1865,55 @@ def fill_regions(states, gene_first, gene_count, cell_off, cell_idx, value):
     return states
 
 
+def paint_regions(out, gene_first, gene_count, cell_off, cell_idx, value):
+    """postProbNormal's matrix in one call (icnv_paint_regions_dev, DESIGN K33), IN PLACE: out (C, G) float64 CUDA tensor, rows
+    `ld` apart, becomes +0.0 everywhere and then value[r] over region r = the genes gene_first[r] .. + gene_count[r] - 1 of the
+    cells cell_idx[cell_off[r] : cell_off[r + 1]], regions in order: where they overlap the highest r stays.  The region arrays
+    are CUDA tensors (int32, int32, int64, int32, float64) or anything numpy converts, which is uploaded.  ValueError (out
+    untouched) when an index is out of range."""
+    L = _lib.load()
+    C, G, ld = _check_matrix_ld(out)
+
+    def dev(a, dtype):
+        if isinstance(a, torch.Tensor):
+            if not (a.is_cuda and a.dtype == dtype and a.dim() == 1 and a.is_contiguous()):
+                raise TypeError(f"region arrays must be contiguous one-dimensional CUDA tensors ({dtype})")
+            return a
+        np_dtype = {torch.int32: np.int32, torch.int64: np.int64, torch.float64: np.float64}[dtype]
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype).ravel()).to(out.device)
+
+    g0, ng, off = dev(gene_first, torch.int32), dev(gene_count, torch.int32), dev(cell_off, torch.int64)
+    idx, val = dev(cell_idx, torch.int32), dev(value, torch.float64)
+    n = int(g0.numel())
+    if ng.numel() != n or val.numel() != n or off.numel() != n + 1:
+        raise ValueError("one gene_first, gene_count and value per region, and regions + 1 offsets")
+    rc = L.icnv_paint_regions_dev(_ptr(out), G, C, ld, n, _ptr(g0), _ptr(ng), _ptr(off), _ptr(idx) if idx.numel() else None,
+                                  int(idx.numel()), _ptr(val), _stream())
+    if rc == _lib.ERR_ARG:
+        raise ValueError(L.icnv_last_error().decode("utf-8", "replace"))
+    check(rc)
+    return out
+
+
+BOX_FIELDS = ("ymin", "lower", "middle", "upper", "ymax", "n_low", "n_high")
+
+
+def theta_box(theta_samples):
+    """The box statistics of every (region, state) over its pooled kept theta draws (icnv_theta_box_dev, DESIGN K33; the
+    library's own contract, modelled on ggplot2's stat_boxplot).  theta_samples: contiguous (regions, n_chains, n_keep, K) CUDA
+    float64 tensor as bayes_sample(want_samples=True) returns it.  Returns the (regions, K, 7) CUDA float64 tensor of
+    BOX_FIELDS.  Synchronises the device."""
+    L = _lib.load()
+    t = theta_samples
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 4 and t.is_contiguous()):
+        raise TypeError("theta_samples must be a contiguous (regions, n_chains, n_keep, K) CUDA float64 tensor")
+    R, m, n, K = (int(v) for v in t.shape)
+    box = torch.empty((R, K, len(BOX_FIELDS)), dtype=torch.float64, device=t.device)
+    check(L.icnv_theta_box_dev(_ptr(t) if t.numel() else _ptr(box.new_empty(1)), R, m, n, K,
+                               _ptr(box) if box.numel() else _ptr(box.new_empty(1)), _stream()))
+    return box
+
+
 def state_consensus(states, groups, overwrite=False):
     """.get_state_consensus (R/inferCNV_HMM.R:977-987) per group -> (n_groups, G) uint8; with
     overwrite=True also returns the state matrix with every member cell set to its group's consensus."""

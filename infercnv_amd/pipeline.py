@@ -6,10 +6,12 @@ tumor_subclusters, hmm, cnv_regions, bayes_net, mask_non_de, heatmap), each a th
 is what R's run() alone wrote down: the order, the guards, `up_to_step`, which object each stage reads, and the file-name
 tokens through which steps 17-20 find each other's files (`file_tokens`, `states_not_constant`).
 
-Not mirrored: resume (`resume_mode`), the Bayes plots (`plot_probabilities`, `diagnostics`), `plot_subclusters`, and the
-options the library does not build (they raise NotImplementedError before anything runs).  run() itself serialises nothing
-(`save_rds`, `save_final_rds` are accepted and ignored); `on_step` is the hook for checkpoints, and `rds_checkpoints` the
-hook that writes R's serialised step objects under R's file names (DESIGN K27).
+Not mirrored: resume (`resume_mode`), `plot_subclusters`, and the options the library does not build (they raise
+NotImplementedError before anything runs).  run() itself draws none of the Bayes plots (`plot_probabilities` and `diagnostics`
+are accepted and ignored) and serialises nothing (`save_rds`, `save_final_rds` likewise); `on_step` is the hook for all three:
+`bayes_probabilities_hook` writes the probability heatmaps and the tables under plotProbabilities' PDFs (DESIGN K33),
+`mcmc_diagnostics_hook` the table under the diagnostic plots (DESIGN K31), and `rds_checkpoints` R's serialised step objects
+under R's file names (DESIGN K27).
 """
 from __future__ import annotations
 
@@ -252,9 +254,58 @@ def mcmc_diagnostics_hook(out_dir, *, max_sample_bytes=2 << 30, **run_args):
     return on_step
 
 
+def bayes_probabilities_hook(out_dir, *, max_sample_bytes=2 << 30, **run_args):
+    """An on_step(step, label, obj) callable for run() that does what `plot_probabilities = TRUE` stands for in infercnv::run
+    (DESIGN K33).  At step 18, where run() passes the MCMC object, it writes into R's `BayesNetOutput.<token>` directory under
+    out_dir (file_tokens), in R's order (R/inferCNV_BayesNet.R:1350-1361, 1429-1437):
+
+      infercnv.NormalProbabilities.PreFiltering    bayes_net.postProbNormal of the object, " (1 - Probabilities of Normal)
+                                                   Before Filtering": whatever heatmap.plot_cnv writes under that name
+      cnvProbs.<p>.dat, cellProbs.<p>.dat          bayes_net.plotProbabilities of kept = bayes_net.kept_regions(obj,
+                                                   BayesMaxPNormal), the object step 19's filter will return (<p>: the threshold)
+      infercnv.NormalProbabilities.PostFiltering   postProbNormal of kept, " (1 - Probabilities of Normal) With Threshold <p>"
+
+    Every other step is ignored.  run_args: the arguments run() is called with; the ones the directory depends on,
+    BayesMaxPNormal, k_obs_groups, cluster_by_groups, useRaster, no_plot and plot_probabilities are read, the others ignored.
+    With no_plot = True or plot_probabilities = False nothing is written and one line is logged.  The record of the last call
+    is kept as on_step.probabilities.  run()'s own `plot_probabilities` argument stays accepted and ignored: the PDFs are R's.
+    The regions are sampled again for the box statistics (as mcmc_diagnostics_hook samples them for its own table)."""
+    a = {"HMM": False, "HMM_type": "i6", "analysis_mode": "subclusters", "tumor_subcluster_partition_method": "leiden",
+         "BayesMaxPNormal": 0.5, "k_obs_groups": 1, "cluster_by_groups": True, "useRaster": True, "no_plot": False,
+         "plot_probabilities": True}
+    a.update({k: v for k, v in run_args.items() if k in a})
+    for k, choices in (("HMM_type", HMM_TYPES), ("analysis_mode", ANALYSIS_MODES), ("tumor_subcluster_partition_method", PARTITION_METHODS)):
+        a[k] = _match_arg(k, a[k], choices)
+    target = os.path.join(out_dir, file_tokens(a["HMM"], a["HMM_type"], a["analysis_mode"], a["tumor_subcluster_partition_method"],
+                                               a["BayesMaxPNormal"])["bayes_dir"])
+    off = bool(a["no_plot"]) or not a["plot_probabilities"]
+
+    def on_step(step, label, obj):
+        if step != 18:
+            return
+        if off:
+            log.info("bayes_probabilities_hook: no_plot / plot_probabilities = FALSE, nothing is written")
+            return
+        import copy
+        from . import bayes_net
+        obj = copy.copy(obj)                     # the plots' arguments ride in args, as in R's MCMC_inferCNV object
+        obj.args = dict(obj.args, k_obs_groups=a["k_obs_groups"], cluster_by_groups=a["cluster_by_groups"], no_plot=False)
+        thr = a["BayesMaxPNormal"]
+        bayes_net.postProbNormal(obj, " (1 - Probabilities of Normal) Before Filtering", "infercnv.NormalProbabilities.PreFiltering",
+                                 out_dir=target, useRaster=a["useRaster"])
+        kept = bayes_net.kept_regions(obj, thr)
+        on_step.probabilities = bayes_net.plotProbabilities(kept, target, max_sample_bytes=max_sample_bytes)
+        bayes_net.postProbNormal(kept, " (1 - Probabilities of Normal) With Threshold %s" % bayes_net._r_threshold(thr),
+                                 "infercnv.NormalProbabilities.PostFiltering", out_dir=target, useRaster=a["useRaster"])
+
+    on_step.probabilities = None
+    on_step.out_dir = target
+    return on_step
+
+
 def chain_hooks(*hooks):
     """One on_step(step, label, obj) that calls every hook given, in order (None entries are skipped): rds_checkpoints next to
-    mcmc_diagnostics_hook, for instance."""
+    mcmc_diagnostics_hook and bayes_probabilities_hook, for instance."""
     hooks = [h for h in hooks if h is not None]
 
     def on_step(step, label, obj):

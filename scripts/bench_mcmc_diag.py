@@ -74,7 +74,8 @@ def mcmc_object(obj, x):
     return m
 
 
-def subclusters_shape(G, C, max_bytes):
+def subclusters_object(G, C):
+    """-> (the MCMCInferCNV object of the shape, L, off, tokens)."""
     from bench_bayes import predicted_regions
     from infercnv_amd import device, synth
     from infercnv_amd.tumor_subclusters import fnv1a64
@@ -93,10 +94,15 @@ def subclusters_shape(G, C, max_bytes):
     m.cell_gene = [{"cnv_regions": n, "Genes": np.arange(g0, g0 + ng), "Cells": c, "State": s} for n, (g0, ng, c), s in zip(names, regions, st)]
     m.cnv_probabilities = [None] * len(names)
     _, L, off = device.bayes_loglik(pre, regions, m.mu, m.sig)
-    return measure("subclusters", m, L, off, [fnv1a64(n) for n in names], max_bytes)
+    return m, L, off, [fnv1a64(n) for n in names]
 
 
-def cells_shape(G, C, share, n_slice, max_bytes, n_restate):
+def subclusters_shape(G, C, max_bytes):
+    return measure("subclusters", *subclusters_object(G, C), max_bytes)
+
+
+def cells_object(G, C, share, n_slice):
+    """-> (the MCMCInferCNV object of the shape on the table route, L, off, tokens, the number of regions)."""
     from bench_cnv_reports import make_object
     from infercnv_amd import bayes_net, device
     obj = make_object(G, C, share, 2)
@@ -108,7 +114,13 @@ def cells_shape(G, C, share, n_slice, max_bytes, n_restate):
     m.cnv_probabilities = bayes_net._LazySeq(cut, lambda r: None)
     t = m.table
     _, L, off = device.bayes_loglik_arrays(x, t.row_first, t.gene_count, t.cell_idx, t.cell_off, MU, TAU)
-    r = measure("cells", m, L, off, t.token, max_bytes)
+    return m, L, off, t.token, cut
+
+
+def cells_shape(G, C, share, n_slice, max_bytes, n_restate):
+    from infercnv_amd import bayes_net
+    m, L, off, tokens, cut = cells_object(G, C, share, n_slice)
+    r = measure("cells", m, L, off, tokens, max_bytes)
     r["cells"] = n_slice
     restate = None
     if n_restate:
