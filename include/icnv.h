@@ -503,7 +503,9 @@ void icnv_leiden_stats_reset(void);   /* R/inferCNV_tumor_subclusters.R:736 */
  *   number of entries (HOST); fill writes the CSR (DEVICE): row_off [sum n_p + 1] over the batch, col ascending positions
  *   within the problem, shared = s_ij, weight = (2 s 2^24 + d) / (2 d) with d = 2 k - s in integer division (s / d in 24-bit
  *   fixed point, rounded to nearest), loop [sum n_p] = 1 (s_ii = k: every node carries a loop of weight 2^24).  An nn_idx
- *   entry outside [0, n_p): ICNV_ERR_ARG from a device check.  1 <= k <= min(128, n_p).  end frees the state.
+ *   entry outside [0, n_p): ICNV_ERR_ARG from a device check.  N(i) is a set: an nn_idx row that repeats an entry is
+ *   ICNV_ERR_ARG too, from a device check on the sorted transposed lists before any row is counted (no handle, the outputs
+ *   untouched); icnv_knn_dev never makes such a row.  So s_ij <= k and d >= k.  1 <= k <= min(128, n_p).  end frees the state.
  * icnv_leiden_graph_dev: icnv_leiden_dev (K11, its contract above word for word) on a caller's weighted graphs instead of
  *   nn_idx: level 0 has the edge weights `weight` (int64 >= 1), s_i = sum of row i's weights + 2 loop_weight loop_i; node
  *   weight 1 (CPM) or s_i (modularity); r = gamma (CPM: the caller scales gamma by its weight unit) or gamma / sum s.  The CSR

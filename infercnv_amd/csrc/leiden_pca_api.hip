@@ -226,6 +226,10 @@ int icnv_snn_begin_dev(const int32_t *nn_idx, int32_t k, const int32_t *node_off
     ICNV_HIP(hipMemcpyAsync(&bad, h->d_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ICNV_HIP(hipStreamSynchronize(s));
     if (bad) ICNV_FAIL(ICNV_ERR_ARG, "snn: nn_idx entry outside [0, n_p)");
+    if ((rc = launch_snn_lists(a, s))) return rc;
+    ICNV_HIP(hipMemcpyAsync(&bad, h->d_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ICNV_HIP(hipStreamSynchronize(s));
+    if (bad) ICNV_FAIL(ICNV_ERR_ARG, "snn: an nn_idx row repeats an entry");   // N(i) is a set: no row is counted
     if ((rc = launch_snn_rows(a, false, s)) || (rc = launch_snn_scan(a, tn, s))) return rc;
     ICNV_HIP(hipMemcpyAsync(&h->nnz, a.row_off + tn, 8, hipMemcpyDeviceToHost, s));
     ICNV_HIP(hipStreamSynchronize(s));

@@ -48,8 +48,11 @@ struct SnnArgs {                  // the SNN graph of a batch of (n, k) kNN bloc
     int32_t *shared;
     int64_t *weight;
     int32_t *loop;                // per node
-    uint32_t *bad;
+    uint32_t *bad;                // SNN_BAD_* bits
 };
+
+constexpr uint32_t SNN_BAD_RANGE = 1u;    // an nn_idx entry outside [0, n_p)
+constexpr uint32_t SNN_BAD_REPEAT = 2u;   // an nn_idx row that repeats an entry
 
 struct LgCheck {                  // device check of a caller's CSR (icnv_leiden_graph_dev)
     const int64_t *node_off, *row_off;
@@ -69,6 +72,7 @@ int launch_lpca_gram(const LpArgs &a, int32_t max_genes, hipStream_t s);
 int launch_lpca_project(const LpArgs &a, int32_t max_n, hipStream_t s);
 int snn_blocks(int64_t total_n);
 int launch_snn_transpose(const SnnArgs &a, hipStream_t s);
+int launch_snn_lists(const SnnArgs &a, hipStream_t s);
 int launch_snn_rows(const SnnArgs &a, bool fill, hipStream_t s);
 int launch_snn_scan(const SnnArgs &a, int64_t total_n, hipStream_t s);
 int launch_lg_check(const LgCheck &c, hipStream_t s);

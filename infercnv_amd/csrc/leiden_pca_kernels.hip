@@ -6,7 +6,7 @@
 //   lpca_scale_kernel     32 x 32 tiles through LDS: z = min(10, (x - mean) / sd), written feature-major
 //   lpca_gram_kernel      M = Z Z^T on the matrix cores (gram::tile_product): upper triangle of 64 x 64 tiles, mirrored
 //   lpca_project_kernel   one lane per (cell, component): E = Z^T V, a sequential fp64 sum over the features
-//   snn_t*_kernel         the transposed kNN lists: count, scan, fill, sort per row
+//   snn_t*_kernel         the transposed kNN lists: count (entries in range), scan, fill, sort per row (no row repeats an entry)
 //   snn_rows_kernel       one wavefront per row: s_ij = |N(i) n N(j)| over the transposed lists of N(i); a count pass, then
 //                         a fill pass into the exactly sized CSR (ascending columns, integer s, 24-bit fixed-point weight)
 //   lg_check_kernel       a caller's CSR for icnv_leiden_graph_dev: ranges, order, weights; strengths
@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(LP_NT) snn_tcount_kernel(SnnArgs a) {
         if (j < 0 || j >= n) bad = 1;
         else atomicAdd(&a.t_cnt[n0 + j], 1);
     }
-    if (bad) atomicOr(a.bad, 1u);
+    if (bad) atomicOr(a.bad, SNN_BAD_RANGE);
 }
 
 __global__ void __launch_bounds__(LP_WAVE) snn_tscan_kernel(SnnArgs a) {
@@ -175,11 +175,14 @@ __global__ void __launch_bounds__(LP_NT) snn_tfill_kernel(SnnArgs a) {
     }
 }
 
-__global__ void __launch_bounds__(LP_NT) snn_tsort_kernel(SnnArgs a) {   // the order of the atomics is gone: sort each row
+// The order of the atomics is gone: sort each row.  An nn_idx row that repeats an entry m is then two equal neighbours in
+// m's sorted list: bad |= SNN_BAD_REPEAT (the rows kernel relies on lists of distinct rows).
+__global__ void __launch_bounds__(LP_NT) snn_tsort_kernel(SnnArgs a) {
     const int p = blockIdx.y;
     const int64_t n0 = a.node_off[p], n = a.node_off[p + 1] - n0;
     const int64_t *toff = a.t_off + n0 + p;
     int32_t *list = a.t_list + n0 * a.k;
+    uint32_t bad = 0;
     for (int64_t i = (int64_t)blockIdx.x * LP_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * LP_NT) {
         int32_t *r = list + toff[i];
         const int64_t m = toff[i + 1] - toff[i];
@@ -192,7 +195,10 @@ __global__ void __launch_bounds__(LP_NT) snn_tsort_kernel(SnnArgs a) {   // the 
                 while (v >= h && r[v - h] > x) { r[v] = r[v - h]; v -= h; }
                 r[v] = x;
             }
+        for (int64_t u = 1; u < m; ++u)
+            if (r[u] == r[u - 1]) bad = SNN_BAD_REPEAT;
     }
+    if (bad) atomicOr(a.bad, bad);
 }
 
 __device__ __forceinline__ int32_t lp_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -343,17 +349,20 @@ int launch_snn_transpose(const SnnArgs &a, hipStream_t s) {
     return ICNV_OK;
 }
 
+// after the range check of launch_snn_transpose: the sorted transposed lists, and the check for a repeated entry
+int launch_snn_lists(const SnnArgs &a, hipStream_t s) {
+    const dim3 g2((unsigned)std::min<int64_t>(std::max<int64_t>((a.max_n * a.k + LP_NT - 1) / LP_NT, 1), 1024), (unsigned)a.n_prob);
+    hipLaunchKernelGGL(snn_tscan_kernel, dim3((unsigned)a.n_prob), dim3(LP_WAVE), 0, s, a);
+    hipLaunchKernelGGL(snn_tfill_kernel, g2, dim3(LP_NT), 0, s, a);
+    hipLaunchKernelGGL(snn_tsort_kernel, g2, dim3(LP_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
+    return ICNV_OK;
+}
+
 int launch_snn_rows(const SnnArgs &a, bool fill, hipStream_t s) {
     const dim3 grid((unsigned)snn_blocks(a.max_n), (unsigned)a.n_prob);
-    if (!fill) {
-        const dim3 g2((unsigned)std::min<int64_t>(std::max<int64_t>((a.max_n * a.k + LP_NT - 1) / LP_NT, 1), 1024), (unsigned)a.n_prob);
-        hipLaunchKernelGGL(snn_tscan_kernel, dim3((unsigned)a.n_prob), dim3(LP_WAVE), 0, s, a);
-        hipLaunchKernelGGL(snn_tfill_kernel, g2, dim3(LP_NT), 0, s, a);
-        hipLaunchKernelGGL(snn_tsort_kernel, g2, dim3(LP_NT), 0, s, a);
-        hipLaunchKernelGGL(snn_rows_kernel<false>, grid, dim3(LP_WAVE), 0, s, a);
-    } else {
-        hipLaunchKernelGGL(snn_rows_kernel<true>, grid, dim3(LP_WAVE), 0, s, a);
-    }
+    if (!fill) hipLaunchKernelGGL(snn_rows_kernel<false>, grid, dim3(LP_WAVE), 0, s, a);
+    else hipLaunchKernelGGL(snn_rows_kernel<true>, grid, dim3(LP_WAVE), 0, s, a);
     ICNV_HIP(hipGetLastError());
     return ICNV_OK;
 }

@@ -120,6 +120,8 @@ def snn(nn_idx):
     nn = np.asarray(nn_idx)
     n, k = nn.shape
     sets = [set(int(x) for x in row) for row in nn]
+    if any(len(s) != k for s in sets):
+        raise ValueError("snn: an nn_idx row repeats an entry")   # the library's ICNV_ERR_ARG
     rev = [[] for _ in range(n)]
     for i in range(n):
         for m in sets[i]:

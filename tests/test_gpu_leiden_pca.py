@@ -51,15 +51,42 @@ def build_batch():
     return X, genes, cells, [8, 20, 5]
 
 
-@pytest.fixture(scope="module")
-def batch(dev):
+def build_edge_batch():
+    """One batch on tile and block edges, nothing planted: n = 256 over 64 genes (k = 8), n = 257 over 65 genes (k = 8),
+    n = 33 over 129 genes (k = 5) -- a Gram tile exactly and one row more, a projection block exactly and one cell more,
+    an odd n shorter than two LDS stages under three tile rows."""
+    X = matrix(200, 700, 21)
+    cells = [np.arange(0, 256), np.arange(256, 513), np.arange(513, 546)]
+    genes = [np.arange(0, 64), np.arange(64, 129), np.arange(71, 200)]
+    return X, genes, cells, [8, 8, 5]
+
+
+BUILDERS = {"planted": build_batch, "edge": build_edge_batch}
+BATCHES = {}
+
+
+def get_batch(name):
     """The GPU's stages and the restatement's, computed once and left unchanged."""
-    from infercnv_amd import tumor_subclusters as ts
-    X, genes, cells, ks = build_batch()
-    x = torch.from_numpy(np.ascontiguousarray(X.T)).cuda()
-    gpu = [ts.pca_stages(x, [genes[p]], [cells[p]], ks[p]) for p in range(3)]
-    ref = [pr.stages(X, genes[p], cells[p], ks[p]) for p in range(3)]
-    return dict(X=X, x=x, genes=genes, cells=cells, ks=ks, gpu=gpu, ref=ref)
+    if name not in BATCHES:
+        from infercnv_amd import tumor_subclusters as ts
+        X, genes, cells, ks = BUILDERS[name]()
+        x = torch.from_numpy(np.ascontiguousarray(X.T)).cuda()
+        gpu = [ts.pca_stages(x, [genes[p]], [cells[p]], ks[p]) for p in range(3)]
+        ref = [pr.stages(X, genes[p], cells[p], ks[p]) for p in range(3)]
+        BATCHES[name] = dict(name=name, X=X, x=x, genes=genes, cells=cells, ks=ks, gpu=gpu, ref=ref)
+    return BATCHES[name]
+
+
+@pytest.fixture(scope="module", params=["planted", "edge"])
+def batch(dev, request):
+    """Either batch: the shape-generic assertions run on both, the planted values are asserted on theirs."""
+    return get_batch(request.param)
+
+
+@pytest.fixture(scope="module")
+def planted(dev):
+    """The batch of build_batch: the weighted Leiden and the CSR refusals are tied to it."""
+    return get_batch("planted")
 
 
 def test_vstd_and_features_identical(batch):
@@ -70,6 +97,9 @@ def test_vstd_and_features_identical(batch):
         assert np.array_equal(g["sd_e"][0], r["sd_e"])
         assert np.array_equal(g["v_std"][0], r["v_std"])
         assert np.array_equal(g["features"][0], r["features"])
+    if batch["name"] != "planted":
+        assert [r["features"].size for r in batch["ref"]] == [64, 65, 129]
+        return
     r = batch["ref"][0]                         # n = 70: the clip binds on the planted gene, the constant gene is 0
     j = 110 - 100
     d = (batch["X"][110, 73] - r["mean"][j]) / r["sd_e"][j]
@@ -90,6 +120,8 @@ def test_scaled_matrix_identical(batch):
         Z, pad = z_blocks(batch["gpu"][p])
         assert np.array_equal(Z, batch["ref"][p]["Z"])
         assert not pad.any()
+    if batch["name"] != "planted":
+        return
     Z = batch["ref"][1]["Z"]
     f = int(np.flatnonzero(batch["ref"][1]["features"] == 50)[0])
     assert Z[f, 17] == 10.0 and Z.max() == 10.0             # the spike gene is clipped
@@ -148,7 +180,10 @@ def test_one_batch_of_three_problems_equals_the_single_calls(batch):
     """The three problems as ONE batch (one k for all, as a route has): every stage's block equals the single call's."""
     from infercnv_amd import tumor_subclusters as ts
     st = ts.pca_stages(batch["x"], batch["genes"], batch["cells"], 5)
-    assert st["active"] == [0, 1, 2] and st["n_cells"] == [70, 200, 21] and st["n_feat"] == [37, 2000, 37]
+    assert st["active"] == [0, 1, 2] and st["n_cells"] == [c.size for c in batch["cells"]]
+    assert st["n_feat"] == [r["features"].size for r in batch["ref"]]
+    if batch["name"] == "planted":
+        assert st["n_cells"] == [70, 200, 21] and st["n_feat"] == [37, 2000, 37]
     z0 = m0 = r0 = 0
     Zb, Mb, Eb, nnb = st["Z"].cpu().numpy(), st["M"].cpu().numpy(), st["E"].cpu().numpy(), st["nn_idx"].cpu().numpy()
     got = csr_of(st)
@@ -185,7 +220,10 @@ def test_snn_graph_identical_given_the_gpus_embedding(batch):
         for got, want in zip(csr_of(st), pr.snn(nn)):
             assert got.dtype == want.dtype and np.array_equal(got, want)
     off = batch["gpu"][1]["row_off"].cpu().numpy()
-    assert np.diff(off)[100] > 64                       # the planted centroid's row is longer than a wavefront and than 2 k
+    if batch["name"] == "planted":
+        assert np.diff(off)[100] > 64                   # the planted centroid's row is longer than a wavefront and than 2 k
+    else:
+        assert np.diff(off).max() > 64                  # so are rows of the edge batch, with nothing planted
 
 
 def hub_block(n, k, seed):
@@ -238,9 +276,9 @@ GRAPH_CASES = [   # (problem, objective, gamma, beta, n_iterations)
 
 
 @pytest.mark.parametrize("case", GRAPH_CASES, ids=lambda c: "-".join(map(str, c)))
-def test_weighted_leiden_identical_to_restatement(dev, batch, case):
+def test_weighted_leiden_identical_to_restatement(dev, planted, case):
     p, obj, g, beta, iters = case
-    st = batch["gpu"][p]
+    st = planted["gpu"][p]
     n = st["n_cells"][0]
     gam = (11.98 / n) ** (1 / 1.165) if g == "auto" else float(g)
     gam = gam * pr.ONE if obj == "CPM" else gam
@@ -253,8 +291,8 @@ def test_weighted_leiden_identical_to_restatement(dev, batch, case):
         assert stats["levels"] > 2 * iters              # some iteration of this graph takes at least two levels
 
 
-def test_weighted_leiden_batch_equals_single_calls(dev, batch):
-    sts = batch["gpu"]
+def test_weighted_leiden_batch_equals_single_calls(dev, planted):
+    sts = planted["gpu"]
     sizes = [st["n_cells"][0] for st in sts]
     offs = [st["row_off"] for st in sts]
     base = np.concatenate([[0], np.cumsum([int(o[-1].item()) for o in offs])])
@@ -272,9 +310,9 @@ def test_weighted_leiden_batch_equals_single_calls(dev, batch):
             r0 += sizes[p]
 
 
-def test_leiden_graph_refuses_a_bad_csr(dev, batch):
+def test_leiden_graph_refuses_a_bad_csr(dev, planted):
     from infercnv_amd import IcnvError, _lib
-    st = batch["gpu"][2]
+    st = planted["gpu"][2]
     n = st["n_cells"][0]
     for name, change in (("col", lambda t: t.index_fill(0, torch.tensor([0]).cuda(), n)),
                          ("weight", lambda t: t.index_fill(0, torch.tensor([1]).cuda(), 0)),

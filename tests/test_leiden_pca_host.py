@@ -143,6 +143,141 @@ def test_weighted_restatement_with_unit_weights_is_the_knn_restatement():
         assert K == Kg and np.array_equal(got, want)
 
 
+# ---------------------------------------------------------------------------------------------------- edge-shape inputs
+# The inputs of tests/test_gpu_leiden_pca_edges.py and what makes them edge cases, shown here on the restatement alone.
+RULER9 = (0, 1, 5, 12, 25, 27, 35, 41, 44)      # Golomb rulers: every difference of two marks occurs once
+RULER8 = (0, 1, 4, 9, 15, 22, 32, 34)
+
+
+def shift_block(n, shifts):
+    """The kNN block nn[i] = (i + d) mod n for d in shifts."""
+    return ((np.arange(n)[:, None] + np.asarray(shifts)[None, :]) % n).astype(np.int32)
+
+
+def shared_counts(nn):
+    """|N(i) n N(j)| of every pair as a dense matrix, the diagonal zeroed."""
+    n, k = nn.shape
+    A = np.zeros((n, n), dtype=np.int64)
+    A[np.repeat(np.arange(n), k), nn.ravel()] = 1
+    assert np.all(A.sum(axis=1) == k)           # no row repeats an entry
+    S = A @ A.T
+    np.fill_diagonal(S, 0)
+    return S
+
+
+def gram_int_input(F, n, seed):
+    """(K, Z): K int64 (F, n) with entries in -16 .. 16, a random sign and magnitude each; Z = K / 8 in [-2, 2]."""
+    K = np.random.default_rng([seed, F, n]).integers(-16, 17, size=(F, n))
+    return K, K / 8.0
+
+
+GRAM_F = (1, 16, 63, 64, 65, 128, 129)
+GRAM_N = (2, 7, 30, 32, 33, 64, 4097)           # ldz = 2, 8, 30, 32, 34, 64, 4098
+
+
+def vstd_clip_case():
+    """(X (5 genes, 4 cells), mean, sd) at n = 4, sqrt(n) = 2: gene 0 has a cell at d = 2 exactly, gene 1 one ulp above it,
+    gene 2 a cell at d = -1000, gene 3 is outside the fit (sd = 0), gene 4 has a cell at d = 30."""
+    rng = np.random.default_rng(41)
+    mean, sd = np.full(5, 1.0), np.full(5, 0.5)
+    X = 1.0 + 0.5 * rng.uniform(-1.0, 1.0, size=(5, 4))
+    X[0, 1] = 2.0
+    mean[1] = 0.0
+    X[1] -= 1.0
+    X[1, 2] = 1.0 + 2.0 ** -52
+    X[2, 0] = 1.0 - 500.0
+    sd[3] = 0.0
+    X[4, 3] = 16.0
+    return X, mean, sd
+
+
+def plant_scale_clips(X, mean, var, genes, cells):
+    """In the block X[genes, cells] (>= 2 cells): gene 0 gets z = 10 exactly and z one ulp above 10, gene 1 (if listed)
+    z = 198 and z = -2002, gene 2 (if listed) a zero variance.  mean and var are per listed gene."""
+    g, c = np.asarray(genes), np.asarray(cells)
+    mean[0], var[0] = 1.0, 0.25
+    X[g[0], c[0]], X[g[0], c[1]] = 6.0, 6.0 + 2.0 ** -50
+    if g.size > 1:
+        mean[1], var[1] = 1.0, 0.25
+        X[g[1], c[0]], X[g[1], c[1]] = 100.0, -1000.0
+    if g.size > 2:
+        var[2] = 0.0
+
+
+def test_ruler_blocks_share_at_most_one_neighbour():
+    for n in (100, 89):
+        nn = shift_block(n, RULER9)
+        S = shared_counts(nn)
+        assert S.max() == 1 and 16 * 1 < 2 * 9                     # two rows share at most one node: every entry is pruned
+        off, col, shared, weight, loop = pr.snn(nn)
+        assert col.size == 0 and not off.any() and off.size == n + 1 and np.array_equal(loop, np.ones(n))
+    nn = shift_block(100, RULER8)
+    S = shared_counts(nn)
+    off, col, shared, weight, loop = pr.snn(nn)
+    assert S.max() == 1 and 16 * 1 == 2 * 8                          # the prune rule binds with equality: kept
+    assert np.array_equal(np.diff(off), np.full(100, 56)) and np.all(shared == 1)
+    assert np.all(weight == pr.snn_weight(1, 8))
+
+
+def test_complete_and_k128_blocks():
+    nn = shift_block(5, range(5))                                    # n = k = 5: rows are the rotations of 0 .. 4
+    off, col, shared, weight, loop = pr.snn(nn)
+    assert np.array_equal(np.diff(off), np.full(5, 4)) and np.all(shared == 5) and np.all(weight == 1 << 24)
+    for i in range(5):
+        assert np.array_equal(col[off[i]:off[i + 1]], np.setdiff1d(np.arange(5), [i]))
+    off, col, shared, weight, loop = pr.snn(shift_block(128, range(128)))
+    assert col.size == 16256 and np.all(shared == 128) and np.all(weight == 1 << 24)
+    off, col, shared, weight, loop = pr.snn(shift_block(129, range(128)))
+    assert col.size == 16512 and np.all(shared == 127) and np.all(weight == pr.snn_weight(127, 128))
+
+
+def test_restated_snn_refuses_a_repeated_entry():
+    """N(i) is a set (include/icnv.h): the library refuses a row that repeats an entry, and so does the restatement."""
+    nn = np.array([[0, 1], [1, 1], [2, 1], [3, 2]], dtype=np.int32)
+    with pytest.raises(ValueError, match="repeats an entry"):
+        pr.snn(nn)
+
+
+def test_integer_gram_inputs_are_exact_in_float64():
+    worst = 0
+    for F in GRAM_F:
+        for n in GRAM_N:
+            K, Z = gram_int_input(F, n, 7)
+            assert np.array_equal(Z * 8.0, K) and np.abs(Z).max() <= 2.0
+            P = K @ K.T
+            assert P.dtype == np.int64 and np.array_equal(Z @ Z.T, P / 64.0) and np.array_equal((P / 64.0) * 64.0, P)
+            worst = max(worst, int((np.abs(K) @ np.abs(K).T).max()))   # 64 |any partial sum, in any order|
+            if n >= 7:                                                 # rows differ: a shifted tile gives another product
+                assert len({r.tobytes() for r in K}) == F
+            if F >= 16:                                                # columns differ: so does a shifted stage or segment
+                assert len({c.tobytes() for c in K.T}) == n
+    assert 0 < worst < 2 ** 53                   # so 64 |M| < 2^53 as well: every sum of the products z_a z_b is exact
+
+
+def test_planted_clips_bind_and_are_met_with_equality():
+    X, mean, sd = vstd_clip_case()
+    n = X.shape[1]
+    vmax = np.sqrt(float(n))
+    d = (X[sd != 0] - mean[sd != 0, None]) / sd[sd != 0, None]
+    assert n == 4 and vmax == 2.0
+    assert d[0, 1] == vmax                                          # met with equality
+    assert d[1, 2] == np.nextafter(2.0, 3.0) > vmax and d[3, 3] == 30.0 > vmax    # it binds (sd[3] = 0: row 3 of d is gene 4)
+    assert d[2, 0] == -1000.0                                       # a large negative d is not clipped
+    v = pr.v_std(X, mean, sd)
+    X2 = X.copy()
+    X2[1, 2], X2[4, 3] = 1.0, 2.0                                   # d = 2 in place of the planted values
+    assert np.array_equal(v, pr.v_std(X2, mean, sd)) and v[3] == 0.0 and v[2] > 1000.0 ** 2 / 3 and v[4] < 30.0 ** 2 / 3
+    rng = np.random.default_rng(43)
+    X = rng.normal(size=(3, 2))
+    mean, var = rng.normal(size=3), rng.uniform(0.5, 2.0, size=3)
+    plant_scale_clips(X, mean, var, np.arange(3), np.arange(2))
+    assert np.sqrt(0.25) == 0.5
+    raw = (X[:2] - mean[:2, None]) / np.sqrt(var[:2, None])
+    assert raw[0, 0] == 10.0 and raw[0, 1] == np.nextafter(10.0, 11.0) and raw[1, 0] == 198.0 and raw[1, 1] == -2002.0
+    Z = pr.scale(X, mean, var)
+    assert Z[0, 0] == 10.0 and Z[0, 1] == 10.0 and Z[1, 0] == 10.0 and Z[1, 1] == -2002.0 and not Z[2].any()
+
+
 # ---------------------------------------------------------------------------------------------------- C ABI without a GPU
 NAMES = ("icnv_lpca_vstd_dev", "icnv_lpca_scale_dev", "icnv_lpca_gram_dev", "icnv_lpca_project_dev", "icnv_snn_begin_dev",
          "icnv_snn_fill_dev", "icnv_snn_end", "icnv_leiden_graph_dev")
