@@ -1707,6 +1707,68 @@ int icnv_median_filter_na_dev(const double *expr_in, double *expr_out, int64_t G
 int icnv_zscore_gene_filter_dev(const double *x, int64_t ld, int64_t G, int64_t C, const int32_t *ref_cells, int64_t n_ref, double *mean_sd,
                                 double *row_mean, void *stream);
 
+/* ---- K34: count matrices out of R's serialisation stream (.rds / .rda) ----------------------------------------------------------
+ * What readRDS hands CreateInfercnvObject (R/inferCNV.R:151-162) -- a matrix, a data.frame or a dgCMatrix -- decoded from the
+ * serialised stream where it lies.  `stream` is the stream as a DEVICE uint8 vector of stream_bytes bytes; every payload is
+ * named by its BYTE offset in it.  Neither the offsets nor `stream` itself need any alignment: the kernels load the aligned
+ * 32-bit words that cover an element and shift, and a word that is not wholly inside [stream, stream + stream_bytes) is read as
+ * the single bytes of it that are.  No byte outside the stream is loaded, so the stream may be a view of a larger allocation.
+ * All index arithmetic is 64-bit.  Elements are big-endian (XDR).
+ *
+ * icnv_rds_columns_dev: dense columns.  Output row j (DEVICE doubles, rows ld >= rows apart: the (cells, genes) layout) is the
+ * `rows` elements that start at byte col_off[j], of kind col_kind[j] (col_off, col_kind: DEVICE [n_out]):
+ *   ICNV_RDS_REAL  8-byte elements, bytes reversed and nothing else: integer loads and stores, so a NaN keeps its payload
+ *                  (NA_real_, 0x7FF00000000007A2, is one)
+ *   ICNV_RDS_INT   4-byte elements, the exact int -> double conversion; NA_integer_ (INT_MIN) becomes NA_real_
+ * For a matrix payload col_off[j] = payload + cells[j] * rows * elem_size; for a data.frame the column's own payload.  The
+ * same column may be asked for twice; bytes that no requested column covers are not read; the padding between rows - 1 and ld
+ * is not written.  ICNV_ERR_ARG before any launch (col_off and col_kind are fetched for it): a null pointer, n_out, rows < 1,
+ * ld < rows, stream_bytes < 0, a kind that is neither, a column that does not lie inside the stream.  The call waits for the
+ * stream once, for that fetch, and NOT after its launch: it returns with the kernel queued on hip_stream, and the kernel reads
+ * col_off and col_kind -- keep both, the stream and out alive until hip_stream has been synchronised.  Timer: "rds_columns".
+ *
+ * icnv_rds_csc_check_dev / icnv_rds_csc_fill_dev: a dgCMatrix (slots i, p, x at their byte offsets; G rows, C columns, nnz
+ * entries) to the CSC arrays of icnv_counts.  cells: DEVICE list of n_out file columns (0-based, any order) or null with
+ * n_out = C: every column in order.  Output column k is file column cells[k], its entries in stream order.
+ * The check validates the WHOLE of p -- p[0] == 0 (ICNV_RDS_P_FIRST), p[j] <= p[j + 1] (ICNV_RDS_P_DESCENT, at index j + 1),
+ * p[C] == nnz (ICNV_RDS_P_LAST, at index C) -- and every entry e of the SELECTED columns: 0 <= i[e] < G (ICNV_RDS_ROW_RANGE),
+ * i strictly increasing within a column (ICNV_RDS_ROW_ORDER, Matrix's own validity rule: it catches a pair stored twice; equal
+ * rows on both sides of a column boundary are valid), x[e] an integer value in 0 .. 2^31 - 1 (ICNV_RDS_VALUE: a fraction, a
+ * negative value, 2^31, an infinity, a NaN; -0 counts as 0; tested on the bits, no floating-point operation).  Entries of
+ * columns that are not selected are not examined (K26's rule: over a deal where every column has one owner every entry is
+ * still examined once).  status (HOST [3]) receives {code, file column, index}: ICNV_RDS_OK, or the violation with the smallest
+ * index -- p violations (index: into p; column: min(index, C - 1)) before entry violations (index: the entry's in the stream;
+ * column: the file column that holds it); among codes at one index the smallest.  The choice is an integer atomic minimum on a
+ * 64-bit key and does not depend on launch order.  On ICNV_RDS_OK colptr (DEVICE int64 [n_out + 1]) is written by a scan and
+ * *nnz_out (HOST) is colptr[n_out]; on a violation nothing is written but status.  Returns ICNV_OK in both cases.
+ * The fill writes rowidx and vals (DEVICE int32 [out_nnz], out_nnz = the check's *nnz_out) for the same arguments and the
+ * check's colptr.  It must follow a check that found no violation; after anything else what it writes is unspecified, but
+ * every access stays inside the stream and the outputs.
+ * ICNV_ERR_ARG before any launch (cells is fetched for it): a null pointer, G, C < 1 or beyond 2^31 - 1, nnz < 0 or beyond
+ * 2^31 - 1, a payload that does not lie inside the stream, n_out < 1, a cells entry that is no column, out_nnz < 0.
+ * The check and the fill synchronise before they return.  Timers: "rds_csc_check", "rds_csc_fill".
+ * icnv_rds_counts_stats: {calls of columns, columns, elements, calls of check, entries examined, refused checks, calls of fill,
+ * entries written} since the last reset (the first n of them). */
+#define ICNV_RDS_INT 13
+#define ICNV_RDS_REAL 14
+#define ICNV_RDS_OK 0
+#define ICNV_RDS_P_FIRST 1
+#define ICNV_RDS_P_DESCENT 2
+#define ICNV_RDS_P_LAST 3
+#define ICNV_RDS_ROW_RANGE 4
+#define ICNV_RDS_ROW_ORDER 5
+#define ICNV_RDS_VALUE 6
+int icnv_rds_columns_dev(const uint8_t *stream, int64_t stream_bytes, const int64_t *col_off, const int32_t *col_kind, int64_t n_out,
+                         int64_t rows, double *out, int64_t ld, void *hip_stream);
+int icnv_rds_csc_check_dev(const uint8_t *stream, int64_t stream_bytes, int64_t i_off, int64_t p_off, int64_t x_off, int64_t G, int64_t C,
+                           int64_t nnz, const int32_t *cells, int64_t n_out, int64_t *colptr, int64_t *status, int64_t *nnz_out,
+                           void *hip_stream);
+int icnv_rds_csc_fill_dev(const uint8_t *stream, int64_t stream_bytes, int64_t i_off, int64_t p_off, int64_t x_off, int64_t G, int64_t C,
+                          int64_t nnz, const int32_t *cells, int64_t n_out, const int64_t *colptr, int32_t *rowidx, int32_t *vals,
+                          int64_t out_nnz, void *hip_stream);
+int icnv_rds_counts_stats(int64_t *out, int32_t n);
+void icnv_rds_counts_stats_reset(void);
+
 /* ---- profiling hooks (used by bench.py) --------------------------------- */
 /* When enabled, every kernel launch is bracketed by hipEvents recorded on the
  * launch stream; icnv_timing_get() synchronises those events and returns the

@@ -39,6 +39,8 @@ CSC_SORTED, CSC_DUPLICATE, CSC_DESCENT = 0, 1, 2   # ICNV_CSC_* results of icnv_
 XDR_COLS, XDR_ROWS = 0, 1                 # ICNV_XDR_* layouts of icnv_xdr_encode_dev / icnv_xdr_decode_dev
 INFLATE_OK_MARKER, INFLATE_OK_FINAL, INFLATE_TRUNCATED, INFLATE_TOO_LONG, INFLATE_BAD_STREAM, INFLATE_NEEDS_HISTORY = range(6)   # ICNV_INFLATE_*
 GUNZIP_OK_BOUNDARY, GUNZIP_OK_FINAL, GUNZIP_TRUNCATED, GUNZIP_TOO_LONG, GUNZIP_BAD_STREAM = range(5)   # ICNV_GUNZIP_*
+RDS_INT, RDS_REAL = 13, 14                # ICNV_RDS_* kinds of icnv_rds_columns_dev (the SEXP types)
+RDS_OK, RDS_P_FIRST, RDS_P_DESCENT, RDS_P_LAST, RDS_ROW_RANGE, RDS_ROW_ORDER, RDS_VALUE = range(7)   # ICNV_RDS_* of icnv_rds_csc_check_dev
 HSPIKE_GENES_TOKEN = 0x6873706B67656E65   # ICNV_HSPIKE_GENES_TOKEN: the stream of the hidden spike-in's genes_means_use_idx
 
 
@@ -262,6 +264,11 @@ PROTOTYPES = {
     "icnv_median_filter_na": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _i32, _ip, _ip, _i32, _i32, ct.POINTER(ct.c_int64)]),
     "icnv_median_filter_na_dev": (ct.c_int, [_vp, _vp, _i64, _i64, _ip, _i32, _ip, _ip, _i32, _i32, ct.POINTER(ct.c_int64), _vp]),
     "icnv_zscore_gene_filter_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _ip, _i64, _dp, _vp, _vp]),
+    "icnv_rds_columns_dev": (ct.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "icnv_rds_csc_check_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64p, _i64p, _vp]),
+    "icnv_rds_csc_fill_dev": (ct.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "icnv_rds_counts_stats": (ct.c_int, [ct.POINTER(_i64), _i32]),
+    "icnv_rds_counts_stats_reset": (None, []),
     "icnv_timing_enable": (None, [ct.c_int]),
     "icnv_timing_reset": (None, []),
     "icnv_timing_get": (ct.c_int, [ct.c_char_p, _dp, ct.POINTER(_i64)]),

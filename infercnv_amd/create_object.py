@@ -263,6 +263,22 @@ def _mtx_source(raw_counts_matrix, gene_names, cell_names, gene_column):
     return path, _name_list(gene_names, gene_column, "gene_names"), _name_list(cell_names, 1, "cell_names")
 
 
+RDS_SUFFIXES = (".rds", ".rda", ".rdata")
+
+
+def _rds_source(raw_counts_matrix):
+    """The path when the matrix is an R file -- .rds, or an .rda / .RData container (the suffix in any case) --, else None."""
+    if not isinstance(raw_counts_matrix, (str, os.PathLike)):
+        return None
+    path = os.fspath(raw_counts_matrix)
+    return path if path.lower().endswith(RDS_SUFFIXES) and not os.path.isdir(path) else None
+
+
+def _rds_names(gene_names, cell_names, gene_column):
+    return {"gene_names": None if gene_names is None else _name_list(gene_names, gene_column, "gene_names"),
+            "cell_names": None if cell_names is None else _name_list(cell_names, 1, "cell_names")}
+
+
 def CreateInfercnvObject(raw_counts_matrix, gene_order_file, annotations_file, ref_group_names, delim="\t", max_cells_per_group=None,
                          min_max_counts_per_cell=(100, float("inf")), chr_exclude=CHR_EXCLUDE, seed=0, gene_names=None,
                          cell_names=None, return_device=False, chunk_bytes=None, sparse=None, gene_column=2):
@@ -270,9 +286,17 @@ def CreateInfercnvObject(raw_counts_matrix, gene_order_file, annotations_file, r
     max_cells_per_group; see the module's notes on the deviations), `gene_names` / `cell_names` (for a matrix given as a NumPy
     array, a scipy sparse matrix or a .mtx file, genes x cells), `return_device`, `sparse` and `gene_column`.
 
-    raw_counts_matrix: a path (text, or .gz; .rds raises NotImplementedError), an array or a sparse matrix.  gene_order_file,
+    raw_counts_matrix: a path (text, or .gz; .rds / .rda / .RData: below), an array or a sparse matrix.  gene_order_file,
     annotations_file: paths, or small tables given as rows.  The matrix file is parsed on the device; a byte outside the
     grammar of include/icnv.h raises IcnvError with its line and field.
+
+    R files (DESIGN K34; R/inferCNV.R:151-162 reads them with readRDS).  A path that ends in .rds -- or .rda / .RData, a
+    container with exactly one variable -- is decoded on the device from the serialised stream (device.read_rds_counts): a
+    numeric or integer matrix and a data.frame of numeric / integer columns take the dense route; a dgCMatrix takes the sparse
+    route of K22 (sparse=None or True), or is expanded on the device and continues on the dense route (sparse=False); sparse=True
+    with a dense kind is the ValueError below.  A dgCMatrix is validated on the device (ValueError with the rule, the column and
+    the entry), and one that holds non-integers is refused with the sparse route's message.  gene_names / cell_names supply the
+    names a file lacks (compact row.names, no dimnames).  What a file may hold and what each refusal names: rds.locate_counts.
 
     Sparse input (DESIGN K22).  raw_counts_matrix may also be a MatrixMarket coordinate file (.mtx, .mtx.gz; gene_names and
     cell_names are then lists, or paths of .tsv[.gz] files whose `gene_column`-th, for cells first, column holds the names), or a
@@ -296,8 +320,17 @@ def CreateInfercnvObject(raw_counts_matrix, gene_order_file, annotations_file, r
     positions = read_gene_order(gene_order_file, chr_exclude)
     annotations = read_annotations(annotations_file, delim)
     counts = x = None
-    mtx = _mtx_source(raw_counts_matrix, gene_names, cell_names, gene_column)
-    if mtx is not None:
+    rds_path = _rds_source(raw_counts_matrix)
+    mtx = None if rds_path is not None else _mtx_source(raw_counts_matrix, gene_names, cell_names, gene_column)
+    if rds_path is not None:
+        genes, cells, got, _ = device.read_rds_counts(rds_path, chunk_bytes=chunk_bytes, **_rds_names(gene_names, cell_names, gene_column))
+        if isinstance(got, device.DeviceCounts):
+            counts, x = (None, got.to_dense()) if sparse is False else (got, None)
+        elif sparse:
+            raise ValueError("sparse=True wants a .mtx file, a 10x directory or a scipy sparse matrix")
+        else:
+            x = got
+    elif mtx is not None:
         genes, cells = mtx[1], mtx[2]
         counts, _ = device.read_mtx(mtx[0], chunk_bytes=chunk_bytes)
         if (counts.G, counts.C) != (len(genes), len(cells)):

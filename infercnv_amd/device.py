@@ -781,7 +781,8 @@ def read_table(path, sep="\t", chunk_bytes=None, cells=None):
     pieces; the row names are gathered on the device and fetched; a chunk comes to the host only when it holds a field the
     device pass cannot certify, or is refused).  stats["source"] is then "device_gunzip"; any other file -- stats["source"]
     "host", stats["source_reason"] why -- is decompressed by Python's gzip into the pinned chunks.  Both routes return the same
-    values and the same refusals.  .rds is not read (NotImplementedError).  A refused byte raises IcnvError
+    values and the same refusals.  .rds is not read here (NotImplementedError): read_rds_counts reads it (DESIGN K34), and
+    CreateInfercnvObject branches to it before this function.  A refused byte raises IcnvError
     with the file line and the field.
 
     cells (DESIGN K26): a list of 0-based numeric file columns, in any order, without repeats (ValueError before the file is
@@ -2013,6 +2014,9 @@ def cells_mean_sd(x, cell_idx):
 
 
 # ------------------------------------------------------------------ ingest from integer counts (steps 2-4)
+ERR_SPARSE_VALUES = "the sparse route wants integer counts in 0 .. 2^31 - 1; pass sparse=False for other data"   # K22's, and K34's
+
+
 class DeviceCounts:
     """The raw count matrix on the device: dense int32 (C, G) tensor -- row-major (C, G) is R's column-major G x C -- or
     CSC (colptr int64 [C + 1], rowidx int32 [nnz], vals int32 [nnz]) tensors."""
@@ -2047,7 +2051,7 @@ class DeviceCounts:
         m.sort_indices()
         vals = np.ascontiguousarray(m.data)
         if not np.array_equal(vals, np.rint(vals)) or (vals.size and (vals.min() < 0 or vals.max() > 0x7fffffff)):
-            raise ValueError("the sparse route wants integer counts in 0 .. 2^31 - 1; pass sparse=False for other data")
+            raise ValueError(ERR_SPARSE_VALUES)
         G, C = m.shape
         if G < 1 or C < 1:
             raise ValueError("the matrix must have at least one gene and one cell")
@@ -2519,6 +2523,251 @@ def csc_select(counts, genes, cells):
         check(L.icnv_csc_select_dev(ct.byref(counts.c), counts.G, counts.C, _ptr(gm), int(genes.size), _ptr(cl), int(cells.size),
                                     _ptr(colptr), _ptr(rowidx), _ptr(vals), nnz.value, ct.byref(nnz), _stream()))
     return DeviceCounts(int(genes.size), int(cells.size), colptr=colptr, rowidx=rowidx, vals=vals)
+
+
+# ------------------------------------------------------------------ count matrices out of R's serialisation (DESIGN K34)
+RDS_COUNTS_STATS = ("columns_calls", "columns", "elements", "check_calls", "entries_checked", "checks_refused", "fill_calls",
+                    "entries_written")
+RDS_KINDS = {"real": _lib.RDS_REAL, "int": _lib.RDS_INT}               # ICNV_RDS_* of include/icnv.h
+READ_RDS_CHUNK = 64 << 20          # bytes of one uploaded chunk of read_rds_counts
+_RDS_CSC_WHAT = {_lib.RDS_P_FIRST: "p does not start with 0", _lib.RDS_P_DESCENT: "p decreases", _lib.RDS_P_LAST: "the last entry of p is not the length of x",
+                 _lib.RDS_ROW_RANGE: "a row index in i is no row of the matrix", _lib.RDS_ROW_ORDER: "the row indices of a column do not strictly increase (an entry stored twice?)"}
+
+
+def rds_counts_stats(reset=False):
+    """The counters of icnv_rds_counts_stats since the last reset, as a dict keyed by RDS_COUNTS_STATS."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(RDS_COUNTS_STATS))()
+    check(L.icnv_rds_counts_stats(out, len(RDS_COUNTS_STATS)))
+    if reset:
+        L.icnv_rds_counts_stats_reset()
+    return dict(zip(RDS_COUNTS_STATS, (int(v) for v in out)))
+
+
+def _dev_list(a, dtype, dev):
+    return a.to(device=dev, dtype=dtype).contiguous() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype={torch.int64: np.int64, torch.int32: np.int32}[dtype])).to(dev)
+
+
+def rds_columns(stream, col_off, col_kind, rows, *, out=None):
+    """icnv_rds_columns_dev: output row j is the `rows` big-endian elements of kind col_kind[j] (RDS_KINDS' values) that start at
+    byte col_off[j] of the CUDA uint8 vector `stream`, as doubles.  stream may be a view at any address; the offsets need no
+    alignment.  out: a CUDA float64 matrix (n_out, >= rows) with contiguous rows -- a view with a larger leading dimension is
+    fine, its padding is not written -- or None for a new (n_out, rows) tensor."""
+    L = _lib.load()
+    _bytes_vector(stream, "stream")
+    dev = stream.device
+    off, kind = _dev_list(col_off, torch.int64, dev), _dev_list(col_kind, torch.int32, dev)
+    n_out = int(off.numel())
+    if kind.numel() != n_out:
+        raise ValueError("col_off and col_kind list the same columns")
+    if out is None:
+        out = torch.empty((n_out, int(rows)), dtype=torch.float64, device=dev)
+    if not (out.is_cuda and out.dtype == torch.float64 and out.dim() == 2 and out.shape[0] == n_out and out.shape[1] >= rows and
+            (out.stride(1) == 1 or out.shape[1] == 1)):
+        raise ValueError("out must be a CUDA float64 matrix (n_out, >= rows) with contiguous rows")
+    ld = int(out.stride(0)) if n_out > 1 else max(int(out.stride(0)), int(rows))
+    check(L.icnv_rds_columns_dev(_ptr(stream), int(stream.numel()), _ptr(off), _ptr(kind), n_out, int(rows), _ptr(out), ld, _stream()))
+    torch.cuda.current_stream().synchronize()                       # (the lists are released when this returns)
+    return out
+
+
+def rds_csc_check(stream, i_off, p_off, x_off, G, C, nnz, cells=None, *, colptr=None):
+    """icnv_rds_csc_check_dev on the CUDA uint8 vector `stream`: ((code, file column, index), colptr, nnz_out).  code is
+    _lib.RDS_OK -- colptr (CUDA int64 [n_out + 1], allocated unless passed) then holds the selected columns' pointer and nnz_out
+    their entries -- or the violation with the smallest index; colptr is then untouched and nnz_out None."""
+    L = _lib.load()
+    _bytes_vector(stream, "stream")
+    dev = stream.device
+    cl = None if cells is None else _dev_list(cells, torch.int32, dev)
+    n_out = int(C) if cl is None else int(cl.numel())
+    if colptr is None:
+        colptr = torch.empty(n_out + 1, dtype=torch.int64, device=dev)
+    if not (_is_vector(colptr, torch.int64) and colptr.numel() == n_out + 1):
+        raise ValueError("colptr must be a CUDA int64 vector of n_out + 1 entries")
+    status, nnz_out = (ct.c_int64 * 3)(), ct.c_int64(0)
+    check(L.icnv_rds_csc_check_dev(_ptr(stream), int(stream.numel()), int(i_off), int(p_off), int(x_off), int(G), int(C), int(nnz),
+                                   None if cl is None else _ptr(cl), n_out, _ptr(colptr), status, ct.byref(nnz_out), _stream()))
+    st = (int(status[0]), int(status[1]), int(status[2]))
+    return st, colptr, (int(nnz_out.value) if st[0] == _lib.RDS_OK else None)
+
+
+def rds_csc_fill(stream, i_off, p_off, x_off, G, C, nnz, colptr, out_nnz, cells=None, *, rowidx=None, vals=None):
+    """icnv_rds_csc_fill_dev after a check that found no violation, with its colptr and nnz_out: (rowidx, vals), CUDA int32."""
+    L = _lib.load()
+    _bytes_vector(stream, "stream")
+    dev = stream.device
+    cl = None if cells is None else _dev_list(cells, torch.int32, dev)
+    n_out = int(C) if cl is None else int(cl.numel())
+    rowidx = torch.empty(int(out_nnz), dtype=torch.int32, device=dev) if rowidx is None else rowidx
+    vals = torch.empty(int(out_nnz), dtype=torch.int32, device=dev) if vals is None else vals
+    for t in (rowidx, vals):
+        if not (_is_vector(t, torch.int32) and t.numel() >= out_nnz):
+            raise ValueError("rowidx and vals must be CUDA int32 vectors of out_nnz entries")
+    check(L.icnv_rds_csc_fill_dev(_ptr(stream), int(stream.numel()), int(i_off), int(p_off), int(x_off), int(G), int(C), int(nnz),
+                                  None if cl is None else _ptr(cl), n_out, _ptr(colptr), _ptr(rowidx) if out_nnz else None,
+                                  _ptr(vals) if out_nnz else None, int(out_nnz), _stream()))
+    return rowidx, vals
+
+
+def _upload_ranges(buf, ranges, pin, dev, stats, at=None, size=None):
+    """The byte ranges [(start, end)] of the host buffer `buf` as one CUDA uint8 vector, through the two pinned buffers `pin`
+    (K21's pattern): a range larger than a buffer goes up in pieces.  The ranges lie back to back, or, with `at` and `size`,
+    range k at byte at[k] of a vector of `size` bytes whose other bytes are left as allocated.  Returns (tensor, offset of
+    every range)."""
+    src = np.frombuffer(buf, dtype=np.uint8)
+    total = sum(e - s for s, e in ranges)
+    if at is None:
+        at, size = (np.cumsum([0] + [e - s for s, e in ranges])[:-1]).tolist(), total
+    out = torch.empty(max(size, 1), dtype=torch.uint8, device=dev)
+    cap, events, k = int(pin[0].numel()), [None, None], 0
+    for (s, e), d in zip(ranges, at):
+        while s < e:
+            slot, n = k % 2, min(cap, e - s)
+            if events[slot] is not None:
+                events[slot].synchronize()                             # the copy out of this pinned buffer has finished
+            pin[slot].numpy()[:n] = src[s:s + n]
+            out[d:d + n].copy_(pin[slot][:n], non_blocking=True)
+            events[slot] = torch.cuda.Event()
+            events[slot].record()
+            s, d, k = s + n, d + n, k + 1
+    torch.cuda.synchronize()
+    del src                                                            # (no view of the buffer outlives the call: a mapping can be closed)
+    stats["uploaded_bytes"] += total
+    stats["chunks"] += k
+    return out[:size], list(at)
+
+
+def _upload_csc(buf, loc, sel, pin, dev, stats):
+    """A host-side dgCMatrix on the device as [i | p | x]: (tensor, i_off, p_off, x_off).  Without a selection the three payloads
+    whole; with one, p whole and only the entry ranges of the selected columns, each at its own place -- the bytes between them
+    are never written and never read, because the kernels look at no entry of a column that is not selected.  Which bytes those
+    are is read off p here, clamped exactly as the kernels clamp it (this plans the upload and decides nothing: p is validated
+    on the device, and every value of the result is decoded there)."""
+    i, p, x = loc.payloads
+    i_off, p_off, x_off = 0, i.nbytes, i.nbytes + p.nbytes
+    size = x_off + x.nbytes
+    if sel is None:
+        return (_upload_ranges(buf, [(q.offset, q.offset + q.nbytes) for q in (i, p, x)], pin, dev, stats)[0], i_off, p_off, x_off)
+    pv = np.clip(np.frombuffer(buf, dtype=">i4", count=loc.C + 1, offset=p.offset).astype(np.int64), 0, loc.nnz)
+    lo, hi = pv[sel], np.maximum(pv[sel + 1], pv[sel])
+    runs = []
+    for k in np.argsort(lo, kind="stable"):                            # the selected columns' entry ranges, adjoining ones merged
+        if hi[k] > lo[k]:
+            if runs and lo[k] <= runs[-1][1]:
+                runs[-1][1] = max(runs[-1][1], int(hi[k]))
+            else:
+                runs.append([int(lo[k]), int(hi[k])])
+    ranges = [(i.offset + 4 * a, i.offset + 4 * b) for a, b in runs] + [(p.offset, p.offset + p.nbytes)] + [(x.offset + 8 * a, x.offset + 8 * b) for a, b in runs]
+    at = [i_off + 4 * a for a, _ in runs] + [p_off] + [x_off + 8 * a for a, _ in runs]
+    return _upload_ranges(buf, ranges, pin, dev, stats, at=at, size=size)[0], i_off, p_off, x_off
+
+
+def read_rds_counts(path, *, cells=None, chunk_bytes=None, gene_names=None, cell_names=None, opened=None):
+    """The count matrix readRDS(path) hands CreateInfercnvObject (R/inferCNV.R:151-162), decoded on the device from the
+    serialised stream (DESIGN K34): a numeric or integer matrix, a data.frame of numeric / integer columns, or a dgCMatrix;
+    .rds, or an .rda / .RData container with exactly one such variable (rds.locate_counts says what is accepted and what each
+    refusal names).  Returns (gene names, ALL cell names, x, stats), the shape of read_table's result:
+        dense kinds   x is the (len(cells) or C, G) CUDA float64 tensor, as from read_table (icnv_rds_columns_dev: REALSXP bytes
+                      reversed and nothing else, so NA_real_ and every NaN payload survive; INTSXP converted exactly, NA_integer_
+                      becoming NA_real_)
+        dgCMatrix     x is the G x (len(cells) or C) CSC DeviceCounts, as from read_mtx (icnv_rds_csc_check_dev, then
+                      icnv_rds_csc_fill_dev).  The file is untrusted: p, and every entry of the selected columns, is validated
+                      on the device, and a violation raises ValueError with the rule, the column and the entry (1-based); a
+                      value that is no integer in 0 .. 2^31 - 1 raises K22's message (ERR_SPARSE_VALUES).
+    The slot order of a dgCMatrix is the Matrix package's documented one, as rds.py writes it; no R-written dgCMatrix was
+    available where this was built, so that layout is believed, not verified.
+
+    Opening: an uncompressed file is mapped; a gzip file is offered to rds._open_on_device (K29, then K30) and the payloads are
+    then consumed device to device from the inflated tensor, at their byte offsets, without a staging copy; gzip turned away
+    there, and bzip2 / xz, are inflated by Python.  A host-side stream goes up through two pinned buffers in pieces of at most
+    chunk_bytes (READ_RDS_CHUNK): for the dense kinds chunks of whole requested columns, each converted as it arrives; for a
+    dgCMatrix p and the ranges of i and x that hold the requested columns' entries (they go, each at its place, into one device
+    buffer of 12 bytes per entry of the file, which the check and the fill read: the transfer is chunked and selective, the
+    buffer is whole).  Only requested columns are uploaded.  The decode is always on the device; there is no NumPy route.
+    The mapping of an uncompressed file is closed before this returns (not one passed in through `opened`).
+
+    cells: 0-based file columns, any order, no repeats (as read_table / read_mtx).  Entries of dgCMatrix columns that are not
+    selected are not examined (K26's rule); p is always validated whole.  opened: what rds.open_counts(path) returned, for a
+    caller that has opened the file already (ShardedCreate reads the column count first).
+
+    stats: kind, inflate ("none", "device_k29", "device_k30" or "host", with inflate_reason), stream_bytes, payload_bytes,
+    uploaded_bytes (host to device), chunks, the counters of rds_counts_stats for this call, open_s / locate_s / decode_s /
+    wall_s."""
+    import time
+    from . import rds
+    path = os.fspath(path)
+    sel = None if cells is None else _selected_columns(cells, "read_rds_counts")
+    cap = max(64, int(chunk_bytes if chunk_bytes is not None else READ_RDS_CHUNK))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    before = rds_counts_stats()
+    t0 = time.perf_counter()
+    buf, route, reason = rds.open_counts(path) if opened is None else opened
+    t1 = time.perf_counter()
+    loc = rds.locate_counts(buf, gene_names=gene_names, cell_names=cell_names)
+    t2 = time.perf_counter()
+    stats = {"kind": loc.kind, "inflate": route, "inflate_reason": reason, "stream_bytes": len(buf), "uploaded_bytes": 0, "chunks": 0,
+             "payload_bytes": int(sum(p.nbytes for p in loc.payloads))}
+    if sel is not None and int(sel.max()) >= loc.C:
+        bad = int(sel[sel >= loc.C][0])
+        raise ValueError(f"read_rds_counts: cells entry {bad} is not a column of the file, which has {loc.C}")
+    stream = buf.tensor if isinstance(buf, rds._DeviceStream) else None
+    pin = None if stream is not None else [_pinned(max(64, min(cap, stats["payload_bytes"]))) for _ in range(2)]
+    G = loc.G
+    if loc.kind == "dgCMatrix":
+        i, p, x = loc.payloads
+        if stream is None:
+            stream, i_off, p_off, x_off = _upload_csc(buf, loc, sel, pin, dev, stats)
+        else:
+            i_off, p_off, x_off = i.offset, p.offset, x.offset
+        (code, column, index), colptr, out_nnz = rds_csc_check(stream, i_off, p_off, x_off, G, loc.C, loc.nnz, sel)
+        if code == _lib.RDS_VALUE:
+            raise ValueError(f"{ERR_SPARSE_VALUES} (entry {index + 1} of x, column {column + 1})")
+        if code != _lib.RDS_OK:
+            raise ValueError(f"read_rds_counts: the dgCMatrix is not valid: {_RDS_CSC_WHAT[code]} (column {column + 1}, " +
+                             (f"entry {index + 1} of p)" if code <= _lib.RDS_P_LAST else f"entry {index + 1} of i)"))
+        rowidx, vals = rds_csc_fill(stream, i_off, p_off, x_off, G, loc.C, loc.nnz, colptr, out_nnz, sel)
+        result = DeviceCounts(G, loc.C if sel is None else int(sel.size), colptr=colptr, rowidx=rowidx, vals=vals)
+    else:
+        want = np.arange(loc.C, dtype=np.int64) if sel is None else sel
+        if loc.kind == "data_frame":
+            off = np.array([loc.payloads[j].offset for j in want], dtype=np.int64)
+            es = np.array([loc.payloads[j].elem_size for j in want], dtype=np.int64)
+        else:
+            es = np.full(want.size, loc.payloads[0].elem_size, dtype=np.int64)
+            off = loc.payloads[0].offset + want * G * es
+        kind = np.where(es == 8, _lib.RDS_REAL, _lib.RDS_INT).astype(np.int32)
+        result = torch.empty((want.size, G), dtype=torch.float64, device=dev)
+        if stream is not None:
+            rds_columns(stream, off, kind, G, out=result)
+        else:                                                          # chunks of whole requested columns, merged where they adjoin
+            k0 = 0
+            while k0 < want.size:
+                k1, size = k0 + 1, int(G * es[k0])
+                while k1 < want.size and size + int(G * es[k1]) <= cap:
+                    size, k1 = size + int(G * es[k1]), k1 + 1
+                ranges = []
+                for k in range(k0, k1):
+                    a, b = int(off[k]), int(off[k] + G * es[k])
+                    if ranges and ranges[-1][1] == a:
+                        ranges[-1][1] = b
+                    else:
+                        ranges.append([a, b])
+                chunk, starts = _upload_ranges(buf, ranges, pin, dev, stats)
+                rel, r = np.empty(k1 - k0, dtype=np.int64), 0           # every column's offset in the chunk
+                for n, k in enumerate(range(k0, k1)):
+                    while not ranges[r][0] <= off[k] < ranges[r][1]:
+                        r += 1
+                    rel[n] = starts[r] + int(off[k]) - ranges[r][0]
+                rds_columns(chunk, rel, kind[k0:k1], G, out=result[k0:k1])
+                k0 = k1
+    torch.cuda.synchronize()
+    if opened is None:
+        rds.close_counts(buf)
+    t3 = time.perf_counter()
+    after = rds_counts_stats()
+    stats.update({k: after[k] - before[k] for k in RDS_COUNTS_STATS})
+    stats.update(open_s=t1 - t0, locate_s=t2 - t1, decode_s=t3 - t2, wall_s=t3 - t0)
+    return loc.genes, loc.cells, result, stats
 
 
 def cells_moments_partial(x, cell_idx, phase, mean=0.0):

@@ -2,7 +2,8 @@
 
 R's `add_to_seurat`, `plot_cnv`, `apply_median_filtering` and `plot_per_group` start from an `infercnv` S4 object read with
 readRDS.  This module writes such a file from an InfercnvObject (save_infercnv_obj), reads one written by either side
-(load_infercnv_obj), and holds the general writer and parser they stand on (write_rds, read_rds).  The byte swap and the
+(load_infercnv_obj), and holds the general writer and parser they stand on (write_rds, read_rds), and the walk that finds a
+count matrix's payloads in a file for device.read_rds_counts (locate_counts, DESIGN K34).  The byte swap and the
 transpose of the matrices run on the device (icnv_xdr_encode_dev / icnv_xdr_decode_dev, include/icnv.h); everything else
 -- the format below -- is written and parsed here.  No R exists where this was built: readRDS has never opened one of
 these files.  What was checked instead is in tests/test_rds_host.py: literal bytes derived by hand from the format, the
@@ -663,14 +664,23 @@ class _Reader:
             v = v.cpu().numpy()                   # only a matrix stays on the device (its attributes follow its payload)
         return _with_attrs(v, attrs)
 
+    def altrep_parts(self, cls):
+        """The state and the attributes of an ALTREP object of class `cls`, whose info was just read."""
+        return self.item(), self.item()
+
+    def compact_seq(self, cls, seq):
+        """What stands for the expanded sequence of a compact_intseq / compact_realseq."""
+        return seq
+
     def altrep(self, at):
-        info, state, attr = self.item(), self.item(), self.item()
+        info = self.item()
         cls = info.values[0].name if isinstance(info, _Pairlist) and info.values and isinstance(info.values[0], RSymbol) else None
+        state, attr = self.altrep_parts(cls)
         attrs = attr.as_dict() if isinstance(attr, _Pairlist) else {}
         if cls in ("compact_intseq", "compact_realseq"):
             n, start, step = (float(x) for x in np.asarray(state)[:3])
             seq = start + step * np.arange(int(n), dtype=np.float64)
-            return _with_attrs(seq.astype(np.int32) if cls == "compact_intseq" else seq, attrs)
+            return _with_attrs(self.compact_seq(cls, seq.astype(np.int32) if cls == "compact_intseq" else seq), attrs)
         if cls == "deferred_string":
             arg = state.values[0] if isinstance(state, _Pairlist) else state
             arg = arg.value if isinstance(arg, RValue) else arg
@@ -718,6 +728,8 @@ def _with_attrs(v, attrs):
     attrs = dict(attrs)
     if not attrs:
         return v
+    if isinstance(v, (RdsPayload, RNoPayload)):    # locate_counts: the vector was not decoded, it only carries its attributes
+        return RValue(v, attrs)
     cls = attrs.get("class")
     cls_list = [] if cls is None else [str(c) for c in np.asarray(cls.value if isinstance(cls, RValue) else cls).ravel()]
     if isinstance(v, np.ndarray) and v.dtype.kind in "iu" and "factor" in cls_list and "levels" in attrs:
@@ -1103,6 +1115,283 @@ def read_rds(path, *, return_device=False):
     if isinstance(top, _Pairlist):
         return RValue(top.values, {"names": _str_array([t or "" for t in top.tags])})
     return top
+
+
+# ---------------------------------------------------------------------------------------------- count matrices (K34)
+@dataclass
+class RdsPayload:
+    """A REALSXP / INTSXP vector where it lies in the serialised stream: `length` big-endian elements of `elem_size` bytes from
+    byte `offset` on.  sexp: REALSXP or INTSXP.  value: the decoded array when the vector is below DEVICE_THRESHOLD, else None."""
+    offset: int
+    elem_size: int
+    length: int
+    sexp: int
+    value: object = None
+
+    @property
+    def nbytes(self):
+        return self.length * self.elem_size
+
+
+@dataclass
+class RdsCounts:
+    """What locate_counts found: kind ("matrix_real", "matrix_int", "data_frame", "dgCMatrix"), the G x C shape, the gene and
+    cell names, the payloads (one for a matrix, one per column for a data.frame, i, p and x for a dgCMatrix), nnz (the length
+    of x; None for the dense kinds) and container (None, or "rda" with `variable` the name of the one variable)."""
+    kind: str
+    G: int
+    C: int
+    genes: list
+    cells: list
+    payloads: list
+    nnz: object = None
+    container: object = None
+    variable: object = None
+
+
+@dataclass
+class RNoPayload:
+    """An ALTREP compact_intseq / compact_realseq met where locate_counts looks for payloads: R stores (length, start, step), so
+    the vector has no elements in the stream.  cls: the ALTREP class; value: the expanded sequence."""
+    cls: str
+    value: object
+
+
+class _LocatingReader(_Reader):
+    """_Reader in the mode of locate_counts.  A REALSXP or INTSXP vector that can be a count payload -- the top-level value, an
+    element of a list, a slot of an S4 object, the vector inside an ALTREP wrap_real / wrap_integer -- is recorded as an
+    RdsPayload, and decoded only when it is smaller than DEVICE_THRESHOLD.  Everything else is read as always, into plain
+    arrays: strings, logicals, every attribute of a vector or list (dim, dimnames, names, row.names, class, levels), and the
+    state of the other ALTREP classes (the three numbers of a compact sequence, the argument of a deferred_string).  A compact
+    sequence in a payload's place comes back as RNoPayload."""
+
+    def __init__(self, buf):
+        super().__init__(buf)
+        self.plain = 0                           # > 0 while attributes or ALTREP state are read: numeric() is _Reader's
+
+    def numeric(self, t, n):
+        if t == LGLSXP or self.plain:
+            return super().numeric(t, n)
+        es = 8 if t == REALSXP else 4
+        pos = self.pos
+        if n * es >= DEVICE_THRESHOLD:
+            self.need(n * es)
+            self.pos += n * es
+            return RdsPayload(pos, es, n, t)
+        return RdsPayload(pos, es, n, t, super().numeric(t, n))
+
+    def plainly(self, read):
+        self.plain += 1
+        try:
+            return read()
+        finally:
+            self.plain -= 1
+
+    def finish(self, v, has_attr):
+        return _with_attrs(v, self.plainly(self.attrs) if has_attr else {})
+
+    def altrep_parts(self, cls):
+        if cls in ("wrap_real", "wrap_integer"):  # the wrapped vector is a payload like any other; its attributes are not
+            return self.item(), self.plainly(self.item)
+        return self.plainly(lambda: (self.item(), self.item()))
+
+    def compact_seq(self, cls, seq):
+        return seq if self.plain else RNoPayload(cls, seq)
+
+
+def _small(v, what):
+    """The host array of a short vector that locate_counts needs here (the slot Dim)."""
+    if isinstance(v, RValue):
+        v = v.value
+    if isinstance(v, (RdsPayload, RNoPayload)):
+        if v.value is None:
+            raise ValueError(f"{what}: a vector of {v.length} elements where a short one is expected")
+        v = v.value
+    return None if v is None else np.asarray(v)
+
+
+def _name_vector(v):
+    """The list of names of a character vector, or None for anything else (NULL, compact integer row.names)."""
+    if isinstance(v, RValue):
+        v = v.value
+    if isinstance(v, np.ndarray) and v.dtype.kind in "US":
+        return [str(s) for s in v.tolist()]
+    if isinstance(v, np.ndarray) and v.dtype.kind == "O" and all(isinstance(s, str) for s in v.tolist()):
+        return list(v.tolist())
+    return None
+
+
+def _dim_names(dn, what):
+    """(row names, column names) of a dimnames / Dimnames value: each a list, or None."""
+    if dn is None:
+        return None, None
+    if isinstance(dn, RValue):
+        dn = dn.value
+    if isinstance(dn, dict):
+        dn = list(dn.values())
+    if not (isinstance(dn, list) and len(dn) == 2):
+        raise ValueError(f"{what}: expected a list of two")
+    return _name_vector(dn[0]), _name_vector(dn[1])
+
+
+def _describe(v):
+    """What a value is, for a refusal."""
+    if isinstance(v, RS4):
+        return f"an S4 object of class {v.cls!r}"
+    if isinstance(v, RFactor):
+        return "a factor"
+    if isinstance(v, RValue):
+        cls = v.attrs.get("class")
+        if cls is not None and "factor" in [str(c) for c in np.asarray(cls.value if isinstance(cls, RValue) else cls).ravel()]:
+            return "a factor"
+        if cls is not None:
+            return "an object of class " + "/".join(repr(str(c)) for c in np.asarray(cls.value if isinstance(cls, RValue) else cls).ravel())
+        return _describe(v.value) + " with the attributes " + ", ".join(v.attrs)
+    if isinstance(v, RdsPayload):
+        return ("a numeric" if v.sexp == REALSXP else "an integer") + " vector"
+    if isinstance(v, RNoPayload):
+        return f"an ALTREP {v.cls} (a sequence R stores as length, start and step: it has no elements in the stream)"
+    if isinstance(v, np.ndarray):
+        return {"U": "a character", "S": "a character", "O": "a character", "b": "a logical"}.get(v.dtype.kind, "a numeric") + (" matrix" if v.ndim == 2 else " vector")
+    if isinstance(v, (list, dict)):
+        return "a list"
+    return "NULL" if v is None else f"a {type(v).__name__}"
+
+
+def _names_or_given(found, given, n, what, missing):
+    if given is not None:
+        given = [str(s) for s in given]
+        if len(given) != n:
+            raise ValueError(f"{what}: {len(given)} names were passed, the matrix has {n}")
+        return given
+    if found is None:
+        raise ValueError(missing)
+    if len(found) != n:
+        raise ValueError(f"{what}: {len(found)} names for {n}")
+    return found
+
+
+def locate_counts(buf, *, gene_names=None, cell_names=None):
+    """Where the count matrix of a serialised stream lies (DESIGN K34): `buf` is what _Reader parses -- an mmap, bytes, or the
+    _DeviceStream of a file inflated on the device.  The stream is walked with _Reader, but a REALSXP / INTSXP vector of at
+    least DEVICE_THRESHOLD bytes is not decoded: it is recorded as an RdsPayload (byte offset, element size, length); smaller
+    ones are recorded AND decoded (RdsPayload.value).  Returns an RdsCounts.
+
+    Accepted: an .rds whose value is a numeric or integer matrix (attributes dim and dimnames only), a data.frame of numeric /
+    integer columns of one length with character row.names, or a dgCMatrix (package Matrix: slots i, p, Dim, Dimnames, x,
+    factors); and an .rda / .RData container that holds exactly one variable of one of them.  Everything else is a ValueError
+    that names what was found: another S4 class, a data.frame column that is a factor, character or logical (with the column's
+    name), further attributes on a matrix, compact row.names or missing dimnames / Dimnames (unless gene_names / cell_names are
+    passed: they then supply the names, and their lengths must match), columns of unequal length, a Dim that disagrees with
+    length(p) - 1, length(i) != length(x).  (length(x) != p[C] needs p: icnv_rds_csc_check_dev tests it on the device.)"""
+    rd = _LocatingReader(buf)
+    container = rd.header()
+    top = rd.item()
+    variable = None
+    if container == "rda":
+        if not isinstance(top, _Pairlist):
+            raise ValueError("an .rda container holds a tagged pairlist")
+        if len(top.values) != 1:
+            raise ValueError(f"the container holds {len(top.values)} variables ({', '.join(str(t) for t in top.tags)}); exactly one count matrix is read")
+        variable, top = top.tags[0], top.values[0]
+    what = "the file" if variable is None else f"the variable {variable!r}"
+    out = RdsCounts("", 0, 0, None, None, [], None, container, variable)
+    no_genes = f"{what} has no row names: pass gene_names"
+    no_cells = f"{what} has no column names: pass cell_names"
+    if isinstance(top, RS4):
+        if top.cls != "dgCMatrix":
+            raise ValueError(f"{what} holds an S4 object of class {top.cls!r}; of the Matrix classes only dgCMatrix is read")
+        sl = top.slots
+        for name, sexp in (("i", INTSXP), ("p", INTSXP), ("x", REALSXP)):
+            if not (isinstance(sl.get(name), RdsPayload) and sl[name].sexp == sexp):
+                raise ValueError(f"{what}: slot {name} of the dgCMatrix is {_describe(sl.get(name))}")
+        dim = _small(sl.get("Dim"), "slot Dim")
+        if dim is None or dim.size != 2 or int(dim[0]) < 1 or int(dim[1]) < 1:
+            raise ValueError(f"{what}: slot Dim of the dgCMatrix is not two positive integers")
+        out.kind, out.G, out.C = "dgCMatrix", int(dim[0]), int(dim[1])
+        i, p, x = sl["i"], sl["p"], sl["x"]
+        if p.length - 1 != out.C:
+            raise ValueError(f"{what}: Dim says {out.C} columns, p has {p.length} entries ({p.length - 1} columns)")
+        if i.length != x.length:
+            raise ValueError(f"{what}: i has {i.length} entries, x has {x.length}")
+        if x.length > 0x7FFFFFFF:
+            raise ValueError(f"{what}: a dgCMatrix of {x.length} entries is beyond 2^31 - 1")
+        g, c = _dim_names(sl.get("Dimnames"), "slot Dimnames")
+        if g is None and gene_names is None:
+            no_genes = f"{what}: the dgCMatrix has no row names in Dimnames: pass gene_names"
+        if c is None and cell_names is None:
+            no_cells = f"{what}: the dgCMatrix has no column names in Dimnames: pass cell_names"
+        out.payloads, out.nnz = [i, p, x], x.length
+    elif isinstance(top, RValue) and isinstance(top.value, RdsPayload):
+        extra = [k for k in top.attrs if k not in ("dim", "dimnames")]
+        if extra:
+            raise ValueError(f"{what} holds a matrix with the attributes {', '.join(extra)} beyond dim and dimnames")
+        dim = _small(top.attrs.get("dim"), "dim")
+        if dim is None or dim.size != 2:
+            raise ValueError(f"{what} holds {_describe(top.value)} that is no matrix (dim has {0 if dim is None else dim.size} entries)")
+        pl = top.value
+        out.G, out.C = int(dim[0]), int(dim[1])
+        if out.G < 1 or out.C < 1 or out.G * out.C != pl.length:
+            raise ValueError(f"{what}: dim is {out.G} x {out.C}, the vector has {pl.length} elements")
+        out.kind = "matrix_real" if pl.sexp == REALSXP else "matrix_int"
+        g, c = _dim_names(top.attrs.get("dimnames"), "dimnames")
+        out.payloads = [pl]
+    elif isinstance(top, RValue) and isinstance(top.value, (dict, list)) and "data.frame" in [
+            str(k) for k in np.asarray(_small(top.attrs.get("class"), "class") if top.attrs.get("class") is not None else []).ravel()]:
+        if isinstance(top.value, dict):
+            names, cols = list(top.value), list(top.value.values())
+        else:
+            names, cols = _name_vector(top.attrs.get("names")), top.value
+        if not cols:
+            raise ValueError(f"{what} holds a data.frame without columns")
+        for k, col in enumerate(cols):
+            label = repr(names[k]) if names is not None and k < len(names) else f"number {k + 1}"
+            if not isinstance(col, RdsPayload):
+                raise ValueError(f"{what}: column {label} of the data.frame is {_describe(col)}; only numeric and integer columns stored in full are read")
+            if col.length != cols[0].length:
+                raise ValueError(f"{what}: column {label} of the data.frame has {col.length} rows, the first column has {cols[0].length}")
+        out.kind, out.G, out.C = "data_frame", cols[0].length, len(cols)
+        if out.G < 1:
+            raise ValueError(f"{what} holds a data.frame without rows")
+        g, c = _name_vector(top.attrs.get("row.names")), names
+        if g is None and gene_names is None:
+            no_genes = f"{what}: the data.frame has compact row.names (no gene names): pass gene_names"
+        out.payloads = list(cols)
+    else:
+        raise ValueError(f"{what} holds {_describe(top)}; a numeric matrix, a data.frame or a dgCMatrix is read")
+    out.genes = _names_or_given(g, gene_names, out.G, "gene_names", no_genes)
+    out.cells = _names_or_given(c, cell_names, out.C, "cell_names", no_cells)
+    return out
+
+
+def open_counts(path, *, device=True):
+    """(buf, route, reason) for locate_counts and device.read_rds_counts: the serialised bytes of `path` and how they were got.
+    route "none": an uncompressed file, mapped; "device_k29" / "device_k30": a gzip file inflated on the device (buf is the
+    _DeviceStream; _open_on_device); "host": gzip turned away there, bzip2 or xz, inflated by Python -- reason says why."""
+    if device:
+        buf = _open_on_device(path)
+        if buf is not None:
+            return buf, ("device_k29" if inflate_stats().get("route") == "device" else "device_k30"), ""
+    buf, compressed = _open_bytes(path)
+    if not compressed:
+        return buf, "none", ""
+    with open(path, "rb") as fh:
+        gz = fh.read(2) == b"\x1f\x8b"
+    if not gz:
+        return buf, "host", "not a gzip file"
+    if not device or not _device_available():
+        return buf, "host", "no device"
+    if not _inflate_enabled():
+        return buf, "host", "ICNV_INFLATE=0"
+    from . import gunzip
+    return buf, "host", f"K29: {inflate_stats().get('reason', '')}; K30: {gunzip.gunzip_stats().get('reason', '')}"
+
+
+def close_counts(buf):
+    """Closes the mapping open_counts made of an uncompressed file (nothing to do for bytes or a device stream).  No NumPy view
+    of it may be alive."""
+    if isinstance(buf, mmap.mmap):
+        buf.close()
 
 
 # ================================================================================================================ infercnv objects

@@ -349,7 +349,8 @@ class ShardedCreate:
         reader          (path, cells) -> (gene names, ALL cell names, the (len(cells), G) array of file columns `cells`, or
                         for a .mtx / 10x source the G x len(cells) scipy CSC); replaces device.read_table / read_mtx, and the
                         matrix work then runs in NumPy / SciPy -- the host logic without a GPU.
-    The matrix is a file: a text table, a .mtx or a 10x directory.  Two phases around one exchange:
+    The matrix is a file: a text table, a .mtx, a 10x directory, or an R file (.rds, .rda / .RData: DESIGN K34 -- the column count
+    comes from rds.locate_counts, the rank's columns from device.read_rds_counts(cells=)).  Two phases around one exchange:
         read()              header or size line, gene order, annotations -- CreateInfercnvObject's checks in its order --, the
                             deal (world > the file's columns: ValueError before the body is read), this rank's columns parsed,
                             .order_reduce; returns the column sums of its columns over the kept genes, in the order of the deal
@@ -395,11 +396,20 @@ class ShardedCreate:
         annotations = co.read_annotations(a["annotations_file"], a["delim"])
         raw = a["raw_counts_matrix"]
         if not isinstance(raw, (str, os.PathLike)):
-            raise ValueError("ShardedCreate reads the matrix from a file: a text table, a .mtx file or a 10x directory")
-        mtx = co._mtx_source(raw, a["gene_names"], a["cell_names"], a["gene_column"])
-        if mtx is None and a["sparse"]:
+            raise ValueError("ShardedCreate reads the matrix from a file: a text table, a .mtx file, a 10x directory or an .rds / .rda file")
+        rds_path = co._rds_source(raw)
+        mtx = None if rds_path is not None else co._mtx_source(raw, a["gene_names"], a["cell_names"], a["gene_column"])
+        if rds_path is not None:                                         # K34: the shape is in the stream's attributes
+            from . import rds
+            names = co._rds_names(a["gene_names"], a["cell_names"], a["gene_column"])
+            opened = rds.open_counts(rds_path, device=self.reader is None)
+            located = rds.locate_counts(opened[0], **names)
+            if a["sparse"] and located.kind != "dgCMatrix":
+                raise ValueError("sparse=True wants a .mtx file, a 10x directory or a scipy sparse matrix")
+            C_file = located.C
+        elif mtx is None and a["sparse"]:
             raise ValueError("sparse=True wants a .mtx file, a 10x directory or a scipy sparse matrix")
-        if mtx is not None:                                              # the size line
+        elif mtx is not None:                                            # the size line
             import gzip
             from .device import _mtx_header
             with (gzip.open(mtx[0], "rb") if mtx[0].endswith(".gz") else open(mtx[0], "rb")) as f:
@@ -410,7 +420,23 @@ class ShardedCreate:
             raise ValueError(f"world is {self.world}, but the file has only {C_file} columns")
         mine = self.dealt(C_file)
         counts = x = None
-        if mtx is not None:
+        if rds_path is not None:
+            if self.reader is not None:
+                genes, cells, got = self.reader(rds_path, mine)
+                sparse_kind = hasattr(got, "tocsc")
+            else:
+                from . import device
+                genes, cells, got, _ = device.read_rds_counts(rds_path, cells=mine, chunk_bytes=a["chunk_bytes"], opened=opened, **names)
+                sparse_kind = isinstance(got, device.DeviceCounts)
+            rds.close_counts(opened[0])
+            del opened
+            if sparse_kind and a["sparse"] is False:
+                x = np.ascontiguousarray(got.toarray().T) if self.reader is not None else got.to_dense()
+            elif sparse_kind:
+                counts = got
+            else:
+                x = got
+        elif mtx is not None:
             genes, cells = mtx[1], mtx[2]
             if self.reader is not None:
                 _, _, counts = self.reader(mtx[0], mine)
