@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import Cfg, check, f64, i32, pack_groups
+from .text_stream import LineChunks, _pinned
 
 
 def _stream():
@@ -28,6 +29,17 @@ def _stream():
 
 def _ptr(t):
     return ct.c_void_p(t.data_ptr()) if t is not None else ct.c_void_p(0)
+
+
+def _counters(name, fields, reset):
+    """The int64 counters of icnv_<name>_stats as a dict keyed by `fields`; reset=True zeroes them afterwards
+    (icnv_<name>_stats_reset)."""
+    L = _lib.load()
+    out = (ct.c_int64 * len(fields))()
+    check(getattr(L, f"icnv_{name}_stats")(out, len(fields)))
+    if reset:
+        getattr(L, f"icnv_{name}_stats_reset")()
+    return dict(zip(fields, (int(v) for v in out)))
 
 
 def _check_matrix(x, dtype=torch.float64):
@@ -123,12 +135,7 @@ SMOOTH_WINDOWS_STATS = ("calls", "tiles_lds", "tiles_spilled", "weighted_calls",
 
 def smooth_windows_stats(reset=False):
     """icnv_smooth_windows_stats as a dict (`us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(SMOOTH_WINDOWS_STATS))()
-    check(L.icnv_smooth_windows_stats(out, len(SMOOTH_WINDOWS_STATS)))
-    if reset:
-        L.icnv_smooth_windows_stats_reset()
-    return dict(zip(SMOOTH_WINDOWS_STATS, (int(v) for v in out)))
+    return _counters("smooth_windows", SMOOTH_WINDOWS_STATS, reset)
 
 
 # ------------------------------------------------------------------ data layer of plot_cnv (DESIGN K17)
@@ -203,12 +210,7 @@ HEATMAP_STATS = ("calls", "radix_passes", "candidates", "us")
 
 def heatmap_stats(reset=False):
     """icnv_heatmap_stats as a dict (`us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(HEATMAP_STATS))()
-    check(L.icnv_heatmap_stats(out, len(HEATMAP_STATS)))
-    if reset:
-        L.icnv_heatmap_stats_reset()
-    return dict(zip(HEATMAP_STATS, (int(v) for v in out)))
+    return _counters("heatmap", HEATMAP_STATS, reset)
 
 
 # ------------------------------------------------------------------ matrix files of plot_cnv (DESIGN K20)
@@ -286,12 +288,7 @@ TABLE_TEXT_STATS = ("calls", "rows", "elements", "host_formatted", "bytes", "col
 def table_text_stats(reset=False):
     """icnv_table_text_stats as a dict (`host_formatted`: elements the digits pass could not certify, formatted by the host;
     `us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(TABLE_TEXT_STATS))()
-    check(L.icnv_table_text_stats(out, len(TABLE_TEXT_STATS)))
-    if reset:
-        L.icnv_table_text_stats_reset()
-    return dict(zip(TABLE_TEXT_STATS, (int(v) for v in out)))
+    return _counters("table_text", TABLE_TEXT_STATS, reset)
 
 
 # ------------------------------------------------------------------ CNV region reports (DESIGN K24)
@@ -396,12 +393,7 @@ def cnv_report(kind, records, groups, chrs, genes, start, end, capacity=None):
 def cnv_report_stats(reset=False):
     """icnv_cnv_report_stats as a dict (`calls`: format calls; `us`: their wall time in microseconds); reset=True zeroes the
     counters."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(CNV_REPORT_STATS))()
-    check(L.icnv_cnv_report_stats(out, len(CNV_REPORT_STATS)))
-    if reset:
-        L.icnv_cnv_report_stats_reset()
-    return dict(zip(CNV_REPORT_STATS, (int(v) for v in out)))
+    return _counters("cnv_report", CNV_REPORT_STATS, reset)
 
 
 # ------------------------------------------------------------------ count matrices from text (DESIGN K21)
@@ -412,12 +404,7 @@ READ_TABLE_CHUNK = 64 << 20        # bytes of one chunk of read_table; ICNV_READ
 def table_parse_stats(reset=False):
     """icnv_table_parse_stats as a dict (`host_parsed`: fields the parse pass could not certify, parsed by the host's strtod;
     `us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(TABLE_PARSE_STATS))()
-    check(L.icnv_table_parse_stats(out, len(TABLE_PARSE_STATS)))
-    if reset:
-        L.icnv_table_parse_stats_reset()
-    return dict(zip(TABLE_PARSE_STATS, (int(v) for v in out)))
+    return _counters("table_parse", TABLE_PARSE_STATS, reset)
 
 
 def _host_text_ptr(host):
@@ -426,12 +413,8 @@ def _host_text_ptr(host):
     return None if host is None else ct.c_void_p(host.ctypes.data)
 
 
-def parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, line0=1):
-    """icnv_parse_table_dev: the first n_bytes of `text_dev` (contiguous CUDA uint8) and of `text_host` (a contiguous uint8
-    numpy array or CPU tensor with the same bytes) are whole lines of a table with out.shape[0] numeric columns; row i of them
-    goes to out[:, row0 + i].  out: a CUDA float64 (n_cols, ld) tensor with contiguous rows.  Returns (rows found, int64 label
-    ranges [rows, 2] into the bytes).  text_host None: no host copy exists; the ranges then still include a label's quotes.  On an IcnvError `out` is as it was.  Synchronises the stream."""
-    L = _lib.load()
+def _check_text(text_dev, text_host, n_bytes):
+    """The argument checks the parse entries share: the host copy of the chunk as a numpy array, or None."""
     if not (isinstance(text_dev, torch.Tensor) and text_dev.is_cuda and text_dev.dtype == torch.uint8 and text_dev.dim() == 1
             and text_dev.is_contiguous()):
         raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
@@ -441,6 +424,16 @@ def parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, lin
     n_bytes = int(n_bytes)
     if n_bytes < 1 or n_bytes > text_dev.numel() or (host is not None and n_bytes > host.size):
         raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
+    return host
+
+
+def parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, line0=1):
+    """icnv_parse_table_dev: the first n_bytes of `text_dev` (contiguous CUDA uint8) and of `text_host` (a contiguous uint8
+    numpy array or CPU tensor with the same bytes) are whole lines of a table with out.shape[0] numeric columns; row i of them
+    goes to out[:, row0 + i].  out: a CUDA float64 (n_cols, ld) tensor with contiguous rows.  Returns (rows found, int64 label
+    ranges [rows, 2] into the bytes).  text_host None: no host copy exists; the ranges then still include a label's quotes.  On an IcnvError `out` is as it was.  Synchronises the stream."""
+    L = _lib.load()
+    host = _check_text(text_dev, text_host, n_bytes)
     n_cols, _, ld = _check_matrix_ld(out)
     row0, max_rows = int(row0), int(max_rows)
     if row0 < 0 or max_rows < 1 or row0 + max_rows > out.shape[1]:
@@ -450,7 +443,7 @@ def parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, lin
     sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
     ranges = np.zeros((max_rows, 2), dtype=np.int64)
     n_rows = ct.c_int64(0)
-    check(L.icnv_parse_table_dev(_ptr(text_dev), _host_text_ptr(host), n_bytes, sep_b, n_cols, int(line0), _ptr(out), int(ld), row0,
+    check(L.icnv_parse_table_dev(_ptr(text_dev), _host_text_ptr(host), int(n_bytes), sep_b, n_cols, int(line0), _ptr(out), int(ld), row0,
                                  max_rows, ranges.ctypes.data_as(ct.POINTER(ct.c_int64)), ct.byref(n_rows), _stream()))
     return int(n_rows.value), ranges[:int(n_rows.value)]
 
@@ -486,18 +479,10 @@ def parse_table_cols_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows
     int32 vector with one entry per numeric column of the FILE, the row of `out` (out.shape[0] = n_cols_out) that column goes
     to, or -1.  The fields of skipped columns are not examined.  Returns (rows found, label ranges)."""
     L = _lib.load()
-    if not (isinstance(text_dev, torch.Tensor) and text_dev.is_cuda and text_dev.dtype == torch.uint8 and text_dev.dim() == 1
-            and text_dev.is_contiguous()):
-        raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
-    host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
-    if host is not None and not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
-        raise TypeError("text_host must be a contiguous one-dimensional uint8 array, or None")
     if not (isinstance(col_map, torch.Tensor) and col_map.is_cuda and col_map.dtype == torch.int32 and col_map.dim() == 1
             and col_map.is_contiguous() and col_map.numel() >= 1):
         raise TypeError("col_map must be a contiguous one-dimensional CUDA int32 tensor")
-    n_bytes = int(n_bytes)
-    if n_bytes < 1 or n_bytes > text_dev.numel() or (host is not None and n_bytes > host.size):
-        raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
+    host = _check_text(text_dev, text_host, n_bytes)
     n_out, _, ld = _check_matrix_ld(out)
     row0, max_rows = int(row0), int(max_rows)
     if row0 < 0 or max_rows < 1 or row0 + max_rows > out.shape[1]:
@@ -507,7 +492,7 @@ def parse_table_cols_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows
     sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
     ranges = np.zeros((max_rows, 2), dtype=np.int64)
     n_rows = ct.c_int64(0)
-    check(L.icnv_parse_table_cols_dev(_ptr(text_dev), _host_text_ptr(host), n_bytes, sep_b, int(col_map.numel()), int(line0), _ptr(out),
+    check(L.icnv_parse_table_cols_dev(_ptr(text_dev), _host_text_ptr(host), int(n_bytes), sep_b, int(col_map.numel()), int(line0), _ptr(out),
                                       int(ld), row0, max_rows, ranges.ctypes.data_as(ct.POINTER(ct.c_int64)), ct.byref(n_rows), _ptr(col_map),
                                       n_out, _stream()))
     return int(n_rows.value), ranges[:int(n_rows.value)]
@@ -582,27 +567,16 @@ def _unquote(b):
     return b[1:-1] if len(b) >= 2 and b[:1] == b"\"" and b[-1:] == b"\"" else b
 
 
-def _pinned(n):
-    return torch.empty(int(n), dtype=torch.uint8, pin_memory=True)
-
-
-def _last_newline(arr, n):
-    """Index of the last '\\n' of arr[:n], or -1."""
-    hi = n
-    while hi > 0:
-        lo = max(0, hi - (1 << 16))
-        hit = np.flatnonzero(arr[lo:hi] == 10)
-        if hit.size:
-            return lo + int(hit[-1])
-        hi = lo
-    return -1
+def _open_text(path, buffering=-1):
+    """The file at `path` open for reading its bytes, decompressed by Python's gzip where the name ends in .gz."""
+    import gzip
+    return gzip.open(path, "rb") if str(path).endswith(".gz") else open(path, "rb", buffering=buffering)
 
 
 def _count_newlines(path, n_bytes):
     """'\\n' among the first n_bytes of the (decompressed) file: the error path of read_table."""
-    import gzip
     count = 0
-    with (gzip.open(path, "rb") if str(path).endswith(".gz") else open(path, "rb")) as f:
+    with _open_text(path) as f:
         while n_bytes > 0:
             block = f.read(min(n_bytes, 1 << 24))
             if not block:
@@ -687,8 +661,56 @@ def _dev_labels(chunk, ranges):
     return out
 
 
+def _table_columns(header_line, first_data_line, sep_b):
+    """The names (bytes) of the numeric columns of a table: the header line (without its '\\n') has one name per numeric
+    column, as write.table writes it, or one more with a corner label in front; the first line with data (None: the file has
+    none) decides which.  Quotes around a name are dropped."""
+    if first_data_line is None:
+        raise ValueError("read_table: the file has no data row")
+    line = header_line[:-1] if header_line.endswith(b"\r") else header_line
+    header_names = [_unquote(t) for t in line.split(sep_b)]
+    k = first_data_line.count(sep_b) + 1
+    if len(header_names) == k - 1:
+        col_names = header_names
+    elif len(header_names) == k and k >= 2:
+        col_names = header_names[1:]
+    else:
+        raise ValueError(f"read_table: the header has {len(header_names)} names, the first row has {k} fields")
+    if len(col_names) < 1:
+        raise ValueError("read_table: the table has no numeric column")
+    return col_names
+
+
+def _parse_table_chunk(chunk, host, nb, sep_b, scratch, col_map, file_line):
+    """The nb bytes of whole lines at the start of `chunk` (on the device; host: the same bytes, or None) through
+    parse_table_into -- parse_table_cols_into where col_map is given -- into `scratch`, a (rows of x, any) CUDA float64 block
+    that is replaced when the chunk may hold more rows than it has columns.  Returns (rows, label ranges, scratch).  A refusal
+    is raised a second time with the file's line numbers; file_line() is then called for the lines of the file before the chunk."""
+    n_cols = scratch.shape[0] if col_map is None else int(col_map.numel())
+    max_rows = nb // (n_cols + 1) + 1                              # a row is at least its separators and its line end
+    if scratch.shape[1] < max_rows:
+        scratch = torch.empty((scratch.shape[0], max_rows), dtype=torch.float64, device=chunk.device)
+
+    def parse(line0=1):
+        if col_map is None:
+            return parse_table_into(chunk, host, nb, sep_b, scratch, 0, max_rows, line0=line0)
+        return parse_table_cols_into(chunk, host, nb, sep_b, scratch, 0, max_rows, col_map, line0=line0)
+    try:
+        rows, ranges = parse()
+    except _lib.IcnvError as exc:
+        short = "max_rows" in str(exc)                             # more lines than full rows fit: some row is too short
+        if exc.code != _lib.ERR_ARG or not (short or "line " in str(exc)):
+            raise
+        if short:
+            max_rows = int((chunk[:nb] == 10).sum()) + 1
+            scratch = torch.empty((scratch.shape[0], max_rows), dtype=torch.float64, device=chunk.device)
+        parse(line0=1 + file_line())                               # the refusal again, with the file's line number
+        raise
+    return rows, ranges, scratch
+
+
 def _read_table_device(text, sep_b, cap0, sel, stats):
-    """read_table's body for a file that lies inflated on the device: (row names, header names as bytes, parts).  The header
+    """read_table's body for a file that lies inflated on the device: (row names, column names as bytes, parts).  The header
     and the first data line are fetched; the body goes to the parse entries as views or device-to-device copies of `text`."""
     import time
     dev, n = text.device, int(text.numel())
@@ -700,47 +722,15 @@ def _read_table_device(text, sep_b, cap0, sel, stats):
         if data or len(head) == n:
             break
         fetch *= 2
-    if not head:
-        raise ValueError("read_table: the file has no data row")
-    line = lines[0]
-    header_names = [_unquote(t) for t in (line[:-1] if line.endswith(b"\r") else line).split(sep_b)]
-    if not data:
-        raise ValueError("read_table: the file has no data row")
-    k = data[0].count(sep_b) + 1
-    if len(header_names) == k - 1:
-        col_names = header_names
-    elif len(header_names) == k and k >= 2:
-        col_names = header_names[1:]
-    else:
-        raise ValueError(f"read_table: the header has {len(header_names)} names, the first row has {k} fields")
+    col_names = _table_columns(lines[0], data[0] if data else None, sep_b)
     n_cols = len(col_names)
-    if n_cols < 1:
-        raise ValueError("read_table: the table has no numeric column")
     col_map = None if sel is None else _column_map(sel, n_cols, "read_table", dev)
-    row_names, parts, scratch, stage = [], [], None, None
-    for a, b in _dev_line_chunks(text, min(len(line) + 1, n), cap0, stats):
+    scratch = torch.empty((n_cols if sel is None else sel.size, 0), dtype=torch.float64, device=dev)
+    row_names, parts, stage = [], [], None
+    for a, b in _dev_line_chunks(text, min(len(lines[0]) + 1, n), cap0, stats):
         t0 = time.perf_counter()
         chunk, stage = _dev_aligned(text, a, b, stage)
-        nb = b - a
-        max_rows = nb // (n_cols + 1) + 1                          # a row is at least its separators and its line end
-        if scratch is None or scratch.shape[1] < max_rows:
-            scratch = torch.empty((n_cols if sel is None else sel.size, max_rows), dtype=torch.float64, device=dev)
-
-        def parse(line0=1):
-            if col_map is None:
-                return parse_table_into(chunk, None, nb, sep_b, scratch, 0, max_rows, line0=line0)
-            return parse_table_cols_into(chunk, None, nb, sep_b, scratch, 0, max_rows, col_map, line0=line0)
-        try:
-            rows, ranges = parse()
-        except _lib.IcnvError as exc:
-            short = "max_rows" in str(exc)                         # more lines than full rows fit: some row is too short
-            if exc.code != _lib.ERR_ARG or not (short or "line " in str(exc)):
-                raise
-            if short:
-                max_rows = int((chunk == 10).sum()) + 1
-                scratch = torch.empty((scratch.shape[0], max_rows), dtype=torch.float64, device=dev)
-            parse(line0=1 + int((text[:a] == 10).sum()))           # the refusal again, with the file's line number
-            raise
+        rows, ranges, scratch = _parse_table_chunk(chunk, None, b - a, sep_b, scratch, col_map, lambda: int((text[:a] == 10).sum()))
         stats["parse_s"] += time.perf_counter() - t0
         if rows:
             parts.append(scratch[:, :rows].clone())
@@ -773,7 +763,7 @@ def read_table(path, sep="\t", chunk_bytes=None, cells=None):
 
     The header line is read here: it has one name per numeric column, as write.table writes it, or one more with a corner
     label in front.  Quotes around a name are dropped.  The body is streamed in chunks of whole lines through two pinned and two
-    device buffers: a thread reads chunk i + 1 from the file while chunk i is copied and parsed; a buffer grows when one line
+    device buffers: a thread (text_stream.LineChunks) reads chunk i + 1 from the file while chunk i is copied and parsed; a buffer grows when one line
     is longer than chunk_bytes.  A path that ends in .gz (R/inferCNV.R:146-150 reads it through gzfile) is first offered to
     gunzip.gunzip (DESIGN K30): a one-member gzip file of at least gunzip.GUNZIP_MIN_BYTES is inflated on the device, its header
     line and first data line are fetched, and the body goes to the same parse entries in chunks of whole lines that are views or
@@ -790,9 +780,6 @@ def read_table(path, sep="\t", chunk_bytes=None, cells=None):
     entry and the count).  Row k of x is then file column cells[k] -- x is (len(cells), n_rows), and so are the per-chunk
     scratch and parts --, through icnv_parse_table_cols_dev: the fields of the other columns are not examined, so a byte
     outside the grammar there is not reported.  All row names and ALL column names of the header still come back."""
-    import gzip
-    import queue
-    import threading
     import time
     path = os.fspath(path)
     sel = None if cells is None else _selected_columns(cells, "read_table")
@@ -809,47 +796,6 @@ def read_table(path, sep="\t", chunk_bytes=None, cells=None):
     text = _gunzip_text(path, stats)
     if text is not None:                                           # K30: the file lies inflated on the device; the body stays there
         return _table_result(*_read_table_device(text, sep_b, cap0, sel, stats), stats, before, t_start)
-    jobs, free, failure = queue.Queue(), [threading.Semaphore(1), threading.Semaphore(1)], []
-    stop = threading.Event()
-    pin = [_pinned(cap0), _pinned(cap0)]
-
-    def reader():
-        try:
-            with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb", buffering=0)) as f:
-                slot, fill, eof = 0, 0, False
-                free[0].acquire()
-                while not eof and not stop.is_set():
-                    t0 = time.perf_counter()
-                    arr = pin[slot].numpy()
-                    total = fill
-                    while total < arr.size:
-                        got = f.readinto(memoryview(arr)[total:])
-                        if not got:
-                            eof = True
-                            break
-                        total += got
-                    cut = total if eof else _last_newline(arr, total) + 1
-                    stats["read_s"] += time.perf_counter() - t0
-                    if cut == 0 and not eof:                      # one line is longer than the buffer: grow it and read on
-                        bigger = _pinned(2 * arr.size)
-                        bigger[:total].copy_(pin[slot][:total])
-                        pin[slot], fill = bigger, total
-                        stats["grown"] += 1
-                        continue
-                    jobs.put((slot, pin[slot], cut))              # only this thread writes a buffer, and only while it holds it
-                    nxt = 1 - slot
-                    free[nxt].acquire()                           # the chunk before this one has left that buffer
-                    tail = total - cut
-                    if pin[nxt].numel() <= tail:
-                        pin[nxt] = _pinned(2 * tail)
-                    if tail:
-                        pin[nxt][:tail].copy_(pin[slot][cut:total])
-                    slot, fill = nxt, tail
-        except Exception as exc:                                  # handed to the caller's thread below
-            failure.append(exc)
-        finally:
-            jobs.put(None)
-
     copy_stream = torch.cuda.Stream(device=dev)
     dbuf = [None, None]
 
@@ -872,96 +818,58 @@ def read_table(path, sep="\t", chunk_bytes=None, cells=None):
             p = hi
         return n
 
-    row_names, header_names, col_names, n_cols, parts, scratch = [], None, None, None, [], None
-    col_map = None                                                 # K26: the device map of the selection, once n_cols is known
+    row_names, header_line, col_names, parts, scratch = [], None, None, [], None
+    col_map = None                                                 # K26: the device map of the selection, once the columns are known
     offset, ahead = 0, None                                        # bytes of the file before this chunk; (job, event) copied ahead
-    thread = threading.Thread(target=reader, daemon=True)
-    thread.start()
-    try:
-        job = jobs.get()
-        while job is not None:
-            slot, buf, n = job
-            arr = buf.numpy()
-            start = 0
-            if header_names is None and n:                         # the header line
-                first = next_newline(arr, 0, n)
-                line = arr[:first].tobytes()
-                header_names = [_unquote(t) for t in (line[:-1] if line.endswith(b"\r") else line).split(sep_b)]
-                start = min(first + 1, n)
-            if n_cols is None:                                     # the first data line decides which header shape this is
+    with _open_text(path, buffering=0) as f, LineChunks(f, cap0, stats) as chunks:
+        try:
+            job = chunks.get()
+            while job is not None:
+                slot, buf, n = job
+                event, ahead = (ahead[1] if ahead is not None else None), None     # a copy ahead was this chunk's
+                arr = buf.numpy()
+                start = 0
+                if header_line is None and n:
+                    first = next_newline(arr, 0, n)
+                    header_line = arr[:first].tobytes()
+                    start = min(first + 1, n)
                 p = start
-                while p < n and n_cols is None:
+                while p < n and col_names is None:                 # the first data line decides which header shape this is
                     e = next_newline(arr, p, n)
                     raw = arr[p:e].tobytes()
                     if raw not in (b"", b"\r"):
-                        k = raw.count(sep_b) + 1
-                        if len(header_names) == k - 1:
-                            col_names = header_names
-                        elif len(header_names) == k and k >= 2:
-                            col_names = header_names[1:]
-                        else:
-                            raise ValueError(f"read_table: the header has {len(header_names)} names, the first row has {k} fields")
-                        n_cols = len(col_names)
-                        if n_cols < 1:
-                            raise ValueError("read_table: the table has no numeric column")
+                        col_names = _table_columns(header_line, raw, sep_b)
                         if sel is not None:
-                            col_map = _column_map(sel, n_cols, "read_table", dev)
+                            col_map = _column_map(sel, len(col_names), "read_table", dev)
+                        scratch = torch.empty((len(col_names) if sel is None else sel.size, 0), dtype=torch.float64, device=dev)
                     p = e + 1
-            nb = n - start
-            if n_cols is not None and nb > 0:
-                event = ahead[1] if ahead is not None and ahead[0] is job else upload(job, start)
-                ahead = None
-                max_rows = nb // (n_cols + 1) + 1                  # a row is at least its separators and its line end
-                if scratch is None or scratch.shape[1] < max_rows:
-                    scratch = torch.empty((n_cols if sel is None else sel.size, max_rows), dtype=torch.float64, device=dev)
-                t0 = time.perf_counter()
-                try:                                               # the next chunk's copy runs beside this parse
-                    peek = jobs.get_nowait()
-                    if peek is None:
-                        jobs.put(None)
-                    else:
+                nb = n - start
+                if col_names is not None and nb > 0:
+                    if event is None:
+                        event = upload(job, start)
+                    t0 = time.perf_counter()
+                    peek = chunks.get_nowait()                     # the next chunk's copy runs beside this parse
+                    if peek is not None:
                         ahead = (peek, upload(peek, 0))
-                except queue.Empty:
-                    pass
-                torch.cuda.current_stream().wait_event(event)
-                host = arr[start:n]
-
-                def parse(line0=1):
-                    if col_map is None:
-                        return parse_table_into(dbuf[slot], host, nb, sep_b, scratch, 0, max_rows, line0=line0)
-                    return parse_table_cols_into(dbuf[slot], host, nb, sep_b, scratch, 0, max_rows, col_map, line0=line0)
-                try:
-                    rows, ranges = parse()
-                except _lib.IcnvError as exc:
-                    short = "max_rows" in str(exc)                 # more lines than full rows fit: some row is too short
-                    if exc.code != _lib.ERR_ARG or not (short or "line " in str(exc)):
-                        raise
-                    if short:
-                        max_rows = int(np.count_nonzero(host == 10)) + 1
-                        scratch = torch.empty((scratch.shape[0], max_rows), dtype=torch.float64, device=dev)
-                    parse(line0=1 + _count_newlines(path, offset + start))       # the refusal again, with the file's line number
-                    raise
-                stats["parse_s"] += time.perf_counter() - t0
-                if rows:
-                    parts.append(scratch[:, :rows].clone())
-                    for b, e in ranges.tolist():
-                        row_names.append(host[b:e].tobytes().decode("utf-8", "surrogateescape"))
-                stats["chunks"] += 1
-            offset += n
-            stats["bytes"] += n
-            free[slot].release()
-            t0 = time.perf_counter()
-            job = ahead[0] if ahead is not None else jobs.get()
-            stats["stall_s"] += time.perf_counter() - t0
-    finally:
-        stop.set()
-        torch.cuda.synchronize()                                   # a copy ahead may still read a pinned buffer
-        for sem in free:
-            sem.release()
-        thread.join()
-    if failure:
-        raise failure[0]
-    if n_cols is None:
+                    torch.cuda.current_stream().wait_event(event)
+                    host = arr[start:n]
+                    rows, ranges, scratch = _parse_table_chunk(dbuf[slot], host, nb, sep_b, scratch, col_map,
+                                                               lambda: _count_newlines(path, offset + start))
+                    stats["parse_s"] += time.perf_counter() - t0
+                    if rows:
+                        parts.append(scratch[:, :rows].clone())
+                        for b, e in ranges.tolist():
+                            row_names.append(host[b:e].tobytes().decode("utf-8", "surrogateescape"))
+                    stats["chunks"] += 1
+                offset += n
+                stats["bytes"] += n
+                chunks.release(slot)
+                t0 = time.perf_counter()
+                job = ahead[0] if ahead is not None else chunks.get()
+                stats["stall_s"] += time.perf_counter() - t0
+        finally:
+            torch.cuda.synchronize()                               # a copy ahead may still read a pinned buffer
+    if col_names is None:
         parts = []
     return _table_result(row_names, col_names, parts, stats, before, t_start)
 
@@ -1267,12 +1175,7 @@ KNN_STATS = ("calls", "problems", "query_rows", "row_blocks", "screened_rows", "
 
 def knn_stats(reset=False):
     """icnv_knn_stats as a dict (synchronises the device); reset=True zeroes the counters afterwards."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(KNN_STATS))()
-    check(L.icnv_knn_stats(out, len(KNN_STATS)))
-    if reset:
-        L.icnv_knn_stats_reset()
-    return dict(zip(KNN_STATS, (int(v) for v in out)))
+    return _counters("knn", KNN_STATS, reset)
 
 
 HCLUST_METHODS = {"ward.D": 1, "ward.D2": 2, "single": 3, "complete": 4, "average": 5, "mcquitty": 6, "centroid": 7,
@@ -1334,12 +1237,7 @@ HCLUST_STATS = ("calls", "problems", "lds_problems", "hbm_problems", "chain_step
 
 def hclust_stats(reset=False):
     """icnv_hclust_stats as a dict (`us`: wall time of the calls in microseconds); reset=True zeroes the counters afterwards."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(HCLUST_STATS))()
-    check(L.icnv_hclust_stats(out, len(HCLUST_STATS)))
-    if reset:
-        L.icnv_hclust_stats_reset()
-    return dict(zip(HCLUST_STATS, (int(v) for v in out)))
+    return _counters("hclust", HCLUST_STATS, reset)
 
 
 def _u64(a):
@@ -1396,12 +1294,7 @@ RANDOM_TREES_STATS = ("calls", "clades", "permuted", "waves", "chain_steps", "us
 
 def random_trees_stats(reset=False):
     """icnv_random_trees_stats as a dict (`us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(RANDOM_TREES_STATS))()
-    check(L.icnv_random_trees_stats(out, len(RANDOM_TREES_STATS)))
-    if reset:
-        L.icnv_random_trees_stats_reset()
-    return dict(zip(RANDOM_TREES_STATS, (int(v) for v in out)))
+    return _counters("random_trees", RANDOM_TREES_STATS, reset)
 
 
 LEIDEN_OBJECTIVES = {"CPM": _lib.LEIDEN_CPM, "modularity": _lib.LEIDEN_MODULARITY}   # ICNV_LEIDEN_* of include/icnv.h
@@ -1589,12 +1482,7 @@ LEIDEN_STATS = ("calls", "problems", "levels", "move_visits", "refine_visits", "
 
 def leiden_stats(reset=False):
     """icnv_leiden_stats as a dict (`us`: wall time of the calls in microseconds); reset=True zeroes the counters."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(LEIDEN_STATS))()
-    check(L.icnv_leiden_stats(out, len(LEIDEN_STATS)))
-    if reset:
-        L.icnv_leiden_stats_reset()
-    return dict(zip(LEIDEN_STATS, (int(v) for v in out)))
+    return _counters("leiden", LEIDEN_STATS, reset)
 
 
 DE_TESTS = {"wilcoxon": _lib.DE_WILCOXON, "t": _lib.DE_T}   # ICNV_DE_* of include/icnv.h
@@ -1700,12 +1588,7 @@ DE_STATS = ("calls", "comparisons", "genes", "segments_lds", "segments_hbm", "wa
 
 def de_stats(reset=False):
     """icnv_de_stats as a dict (`us`: wall time of the test calls in microseconds); reset=True zeroes the counters."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(DE_STATS))()
-    check(L.icnv_de_stats(out, len(DE_STATS)))
-    if reset:
-        L.icnv_de_stats_reset()
-    return dict(zip(DE_STATS, (int(v) for v in out)))
+    return _counters("de", DE_STATS, reset)
 
 
 def _bayes_offsets(regions_cells):
@@ -1793,12 +1676,7 @@ BAYES_STATS = ("calls", "regions", "rows", "undecided_rows", "regions_lds", "reg
 
 def bayes_stats(reset=False):
     """icnv_bayes_stats as a dict (`us` / `loglik_us`: wall microseconds of the sample / likelihood calls); reset=True zeroes it."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(BAYES_STATS))()
-    check(L.icnv_bayes_stats(out, len(BAYES_STATS)))
-    if reset:
-        L.icnv_bayes_stats_reset()
-    return dict(zip(BAYES_STATS, (int(v) for v in out)))
+    return _counters("bayes", BAYES_STATS, reset)
 
 
 MCMC_CHAIN_FIELDS = ("mean", "var", "spec0", "order", "geweke", "acf1", "acf5", "acf10", "acf50")
@@ -2176,21 +2054,10 @@ def _mtx_header(f):
         return _MM_FIELDS[field], G, C, nnz, n_lines, n_bytes
 
 
-def parse_triplets_into(text_dev, text_host, n_bytes, field, G, C, row, col, val, offset, line0=1):
-    """icnv_parse_triplets_dev: the first n_bytes of `text_dev` (contiguous CUDA uint8) and of `text_host` (uint8 numpy array
-    with the same bytes) are whole lines of the body of a coordinate file of a G x C matrix; entry k of them goes to slot
-    offset + k of row / col / val (CUDA int32 of one length).  Returns the entries found.  On an IcnvError the arrays are as they
-    were.  Synchronises the stream."""
-    L = _lib.load()
-    if not (isinstance(text_dev, torch.Tensor) and text_dev.is_cuda and text_dev.dtype == torch.uint8 and text_dev.dim() == 1
-            and text_dev.is_contiguous()):
-        raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
-    host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
-    if host is not None and not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
-        raise TypeError("text_host must be a contiguous one-dimensional uint8 array, or None")
-    n_bytes, offset = int(n_bytes), int(offset)
-    if n_bytes < 1 or n_bytes > text_dev.numel() or (host is not None and n_bytes > host.size):
-        raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
+def _triplet_slots(row, col, val, offset):
+    """The argument checks the triplet entries share: (the addresses of slot `offset` of row / col / val, the slots from there
+    on)."""
+    offset = int(offset)
     for t in (row, col, val):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
                 and t.numel() == row.numel()):
@@ -2199,8 +2066,19 @@ def parse_triplets_into(text_dev, text_host, n_bytes, field, G, C, row, col, val
         raise ValueError("offset must be 0 .. the length of the arrays")
     capacity = row.numel() - offset
     at = [ct.c_void_p(t.data_ptr() + 4 * offset) if capacity else ct.c_void_p(0) for t in (row, col, val)]
+    return at, capacity
+
+
+def parse_triplets_into(text_dev, text_host, n_bytes, field, G, C, row, col, val, offset, line0=1):
+    """icnv_parse_triplets_dev: the first n_bytes of `text_dev` (contiguous CUDA uint8) and of `text_host` (uint8 numpy array
+    with the same bytes) are whole lines of the body of a coordinate file of a G x C matrix; entry k of them goes to slot
+    offset + k of row / col / val (CUDA int32 of one length).  Returns the entries found.  On an IcnvError the arrays are as they
+    were.  Synchronises the stream."""
+    L = _lib.load()
+    host = _check_text(text_dev, text_host, n_bytes)
+    at, capacity = _triplet_slots(row, col, val, offset)
     n = ct.c_int64(0)
-    check(L.icnv_parse_triplets_dev(_ptr(text_dev), _host_text_ptr(host), n_bytes, int(field), int(G), int(C), int(line0), at[0], at[1],
+    check(L.icnv_parse_triplets_dev(_ptr(text_dev), _host_text_ptr(host), int(n_bytes), int(field), int(G), int(C), int(line0), at[0], at[1],
                                     at[2], capacity, ct.byref(n), _stream()))
     return int(n.value)
 
@@ -2211,28 +2089,13 @@ def parse_triplets_cols_into(text_dev, text_host, n_bytes, field, G, C, row, col
     go, in file order and with their new column, to the slots from `offset` on.  Returns (kept, seen).  When the arrays are
     too short for the kept entries the IcnvError's text holds their number ("N entries are kept")."""
     L = _lib.load()
-    if not (isinstance(text_dev, torch.Tensor) and text_dev.is_cuda and text_dev.dtype == torch.uint8 and text_dev.dim() == 1
-            and text_dev.is_contiguous()):
-        raise TypeError("text_dev must be a contiguous one-dimensional CUDA uint8 tensor")
-    host = text_host.numpy() if isinstance(text_host, torch.Tensor) else text_host
-    if host is not None and not (isinstance(host, np.ndarray) and host.dtype == np.uint8 and host.ndim == 1 and host.flags.c_contiguous):
-        raise TypeError("text_host must be a contiguous one-dimensional uint8 array, or None")
     if not (isinstance(col_map, torch.Tensor) and col_map.is_cuda and col_map.dtype == torch.int32 and col_map.dim() == 1
             and col_map.is_contiguous() and col_map.numel() == int(C)):
         raise TypeError("col_map must be a contiguous CUDA int32 vector with one entry per column of the matrix")
-    n_bytes, offset = int(n_bytes), int(offset)
-    if n_bytes < 1 or n_bytes > text_dev.numel() or (host is not None and n_bytes > host.size):
-        raise ValueError("n_bytes must be 1 .. the size of both copies of the text")
-    for t in (row, col, val):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
-                and t.numel() == row.numel()):
-            raise TypeError("row, col and val must be contiguous CUDA int32 vectors of one length")
-    if offset < 0 or offset > row.numel():
-        raise ValueError("offset must be 0 .. the length of the arrays")
-    capacity = row.numel() - offset
-    at = [ct.c_void_p(t.data_ptr() + 4 * offset) if capacity else ct.c_void_p(0) for t in (row, col, val)]
+    host = _check_text(text_dev, text_host, n_bytes)
+    at, capacity = _triplet_slots(row, col, val, offset)
     kept, seen = ct.c_int64(0), ct.c_int64(0)
-    check(L.icnv_parse_triplets_cols_dev(_ptr(text_dev), _host_text_ptr(host), n_bytes, int(field), int(G), int(C), int(line0), at[0],
+    check(L.icnv_parse_triplets_cols_dev(_ptr(text_dev), _host_text_ptr(host), int(n_bytes), int(field), int(G), int(C), int(line0), at[0],
                                          at[1], at[2], capacity, ct.byref(kept), _ptr(col_map), int(n_cols_out), ct.byref(seen), _stream()))
     return int(kept.value), int(seen.value)
 
@@ -2252,9 +2115,8 @@ def csc_from_sorted_triplets(row, col, G, C):
 
 def _count_entries(path, skip_bytes):
     """The lines after the first skip_bytes of the (decompressed) file that are not blank: the error path of read_mtx."""
-    import gzip
     count = 0
-    with (gzip.open(path, "rb") if str(path).endswith(".gz") else open(path, "rb")) as f:
+    with _open_text(path) as f:
         f.read(skip_bytes)
         for line in f:
             count += bool(line.strip(b" \t\r\n"))
@@ -2300,7 +2162,7 @@ def read_mtx(path, chunk_bytes=None, cells=None):
 
     The banner, the % comment lines and the size line `G C nnz` are read here; only `%%MatrixMarket matrix coordinate
     {integer|real|pattern} general` is accepted (ValueError names the banner field otherwise).  The body is streamed in chunks
-    of whole lines through two pinned buffers and a device buffer while a thread reads ahead.  A .gz path is first offered to
+    of whole lines through two pinned buffers and a device buffer while a thread (text_stream.LineChunks) reads ahead.  A .gz path is first offered to
     gunzip.gunzip (DESIGN K30): a one-member gzip file of at least gunzip.GUNZIP_MIN_BYTES is inflated on the device, its header
     lines are fetched, and the body goes to the same parse entries in chunks of whole lines that are views or device-to-device
     copies of the inflated tensor -- it does not cross PCIe (a chunk's last newline is looked for in 64 KiB pieces; a refused
@@ -2325,11 +2187,8 @@ def read_mtx(path, chunk_bytes=None, cells=None):
     need and the chunk is parsed again.  The entry count that must equal the size line's is the number of entries seen;
     stats["entries"] is that number, stats["entries_kept"] the entries of the result and stats["arrays_grown"] the reallocations.  A selection that is ascending keeps
     a column-major file sorted; any other one goes through the torch.sort path."""
-    import gzip
     import io
-    import queue
     import re
-    import threading
     import time
     path = os.fspath(path)
     sel = None if cells is None else _selected_columns(cells, "read_mtx")
@@ -2353,51 +2212,12 @@ def read_mtx(path, chunk_bytes=None, cells=None):
             window *= 2
         field, G, C, nnz, header_lines, header_bytes = header
     else:
-        f = gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")
+        f = _open_text(path)
         try:
             field, G, C, nnz, header_lines, header_bytes = _mtx_header(f)
         except BaseException:
             f.close()
             raise
-    jobs, free, failure = queue.Queue(), [threading.Semaphore(1), threading.Semaphore(1)], []
-    stop = threading.Event()
-    pin = [_pinned(cap0), _pinned(cap0)]
-
-    def reader():
-        try:
-            slot, fill, eof = 0, 0, False
-            free[0].acquire()
-            while not eof and not stop.is_set():
-                t0 = time.perf_counter()
-                arr = pin[slot].numpy()
-                total = fill
-                while total < arr.size:
-                    got = f.readinto(memoryview(arr)[total:])
-                    if not got:
-                        eof = True
-                        break
-                    total += got
-                cut = total if eof else _last_newline(arr, total) + 1
-                stats["read_s"] += time.perf_counter() - t0
-                if cut == 0 and not eof:                          # one line is longer than the buffer: grow it and read on
-                    bigger = _pinned(2 * arr.size)
-                    bigger[:total].copy_(pin[slot][:total])
-                    pin[slot], fill = bigger, total
-                    continue
-                jobs.put((slot, pin[slot], cut))                  # only this thread writes a buffer, and only while it holds it
-                nxt = 1 - slot
-                free[nxt].acquire()                               # the chunk before this one has left that buffer
-                tail = total - cut
-                if pin[nxt].numel() <= tail:
-                    pin[nxt] = _pinned(2 * tail)
-                if tail:
-                    pin[nxt][:tail].copy_(pin[slot][cut:total])
-                slot, fill = nxt, tail
-        except Exception as exc:                                  # handed to the caller's thread below
-            failure.append(exc)
-        finally:
-            jobs.put(None)
-
     col_map, seen = None, 0                                        # K26: the device map of the selection; entries seen
     try:
         if sel is not None:
@@ -2463,34 +2283,26 @@ def read_mtx(path, chunk_bytes=None, cells=None):
             f.close()
         del text, stage
         return _mtx_result(row, col, val, filled, seen, nnz, G, C, sel, offset, stats, t_start)
-    thread = threading.Thread(target=reader, daemon=True)
-    thread.start()
-    try:
-        job = jobs.get()
-        while job is not None:
-            slot, buf, n = job
-            if n > 0:
-                if dbuf is None or dbuf.numel() < n:
-                    dbuf = torch.empty(max(cap0, n), dtype=torch.uint8, device=dev)
+    with f, LineChunks(f, cap0, stats) as chunks:
+        try:
+            job = chunks.get()
+            while job is not None:
+                slot, buf, n = job
+                if n > 0:
+                    if dbuf is None or dbuf.numel() < n:
+                        dbuf = torch.empty(max(cap0, n), dtype=torch.uint8, device=dev)
+                    t0 = time.perf_counter()
+                    dbuf[:n].copy_(buf[:n], non_blocking=True)
+                    consume(dbuf, buf.numpy()[:n], n)
+                    stats["parse_s"] += time.perf_counter() - t0
+                    stats["chunks"] += 1
+                offset += n
+                chunks.release(slot)
                 t0 = time.perf_counter()
-                dbuf[:n].copy_(buf[:n], non_blocking=True)
-                consume(dbuf, buf.numpy()[:n], n)
-                stats["parse_s"] += time.perf_counter() - t0
-                stats["chunks"] += 1
-            offset += n
-            free[slot].release()
-            t0 = time.perf_counter()
-            job = jobs.get()
-            stats["stall_s"] += time.perf_counter() - t0
-    finally:
-        stop.set()
-        torch.cuda.synchronize()
-        for sem in free:
-            sem.release()
-        thread.join()
-        f.close()
-    if failure:
-        raise failure[0]
+                job = chunks.get()
+                stats["stall_s"] += time.perf_counter() - t0
+        finally:
+            torch.cuda.synchronize()                               # the last copy may still read a pinned buffer
     return _mtx_result(row, col, val, filled, seen, nnz, G, C, sel, offset, stats, t_start)
 
 
@@ -2536,12 +2348,7 @@ _RDS_CSC_WHAT = {_lib.RDS_P_FIRST: "p does not start with 0", _lib.RDS_P_DESCENT
 
 def rds_counts_stats(reset=False):
     """The counters of icnv_rds_counts_stats since the last reset, as a dict keyed by RDS_COUNTS_STATS."""
-    L = _lib.load()
-    out = (ct.c_int64 * len(RDS_COUNTS_STATS))()
-    check(L.icnv_rds_counts_stats(out, len(RDS_COUNTS_STATS)))
-    if reset:
-        L.icnv_rds_counts_stats_reset()
-    return dict(zip(RDS_COUNTS_STATS, (int(v) for v in out)))
+    return _counters("rds_counts", RDS_COUNTS_STATS, reset)
 
 
 def _dev_list(a, dtype, dev):

@@ -312,32 +312,16 @@ class ShardedIngest:
 def _table_columns(path, sep):
     """The column names of a text table as device.read_table takes them: the header line has one name per numeric column, or
     one more with a corner label in front; the first data line decides which."""
-    import gzip
     import os
+    from . import device
     path = os.fspath(path)
     if path.endswith(".rds"):
         raise NotImplementedError("read_table: .rds input is not read; pass the matrix as an array")
     sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
-    unquote = lambda b: b[1:-1] if len(b) >= 2 and b[:1] == b"\"" and b[-1:] == b"\"" else b
-    with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
-        line = f.readline()
-        line = line[:-1] if line.endswith(b"\n") else line
-        header = [unquote(t) for t in (line[:-1] if line.endswith(b"\r") else line).split(sep_b)]
-        for raw in f:
-            raw = raw.rstrip(b"\n")
-            if raw in (b"", b"\r"):
-                continue
-            k = raw.count(sep_b) + 1
-            if len(header) == k - 1:
-                names = header
-            elif len(header) == k and k >= 2:
-                names = header[1:]
-            else:
-                raise ValueError(f"read_table: the header has {len(header)} names, the first row has {k} fields")
-            if len(names) < 1:
-                raise ValueError("read_table: the table has no numeric column")
-            return [c.decode("utf-8", "surrogateescape") for c in names]
-    raise ValueError("read_table: the file has no data row")
+    with device._open_text(path) as f:
+        header = f.readline().rstrip(b"\n")
+        first = next((raw for raw in (line.rstrip(b"\n") for line in f) if raw not in (b"", b"\r")), None)
+    return [c.decode("utf-8", "surrogateescape") for c in device._table_columns(header, first, sep_b)]
 
 
 class ShardedCreate:
@@ -410,9 +394,8 @@ class ShardedCreate:
         elif mtx is None and a["sparse"]:
             raise ValueError("sparse=True wants a .mtx file, a 10x directory or a scipy sparse matrix")
         elif mtx is not None:                                            # the size line
-            import gzip
-            from .device import _mtx_header
-            with (gzip.open(mtx[0], "rb") if mtx[0].endswith(".gz") else open(mtx[0], "rb")) as f:
+            from .device import _mtx_header, _open_text
+            with _open_text(mtx[0]) as f:
                 _, G_file, C_file, _, _, _ = _mtx_header(f)
         else:                                                            # the header line
             C_file = len(_table_columns(raw, a["delim"]))

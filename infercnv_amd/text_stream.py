@@ -1,13 +1,120 @@
-"""Streaming of text that is formatted on the device into a file (DESIGN K20, K24): two device buffers, two pinned host
-buffers, a copy stream and a writer thread.  Used by heatmap.write_matrix (plot_cnv's matrix files) and by
-cnv_regions.generate_cnv_region_reports (the CNV region reports)."""
+"""Streaming of text between a file and the device, chunk after chunk, with a thread at the file's end of it.
+
+stream_chunks (DESIGN K20, K24) writes text that is formatted on the device: two device buffers, two pinned host buffers, a
+copy stream and a writer thread.  Used by heatmap.write_matrix (plot_cnv's matrix files), by
+cnv_regions.generate_cnv_region_reports (the CNV region reports) and by the .rds writer.
+
+LineChunks (DESIGN K21, K22) reads a file in chunks of whole lines: two pinned host buffers and a reader thread.  Used by
+device.read_table and device.read_mtx, which upload and parse chunk i while the thread reads chunk i + 1."""
 from __future__ import annotations
 
 import queue
 import threading
 import time
 
+import numpy as np
 import torch
+
+
+def _pinned(n):
+    return torch.empty(int(n), dtype=torch.uint8, pin_memory=True)
+
+
+def _last_newline(arr, n):
+    """Index of the last '\\n' of arr[:n], or -1."""
+    hi = n
+    while hi > 0:
+        lo = max(0, hi - (1 << 16))
+        hit = np.flatnonzero(arr[lo:hi] == 10)
+        if hit.size:
+            return lo + int(hit[-1])
+        hi = lo
+    return -1
+
+
+class LineChunks:
+    """The rest of the binary file `f` as chunks of whole lines of about `cap` bytes, read by a thread into two buffers in
+    turn.  Within the `with` block get() blocks for the next chunk and returns (slot, buf, n) -- the first n bytes of the uint8
+    CPU tensor buf, which the caller may read until it calls release(slot) --, or None at the end of the file.  Every chunk
+    but the last ends in '\\n'; a chunk may be empty (the last one is when the file ends in '\\n' at a buffer's end).  What
+    follows a chunk's last '\\n' is carried to the other buffer; a buffer doubles when one line is longer than it.
+    stats["read_s"] gains the thread's seconds inside readinto and the newline search, stats["grown"], where the caller has
+    that key, the doublings.  Leaving the block stops and joins the thread, and raises what the thread caught unless another
+    exception is on its way; a caller whose device copies may still read a buffer synchronises before it leaves.
+    alloc(n): a buffer of n bytes -- pinned memory, unless a test without a GPU says otherwise."""
+
+    def __init__(self, f, cap, stats, alloc=_pinned):
+        self._f, self._stats, self._alloc = f, stats, alloc
+        self._pin = [alloc(cap), alloc(cap)]
+        self._jobs, self._free = queue.Queue(), [threading.Semaphore(1), threading.Semaphore(1)]
+        self._stop, self._failure = threading.Event(), []
+        self.thread = threading.Thread(target=self._reader, daemon=True)
+
+    def _reader(self):
+        f, pin, free, stats = self._f, self._pin, self._free, self._stats
+        try:
+            slot, fill, eof = 0, 0, False
+            free[0].acquire()
+            while not eof and not self._stop.is_set():
+                t0 = time.perf_counter()
+                arr = pin[slot].numpy()
+                total = fill
+                while total < arr.size:
+                    got = f.readinto(memoryview(arr)[total:])
+                    if not got:
+                        eof = True
+                        break
+                    total += got
+                cut = total if eof else _last_newline(arr, total) + 1
+                stats["read_s"] += time.perf_counter() - t0
+                if cut == 0 and not eof:                          # one line is longer than the buffer: grow it and read on
+                    bigger = self._alloc(2 * arr.size)
+                    bigger[:total].copy_(pin[slot][:total])
+                    pin[slot], fill = bigger, total
+                    if "grown" in stats:
+                        stats["grown"] += 1
+                    continue
+                self._jobs.put((slot, pin[slot], cut))            # only this thread writes a buffer, and only while it holds it
+                nxt = 1 - slot
+                free[nxt].acquire()                               # the chunk before this one has left that buffer
+                tail = total - cut
+                if pin[nxt].numel() <= tail:
+                    pin[nxt] = self._alloc(2 * tail)
+                if tail:
+                    pin[nxt][:tail].copy_(pin[slot][cut:total])
+                slot, fill = nxt, tail
+        except Exception as exc:                                  # handed to the caller's thread by __exit__
+            self._failure.append(exc)
+        finally:
+            self._jobs.put(None)
+
+    def __enter__(self):
+        self.thread.start()
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self._stop.set()
+        for sem in self._free:
+            sem.release()
+        self.thread.join()
+        if exc_type is None and self._failure:
+            raise self._failure[0]
+
+    def get(self):
+        return self._jobs.get()
+
+    def get_nowait(self):
+        """The next chunk where the thread has it ready, else None: the end of the file is left for get()."""
+        try:
+            job = self._jobs.get_nowait()
+        except queue.Empty:
+            return None
+        if job is None:
+            self._jobs.put(None)
+        return job
+
+    def release(self, slot):
+        self._free[slot].release()
 
 
 def stream_chunks(f, cap, device, fill):

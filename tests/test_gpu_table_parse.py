@@ -108,6 +108,32 @@ def test_crlf_pair_across_a_segment_boundary(dev, tmp_path):
     read_both(dev, write(tmp_path, "seg.tsv", text))
 
 
+def test_a_file_that_ends_where_a_buffer_ends(dev, tmp_path):
+    """Every line, the header too, is exactly the 64 bytes of a chunk: the file ends with a full buffer, and the reader hands
+    over an empty last chunk -- as a rule while the chunk before it is parsed, so the copy ahead takes it.  It is passed over
+    like any empty chunk.  The reading runs on a thread that is joined with a time limit, so a loop that does not end fails."""
+    import threading
+    lines = ["a" * 31 + "\t" + "b" * 31] + [f"r{i}\t" + "1" * (63 - len(f"r{i}") - 3) + "\t7" for i in range(20)]
+    assert all(len(l) == 63 for l in lines)
+    path = write(tmp_path, "full.tsv", "\n".join(lines) + "\n")
+    box = {}
+
+    def run():
+        try:
+            dev.init(0)
+            box["value"] = read_both(dev, path, chunk_bytes=64)
+        except BaseException as exc:
+            box["raised"] = exc
+    worker = threading.Thread(target=run, daemon=True)
+    worker.start()
+    worker.join(60.0)
+    assert not worker.is_alive(), "read_table did not return"
+    if "raised" in box:
+        raise box["raised"]
+    rows, _, _, stats = box["value"]
+    assert len(rows) == 20 and stats["chunks"] == 20 and stats["grown"] == 0
+
+
 def test_one_line_longer_than_the_chunk(dev, tmp_path):
     fields = small(3, 400, 4)
     text, _, _, _ = cases.table_text(fields, 400)
