@@ -6,6 +6,7 @@ import math
 import numpy as np
 import pytest
 
+import de_edge_cases as ec
 import de_restate as dr
 
 stats = pytest.importorskip("scipy.stats")
@@ -78,6 +79,73 @@ def test_pt_tail_against_mpmath():
             assert rel(p, ref) <= 1e-12, (t, df, p, ref)
 
 
+@pytest.mark.parametrize("z", ec.PNORM_POINTS)
+def test_pnorm2_regimes_against_mpmath(z):
+    # both sides of the 0.674 and 5.657 switches, the fully separated 50 vs 500 ladder rung (11.67) and the deep tail up to
+    # the last |z| whose p is still above 1e-300
+    mpmath = pytest.importorskip("mpmath")
+    mpmath.mp.dps = 50
+    ref = float(mpmath.erfc(mpmath.mpf(z) / mpmath.sqrt(2)))
+    assert ref >= 1e-300
+    for s in (z, -z):
+        assert rel(dr.pnorm2(s), ref) <= 1e-12, (s, dr.pnorm2(s), ref)
+
+
+def test_pnorm2_points_cover_the_regimes():
+    assert {ec.pnorm_regime(z) for z in ec.PNORM_POINTS} == {1, 2, 3}
+    assert ec.pnorm_regime(0.67448975) == 1 and ec.pnorm_regime(0.6744898) == 2
+    assert ec.pnorm_regime(5.65685) == 2 and ec.pnorm_regime(5.65686) == 3
+    for z in (37.5193, 38.7, math.inf):              # from here on R's pnorm returns 0 (2 pnorm(-37.5193) would be about 4e-308)
+        assert ec.pnorm_regime(z) == 4 and dr.pnorm2(z) == 0.0 and dr.pnorm2(-z) == 0.0
+    assert dr.pnorm2(0.0) == 1.0 and math.isnan(dr.pnorm2(math.nan))
+
+
+def test_wilcoxon_ladder_reaches_every_regime():
+    expr, groups, cmps = ec.wilcoxon_ladder()
+    reg = ec.wilcoxon_regimes(expr, groups, cmps)
+    ec.check_wilcoxon_ladder(reg)
+    _, p, _ = dr.de_tests(expr, groups, cmps, jitter_on=False)
+    assert (p[reg == 4] == 0.0).all() and np.isnan(p[reg == 0]).all() and (p[(reg > 0) & (reg < 4)] > 0.0).all()
+    z = [ec.wilcox_z(expr[3, groups[a]].tolist(), expr[3, groups[b]].tolist()) for a, b in cmps[4:]]
+    assert 37.5193 <= -z[0] < 37.6 and 37.4 < -z[1] < 37.5193
+    assert p[4, 3] == 0.0 and 2.3e-308 < p[5, 3] < 2e-307     # the formula would not underflow at either: the cut decides
+
+
+def test_exact_table_ends():
+    expr, groups, cmps = ec.exact_ends()
+    W, p, _ = dr.de_tests(expr, groups, cmps, jitter_on=False)
+    for k, (qx, qy) in enumerate(cmps):
+        full = float(len(groups[qx]) * len(groups[qy]))
+        assert {W[k, 0], W[k, 1]} == {0.0, full}
+        if full < 50 * 49:                           # the exact table: the two ends are one arrangement out of choose(n, n.x)
+            assert ec.wilcox_z(expr[0, groups[qx]].tolist(), expr[0, groups[qy]].tolist()) is None
+            end = min(1.0, 2.0 / math.comb(len(groups[qx]) + len(groups[qy]), len(groups[qx])))
+            assert rel(p[k, 0], end) <= 1e-15 and p[k, 0] == p[k, 1]
+        else:
+            assert ec.wilcox_z(expr[0, groups[qx]].tolist(), expr[0, groups[qy]].tolist()) is not None
+
+
+def test_pt2_ladder_against_mpmath():
+    mpmath = pytest.importorskip("mpmath")
+    mpmath.mp.dps = 50
+    expr, groups, cmps = ec.welch_ladder()
+    pts = ec.welch_points(expr, groups, cmps)
+    ec.check_welch_ladder(pts)
+    for r in range(len(ec.WELCH_RUNGS)):
+        t, df, p = pts[r, r]
+        assert p == dr.pt2(-abs(t), df)
+        ref = float(mpmath.betainc(mpmath.mpf(df) / 2, 0.5, 0, mpmath.mpf(df) / (df + mpmath.mpf(t) ** 2), regularized=True))
+        if ref >= 1e-300:
+            assert rel(p, ref) <= 1e-12, (ec.WELCH_RUNGS[r], t, df, p, ref)
+
+
+def test_exact_mean_fast_is_exact_mean():
+    rng = np.random.default_rng(8)
+    for v in (rng.normal(1.0, 0.3, size=5000), rng.normal(0.0, 1.0, size=4097) * 10.0 ** rng.integers(-3, 4, size=4097),
+              np.array([1e16, 1.0, -1e16, 3.0]), np.array([-0.0, 5e-324, -2.5])):
+        assert ec.exact_mean_fast(v) == dr.exact_mean(v)
+
+
 def test_welch_na_rules():
     nan = math.nan
     assert math.isnan(dr.welch([1.0], [1.0, 2.0])[1])
@@ -113,6 +181,13 @@ def test_jitter_stream_is_numpy_philox():
     assert rel(dr.pnorm2(1.7), 2 * stats.norm.sf(1.7)) <= 1e-14
     assert rel(dr.pnorm2(-9.0), 2 * stats.norm.sf(9.0)) <= 1e-13
     assert dr.exp_lib(-800.0) == 0.0 and rel(dr.exp_lib(-700.0), math.exp(-700.0)) <= 1e-15
+
+
+def test_jitter_matrix_is_the_jitter_of_every_gene_and_cell():
+    for seed, G, C in ((0, 3, 700), (2**63 + 5, 9, 130)):
+        J = ec.jitter_matrix(seed, G, C)
+        assert all(J[g, c] == dr.jitter(seed, g, c) for g in range(G) for c in range(C))
+        assert ec.jitter_sample_matches(J, seed) and not ec.jitter_sample_matches(J, seed + 1)
 
 
 def test_mask_rules_hand_built():
