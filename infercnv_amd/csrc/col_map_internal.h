@@ -1,5 +1,5 @@
-// K26: the check of a column map, shared by the two column-selected readers (table_cols_api.hip, triplets_cols_api.hip; the
-// kernels are in table_cols_kernels.hip).  DESIGN.md section 4 K26.
+// K26: the check of a column map, shared by the two column-selected readers (their entries are in table_parse_api.hip and
+// sparse_counts_api.hip; the kernels are in table_cols_kernels.hip).  DESIGN.md section 4 K26.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// Shared between sparse_counts_api.hip (validation, the order of the passes, the text of a refusal) and
+// Shared between sparse_counts_api.hip (validation, the order of the passes, the text of a refusal; K22's entries and K26's) and
 // sparse_counts_kernels.hip (K22, sparse count matrices: the triplet parser, the CSC builder, the CSC selector).
 // The grammar of one triplet line lives here as plain C++ that compiles for the device and for the host, so that the
 // kernel and the refusal text of the entry read a line with the same code.  DESIGN.md section 4 K22.

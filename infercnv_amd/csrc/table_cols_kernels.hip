@@ -2,7 +2,8 @@
 // a column map, shared with the triplet flavour (triplets_cols_kernels.hip); then, after K21's structure pass over the whole
 // chunk: index (the rows' starts; the rows' checks of K21; the first byte of every SELECTED field), parse (one lane per
 // selected field), collect.  The staged values are n_cols_out wide and go through K21's transpose.  The host side is
-// table_cols_api.hip.  DESIGN.md section 4 K26.
+// the driver K21 and K26 share in table_parse_api.hip; the index pass and the conversion of a field are K21's device functions
+// (table_parse_internal.h).  DESIGN.md section 4 K26.
 #include "icnv_internal.h"
 #include "col_map_internal.h"
 #include "table_parse_internal.h"
@@ -38,23 +39,7 @@ __global__ __launch_bounds__(TP_NT) void cm_hits_kernel(const int32_t *col_map, 
 // K21's index pass without the field lists: the rows' first bytes and first fields only.
 __global__ __launch_bounds__(TP_NT) void tc_index_rows_kernel(TpArgs a) {
     __shared__ uint32_t s_scan[TP_NT];
-    const int64_t base = ((int64_t)blockIdx.x * TP_NT + threadIdx.x) * TP_BYTES;
-    uint32_t rows, fields;
-    tp_masks(a, base, rows, fields);
-    const uint32_t mine = tp_packed_counts(rows, fields), excl = tp_block_scan(mine, s_scan) - mine;
-    int64_t r = (int64_t)a.seg_row_off[blockIdx.x] + (excl >> 16), f = (int64_t)a.seg_field_off[blockIdx.x] + (excl & 0xffffu);
-    while (fields) {
-        const int j = __ffs((int)fields) - 1;
-        fields &= fields - 1;
-        if ((rows >> j) & 1u) {
-            if (r < a.n_rows) {
-                a.row_pos[r] = (uint32_t)(base + j);
-                a.row_field0[r] = (uint32_t)f;
-            }
-            ++r;
-        }
-        ++f;
-    }
+    tp_index_starts<false>(a, s_scan);
 }
 
 // Runs after tc_index_rows_kernel: the field start f of row r is file column f - row_field0[r] - 1; where the map selects it,
@@ -90,19 +75,7 @@ __global__ __launch_bounds__(TP_NT) void tc_parse_kernel(TcArgs t) {
     if (slot >= a.n_rows * t.n_cols_out) return;
     const uint32_t at = t.sel_pos[slot];
     if (at == TC_ABSENT || (int64_t)at > a.n) return;          // a ragged row without this field: the rows pass refuses the chunk
-    const int64_t p = at;
-    int64_t end = p;
-    while (end - p <= TP_MAX_SCAN && !tp_at_line_end(a.text, a.n, end) && a.text[end] != a.sep) ++end;
-    uint64_t bits = TP_PENDING, w;
-    int q;
-    bool neg;
-    int kind = TP_HOST;
-    if (end - p <= TP_MAX_SCAN) kind = tp_scan_number(a.text + p, end - p, bits, w, q, neg);
-    if (kind == TP_DECIMAL) kind = tp_convert(w, q, neg, bits) ? TP_VALUE : TP_HOST;
-    if (kind == TP_BAD) tp_refuse(a, p, 2 /* TP_E_NUMBER */);
-    if (kind != TP_VALUE) bits = TP_PENDING;
-    if (kind == TP_HOST) tp_flag(a, slot, p);
-    a.vals[slot] = bits;
+    tp_stage_field(a, at, slot);
 }
 
 // More than TP_FLAG_CAP uncertified fields: list (up to the capacity) those that are still pending.  Runs only on a chunk
@@ -112,12 +85,6 @@ __global__ __launch_bounds__(TP_NT) void tc_collect_kernel(TcArgs t) {
     const int64_t n = a.n_rows * t.n_cols_out;
     for (int64_t i = (int64_t)blockIdx.x * TP_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * TP_NT)
         if (a.vals[i] == TP_PENDING && t.sel_pos[i] != TC_ABSENT) tp_flag(a, i, t.sel_pos[i]);
-}
-
-int tc_grid(int64_t blocks, unsigned &grid) {
-    if (blocks < 1 || blocks > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "parse_table_cols: the chunk needs more than 2^31 - 1 workgroups");
-    grid = (unsigned)blocks;
-    return ICNV_OK;
 }
 
 }  // namespace
@@ -155,7 +122,7 @@ int check_col_map(const int32_t *col_map_dev, int64_t n_cols, int64_t n_cols_out
 int launch_tc_index(const TcArgs &t, hipStream_t s) {
     unsigned grid;
     int rc;
-    if ((rc = tc_grid(t.tp.n_seg, grid))) return rc;
+    if ((rc = tp_grid(t.tp.n_seg, grid, "parse_table_cols"))) return rc;
     {
         KernelTimer kt("table_cols_index", s);
         hipLaunchKernelGGL(tc_index_rows_kernel, dim3(grid), dim3(TP_NT), 0, s, t.tp);
@@ -173,7 +140,7 @@ int launch_tc_parse(const TcArgs &t, hipStream_t s) {
     KernelTimer kt("table_cols_fields", s);
     unsigned grid;
     int rc;
-    if ((rc = tc_grid((t.tp.n_rows * t.n_cols_out + TP_NT - 1) / TP_NT, grid))) return rc;
+    if ((rc = tp_grid((t.tp.n_rows * t.n_cols_out + TP_NT - 1) / TP_NT, grid, "parse_table_cols"))) return rc;
     hipLaunchKernelGGL(tc_parse_kernel, dim3(grid), dim3(TP_NT), 0, s, t);
     ICNV_HIP(hipGetLastError());
     return ICNV_OK;

@@ -1,6 +1,7 @@
-// C ABI of K21 (include/icnv.h "count matrices from text"): validation, the order of the passes over a chunk of whole lines,
-// strtod for the fields the parse pass does not certify, the text of a refusal; and the matrix gather of CreateInfercnvObject.
-// Kernels: table_parse_kernels.hip.  DESIGN.md section 4 K21.
+// C ABI of K21 (include/icnv.h "count matrices from text") and of the dense half of K26 ("reading a selection of columns"):
+// validation, the order of the passes over a chunk of whole lines, strtod for the fields the parse pass does not certify, the
+// text of a refusal -- one driver for the plain and the column-selected entry; and the matrix gather of CreateInfercnvObject.
+// Kernels: table_parse_kernels.hip, table_cols_kernels.hip.  DESIGN.md section 4 K21, K26.
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "icnv_internal.h"
+#include "col_map_internal.h"
 #include "table_parse_host.h"
 #include "table_parse_internal.h"
 #include "../../include/icnv.h"
@@ -34,40 +36,28 @@ int tp_refused(const uint8_t *text_host, int64_t n, uint64_t word, uint8_t sep, 
     ICNV_FAIL(ICNV_ERR_ARG, "parse_table: " + tp_describe(text_host, n, (int64_t)(word >> 8), (int)(word & 0xff), sep, line0, n_cols));
 }
 
-}  // namespace
-
-// the same checks, refusal text and counters for the column-selected entry (table_cols_api.hip, K26)
-namespace icnv {
-
-int tp_check_args(const void *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0, const void *out,
-                  int64_t ld, int64_t row0, int64_t max_rows, const int64_t *label_ranges, const int64_t *n_rows) {
+// The arguments of the two device entries: tp_validate and the alignment of the device text.
+int tp_check_dev(const void *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0, const void *out,
+                 int64_t ld, int64_t row0, int64_t max_rows, const int64_t *label_ranges, const int64_t *n_rows) {
     int rc;
     if ((rc = tp_validate(text_dev, text_host, n_bytes, sep, n_cols, line0, out, ld, row0, max_rows, label_ranges, n_rows))) return rc;
     if (reinterpret_cast<uintptr_t>(text_dev) & 15) ICNV_FAIL(ICNV_ERR_ARG, "parse_table: the device text must start on a 16-byte boundary");
     return ICNV_OK;
 }
 
-int tp_refusal(const uint8_t *text_host, int64_t n, uint64_t word, uint8_t sep, int64_t line0, int64_t n_cols) {
-    return tp_refused(text_host, n, word, sep, line0, n_cols);
-}
-
-void tp_count_call(int64_t rows, int64_t fields, int64_t host_fields, int64_t bytes, int64_t rounds, int64_t us) {
-    g_tp[0] += 1; g_tp[1] += rows; g_tp[2] += fields; g_tp[3] += host_fields; g_tp[4] += bytes; g_tp[5] += rounds; g_tp[6] += us;
-}
-
-}  // namespace icnv
-
-extern "C" {
-
-int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0,
-                         double *out, int64_t ld, int64_t row0, int64_t max_rows, int64_t *label_ranges, int64_t *n_rows, void *stream) {
+// The driver of icnv_parse_table_dev (col_map null; n_cols_out unused) and of icnv_parse_table_cols_dev (K26: the staged values
+// are n_cols_out wide and only the selected fields are indexed, parsed and collected).  The arguments are checked by the entry.
+int tp_parse_chunk(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0, double *out,
+                   int64_t ld, int64_t row0, int64_t max_rows, int64_t *label_ranges, int64_t *n_rows, const int32_t *col_map, int64_t n_cols_out,
+                   void *stream) {
     int rc;
-    if ((rc = tp_validate(text_dev, text_host, n_bytes, sep, n_cols, line0, out, ld, row0, max_rows, label_ranges, n_rows))) return rc;
-    if (reinterpret_cast<uintptr_t>(text_dev) & 15) ICNV_FAIL(ICNV_ERR_ARG, "parse_table: the device text must start on a 16-byte boundary");
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t s = (hipStream_t)stream;
+    if (col_map && (rc = check_col_map(col_map, n_cols, n_cols_out, "parse_table_cols", s))) return rc;
 
-    TpArgs a{};
+    TcArgs t{};                                                         // t.tp is all the plain entry uses
+    TpArgs &a = t.tp;
+    t.col_map = col_map; t.n_cols_out = n_cols_out;
     a.text = text_dev; a.n = n_bytes; a.sep = (uint8_t)sep[0]; a.n_cols = n_cols;
     a.n_seg = (n_bytes + 1 + TP_SEG - 1) / TP_SEG;
     a.out = out; a.ld = ld; a.row0 = row0;
@@ -80,7 +70,7 @@ int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int6
     const uint64_t init[4] = {TP_NO_ERROR, 0, 0, 0};
     ICNV_HIP(hipMemcpyAsync(d_small.p, init, sizeof init, hipMemcpyHostToDevice, s));
 
-    // structure: how many rows and fields
+    // structure: how many rows and fields, over the whole chunk
     if ((rc = launch_tp_structure(a, s))) return rc;
     uint32_t totals[2] = {0, 0};
     ICNV_HIP(hipMemcpyAsync(totals, a.totals, sizeof totals, hipMemcpyDeviceToHost, s));
@@ -94,18 +84,25 @@ int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int6
         g_tp[6] += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
         return ICNV_OK;
     }
-    const int64_t n_vals = a.n_rows * n_cols;
+    const int64_t n_vals = a.n_rows * (col_map ? n_cols_out : n_cols);
 
-    // index, rows, parse
-    DevBuf d_field, d_row, d_vals, d_flag;
-    if ((rc = d_field.alloc((size_t)a.n_fields * 2 * sizeof(uint32_t))) || (rc = d_row.alloc((size_t)a.n_rows * 4 * sizeof(uint32_t))) ||
-        (rc = d_vals.alloc((size_t)n_vals * sizeof(uint64_t))) || (rc = d_flag.alloc((size_t)TP_FLAG_CAP * sizeof(TpFlagged))))
+    // index, rows, parse: the list of all fields, or (K26) only the positions of the selected ones
+    DevBuf d_row, d_vals, d_flag, d_field, d_sel;
+    if ((rc = d_row.alloc((size_t)a.n_rows * 4 * sizeof(uint32_t))) || (rc = d_vals.alloc((size_t)n_vals * sizeof(uint64_t))) ||
+        (rc = d_flag.alloc((size_t)TP_FLAG_CAP * sizeof(TpFlagged))))
         return rc;
-    a.field_pos = d_field.as<uint32_t>(); a.field_row = a.field_pos + a.n_fields;
     a.row_pos = d_row.as<uint32_t>(); a.row_field0 = a.row_pos + a.n_rows;
     a.label_range = reinterpret_cast<int32_t *>(a.row_field0 + a.n_rows);
     a.vals = d_vals.as<uint64_t>(); a.flagged = d_flag.as<TpFlagged>();
-    if ((rc = launch_tp_index(a, s)) || (rc = launch_tp_parse(a, s))) return rc;
+    if (col_map) {
+        if ((rc = d_sel.alloc((size_t)n_vals * sizeof(uint32_t)))) return rc;
+        t.sel_pos = d_sel.as<uint32_t>();
+        if ((rc = launch_tc_index(t, s)) || (rc = launch_tc_parse(t, s))) return rc;
+    } else {
+        if ((rc = d_field.alloc((size_t)a.n_fields * 2 * sizeof(uint32_t)))) return rc;
+        a.field_pos = d_field.as<uint32_t>(); a.field_row = a.field_pos + a.n_fields;
+        if ((rc = launch_tp_index(a, s)) || (rc = launch_tp_parse(a, s))) return rc;
+    }
 
     // the fields the parse pass did not certify, at most TP_FLAG_CAP per round: strtod here, the staged value replaced
     int64_t n_host = 0, rounds = 0;
@@ -129,7 +126,7 @@ int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int6
         if ((rc = host.get(text))) return rc;
         for (size_t i = 0; i < n; ++i) {
             if (fl[i].slot < 0 || fl[i].slot >= n_vals || fl[i].pos < 0 || fl[i].pos > n_bytes)
-                ICNV_FAIL(ICNV_ERR_HIP, "parse_table: a flagged field lies outside the chunk (internal error)");
+                ICNV_FAIL(ICNV_ERR_HIP, std::string(col_map ? "parse_table_cols" : "parse_table") + ": a flagged field lies outside the chunk (internal error)");
             slot[i] = fl[i].slot;
             if (tp_host_field(text, n_bytes, fl[i].pos, a.sep, bits[i]) != TP_VALUE) {
                 const uint64_t word = ((uint64_t)fl[i].pos << 8) | (uint64_t)TP_E_NUMBER;
@@ -145,14 +142,17 @@ int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int6
         ICNV_HIP(hipMemsetAsync(a.n_flagged, 0, sizeof(uint64_t), s));
         if (count > (uint32_t)TP_FLAG_CAP) {                          // some were counted but not listed: look for what is still pending
             ++rounds;
-            if ((rc = launch_tp_collect(a, s))) return rc;
+            if ((rc = col_map ? launch_tc_collect(t, s) : launch_tp_collect(a, s))) return rc;
         }
         ICNV_HIP(hipStreamSynchronize(s));                              // the uploads' pool blocks outlive the patch
     }
 
-    // every value is known and nothing was refused: only now is the matrix written
+    // every value is known and nothing was refused: only now is the matrix written, by the transpose of a table that is as wide
+    // as the staged values
     std::vector<int32_t> ranges((size_t)a.n_rows * 2);
-    if ((rc = launch_tp_transpose(a, s))) return rc;
+    TpArgs staged = a;
+    if (col_map) staged.n_cols = n_cols_out;
+    if ((rc = launch_tp_transpose(staged, s))) return rc;
     ICNV_HIP(hipMemcpyAsync(ranges.data(), a.label_range, ranges.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     ICNV_HIP(hipStreamSynchronize(s));
     for (int64_t r = 0; r < a.n_rows; ++r) {
@@ -165,6 +165,27 @@ int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int6
     g_tp[0] += 1; g_tp[1] += a.n_rows; g_tp[2] += n_vals; g_tp[3] += n_host; g_tp[4] += n_bytes; g_tp[5] += rounds;
     g_tp[6] += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     return ICNV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int icnv_parse_table_dev(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0,
+                         double *out, int64_t ld, int64_t row0, int64_t max_rows, int64_t *label_ranges, int64_t *n_rows, void *stream) {
+    int rc;
+    if ((rc = tp_check_dev(text_dev, text_host, n_bytes, sep, n_cols, line0, out, ld, row0, max_rows, label_ranges, n_rows))) return rc;
+    return tp_parse_chunk(text_dev, text_host, n_bytes, sep, n_cols, line0, out, ld, row0, max_rows, label_ranges, n_rows, nullptr, 0, stream);
+}
+
+int icnv_parse_table_cols_dev(const uint8_t *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0,
+                              double *out, int64_t ld, int64_t row0, int64_t max_rows, int64_t *label_ranges, int64_t *n_rows,
+                              const int32_t *col_map_dev, int64_t n_cols_out, void *stream) {
+    int rc;
+    if ((rc = tp_check_dev(text_dev, text_host, n_bytes, sep, n_cols, line0, out, ld, row0, max_rows, label_ranges, n_rows))) return rc;
+    if (!col_map_dev) ICNV_FAIL(ICNV_ERR_ARG, "parse_table_cols: null column map");
+    return tp_parse_chunk(text_dev, text_host, n_bytes, sep, n_cols, line0, out, ld, row0, max_rows, label_ranges, n_rows, col_map_dev, n_cols_out,
+                          stream);
 }
 
 int icnv_parse_table(const uint8_t *text, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0, double *out, int64_t ld,

@@ -1,5 +1,7 @@
-// Shared between table_parse_api.hip (validation, the host's strtod path, the error text) and table_parse_kernels.hip
-// (K21, count matrices from text: structure, index, rows, parse, transpose; the matrix gather).  DESIGN.md section 4 K21.
+// Shared between table_parse_api.hip (the one host driver of the plain and the column-selected table entries: validation, the
+// host's strtod path, the error text), table_parse_kernels.hip (K21, count matrices from text: structure, index, rows, parse,
+// transpose; the matrix gather) and table_cols_kernels.hip (K26: index, parse and collect of selected columns).
+// DESIGN.md section 4 K21, K26.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -104,14 +106,59 @@ __device__ inline void tp_flag(const TpArgs &a, int64_t slot, int64_t pos) {
     if (t < (uint32_t)TP_FLAG_CAP) a.flagged[t] = TpFlagged{slot, pos};
 }
 
+// The index pass of one lane: the first byte and first field of every row that starts in the lane's positions and, with
+// LIST_FIELDS (K21), the first byte and the row of every field.  K26 lists no fields: it keeps positions of selected ones only.
+template <bool LIST_FIELDS>
+__device__ inline void tp_index_starts(const TpArgs &a, uint32_t *s_scan) {
+    const int64_t base = ((int64_t)blockIdx.x * TP_NT + threadIdx.x) * TP_BYTES;
+    uint32_t rows, fields;
+    tp_masks(a, base, rows, fields);
+    const uint32_t mine = tp_packed_counts(rows, fields), excl = tp_block_scan(mine, s_scan) - mine;
+    int64_t r = (int64_t)a.seg_row_off[blockIdx.x] + (excl >> 16), f = (int64_t)a.seg_field_off[blockIdx.x] + (excl & 0xffffu);
+    while (fields) {
+        const int j = __ffs((int)fields) - 1;
+        fields &= fields - 1;
+        if ((rows >> j) & 1u) {
+            if (r < a.n_rows) {
+                a.row_pos[r] = (uint32_t)(base + j);
+                a.row_field0[r] = (uint32_t)f;
+            }
+            ++r;
+        }
+        if (LIST_FIELDS && f < a.n_fields && r >= 1 && r <= a.n_rows) {
+            a.field_pos[f] = (uint32_t)(base + j);
+            a.field_row[f] = (uint32_t)(r - 1);
+        }
+        ++f;
+    }
+}
+
+// The field that starts at p, converted and staged at vals[slot]: its value where the scan certifies one, else TP_PENDING --
+// with the field flagged for the host's strtod, or the chunk refused where the field is no number at all.
+__device__ inline void tp_stage_field(const TpArgs &a, int64_t p, int64_t slot) {
+    int64_t end = p;
+    while (end - p <= TP_MAX_SCAN && !tp_at_line_end(a.text, a.n, end) && a.text[end] != a.sep) ++end;
+    uint64_t bits = TP_PENDING, w;
+    int q;
+    bool neg;
+    int kind = TP_HOST;
+    if (end - p <= TP_MAX_SCAN) kind = tp_scan_number(a.text + p, end - p, bits, w, q, neg);
+    if (kind == TP_DECIMAL) kind = tp_convert(w, q, neg, bits) ? TP_VALUE : TP_HOST;
+    if (kind == TP_BAD) tp_refuse(a, p, 2 /* TP_E_NUMBER */);
+    if (kind != TP_VALUE) bits = TP_PENDING;
+    if (kind == TP_HOST) tp_flag(a, slot, p);
+    a.vals[slot] = bits;
+}
+
+int tp_grid(int64_t blocks, unsigned &grid, const char *who);   // blocks as a grid size, or ICNV_ERR_UNSUPPORTED "<who>: the chunk needs ..."
 int launch_tp_structure(const TpArgs &a, hipStream_t s);     // seg_count, the scans, totals
 int launch_tp_index(const TpArgs &a, hipStream_t s);         // field_pos, field_row, row_pos, row_field0; then the rows' checks and label ranges
-int launch_tp_rows(const TpArgs &a, hipStream_t s);          // the rows' checks and label ranges alone (K26: needs row_pos, row_field0 only)
+int launch_tp_rows(const TpArgs &a, hipStream_t s);          // the rows' checks and label ranges alone, timed as table_cols_rows (K26: needs row_pos, row_field0 only)
 int launch_tp_parse(const TpArgs &a, hipStream_t s);
 int launch_tp_collect(const TpArgs &a, hipStream_t s);
 int launch_tp_patch(const TpArgs &a, const int64_t *slot, const uint64_t *bits, int32_t n, hipStream_t s);
 int launch_tp_transpose(const TpArgs &a, hipStream_t s);
-// K26, the column-selected entry: its launches (table_cols_kernels.hip) and what it shares with table_parse_api.hip
+// K26, the column-selected entry: its launches (table_cols_kernels.hip)
 struct TcArgs {
     TpArgs tp;                             // n_cols: the file's; vals: [n_rows * n_cols_out], row r, output column k at r * n_cols_out + k
     const int32_t *col_map;                // [tp.n_cols] output column of a file column, or -1
@@ -122,10 +169,6 @@ constexpr uint32_t TC_ABSENT = 0xffffffffu;
 int launch_tc_index(const TcArgs &a, hipStream_t s);         // row_pos, row_field0; the rows' checks; sel_pos
 int launch_tc_parse(const TcArgs &a, hipStream_t s);
 int launch_tc_collect(const TcArgs &a, hipStream_t s);
-int tp_check_args(const void *text_dev, const uint8_t *text_host, int64_t n_bytes, const char *sep, int64_t n_cols, int64_t line0, const void *out,
-                  int64_t ld, int64_t row0, int64_t max_rows, const int64_t *label_ranges, const int64_t *n_rows);
-int tp_refusal(const uint8_t *text_host, int64_t n, uint64_t word, uint8_t sep, int64_t line0, int64_t n_cols);   // sets the message, returns ICNV_ERR_ARG
-void tp_count_call(int64_t rows, int64_t fields, int64_t host_fields, int64_t bytes, int64_t rounds, int64_t us);   // icnv_table_parse_stats
 
 int launch_gather_matrix(const double *in, int64_t ld_in, const int32_t *genes, int64_t n_genes, const int32_t *cells, int64_t n_cells,
                          double *out, int64_t ld_out, hipStream_t s);

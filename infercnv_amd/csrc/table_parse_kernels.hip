@@ -49,27 +49,7 @@ __global__ __launch_bounds__(TP_NT) void tp_scan_kernel(TpArgs a) {
 // ---- index ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TP_NT) void tp_index_kernel(TpArgs a) {
     __shared__ uint32_t s_scan[TP_NT];
-    const int64_t base = ((int64_t)blockIdx.x * TP_NT + threadIdx.x) * TP_BYTES;
-    uint32_t rows, fields;
-    tp_masks(a, base, rows, fields);
-    const uint32_t mine = tp_packed_counts(rows, fields), excl = tp_block_scan(mine, s_scan) - mine;
-    int64_t r = (int64_t)a.seg_row_off[blockIdx.x] + (excl >> 16), f = (int64_t)a.seg_field_off[blockIdx.x] + (excl & 0xffffu);
-    while (fields) {
-        const int j = __ffs((int)fields) - 1;
-        fields &= fields - 1;
-        if ((rows >> j) & 1u) {
-            if (r < a.n_rows) {
-                a.row_pos[r] = (uint32_t)(base + j);
-                a.row_field0[r] = (uint32_t)f;
-            }
-            ++r;
-        }
-        if (f < a.n_fields && r >= 1 && r <= a.n_rows) {
-            a.field_pos[f] = (uint32_t)(base + j);
-            a.field_row[f] = (uint32_t)(r - 1);
-        }
-        ++f;
-    }
+    tp_index_starts<true>(a, s_scan);
 }
 
 // One lane per row: the field count, the label's range and its quotes.
@@ -100,18 +80,7 @@ __global__ __launch_bounds__(TP_NT) void tp_parse_kernel(TpArgs a) {
     const int64_t c = f - (int64_t)a.row_field0[r];
     if (c < 1 || c > a.n_cols) return;
     const int64_t slot = r * a.n_cols + c - 1;
-    int64_t end = p;
-    while (end - p <= TP_MAX_SCAN && !tp_at_line_end(a.text, a.n, end) && a.text[end] != a.sep) ++end;
-    uint64_t bits = TP_PENDING, w;
-    int q;
-    bool neg;
-    int kind = TP_HOST;
-    if (end - p <= TP_MAX_SCAN) kind = tp_scan_number(a.text + p, end - p, bits, w, q, neg);
-    if (kind == TP_DECIMAL) kind = tp_convert(w, q, neg, bits) ? TP_VALUE : TP_HOST;
-    if (kind == TP_BAD) tp_refuse(a, p, 2 /* TP_E_NUMBER */);
-    if (kind != TP_VALUE) bits = TP_PENDING;
-    if (kind == TP_HOST) tp_flag(a, slot, p);
-    a.vals[slot] = bits;
+    tp_stage_field(a, p, slot);
 }
 
 // More than TP_FLAG_CAP uncertified fields: list (up to the capacity) those that are still pending.  Runs only on a chunk
@@ -159,19 +128,29 @@ __global__ __launch_bounds__(TP_NT) void gather_matrix_kernel(const double *in, 
     out[j * ld_out + i] = in[c * ld_in + g];
 }
 
-int tp_grid(int64_t blocks, unsigned &grid) {
-    if (blocks < 1 || blocks > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, "parse_table: the chunk needs more than 2^31 - 1 workgroups");
-    grid = (unsigned)blocks;
+// The rows pass without a timer of its own: launch_tp_index and launch_tp_rows each run it under theirs.
+int tp_rows_untimed(const TpArgs &a, hipStream_t s) {
+    unsigned grid;
+    int rc;
+    if ((rc = tp_grid((a.n_rows + TP_NT - 1) / TP_NT, grid, "parse_table"))) return rc;
+    hipLaunchKernelGGL(tp_rows_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
+    ICNV_HIP(hipGetLastError());
     return ICNV_OK;
 }
 
 }  // namespace
 
+int tp_grid(int64_t blocks, unsigned &grid, const char *who) {
+    if (blocks < 1 || blocks > 0x7fffffff) ICNV_FAIL(ICNV_ERR_UNSUPPORTED, std::string(who) + ": the chunk needs more than 2^31 - 1 workgroups");
+    grid = (unsigned)blocks;
+    return ICNV_OK;
+}
+
 int launch_tp_structure(const TpArgs &a, hipStream_t s) {
     KernelTimer kt("table_parse_structure", s);
     unsigned grid;
     int rc;
-    if ((rc = tp_grid(a.n_seg, grid))) return rc;
+    if ((rc = tp_grid(a.n_seg, grid, "parse_table"))) return rc;
     hipLaunchKernelGGL(tp_count_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
     ICNV_HIP(hipGetLastError());
     hipLaunchKernelGGL(tp_scan_kernel, dim3(1), dim3(TP_NT), 0, s, a);
@@ -183,30 +162,22 @@ int launch_tp_index(const TpArgs &a, hipStream_t s) {
     KernelTimer kt("table_parse_index", s);
     unsigned grid;
     int rc;
-    if ((rc = tp_grid(a.n_seg, grid))) return rc;
+    if ((rc = tp_grid(a.n_seg, grid, "parse_table"))) return rc;
     hipLaunchKernelGGL(tp_index_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
     ICNV_HIP(hipGetLastError());
-    if ((rc = tp_grid((a.n_rows + TP_NT - 1) / TP_NT, grid))) return rc;
-    hipLaunchKernelGGL(tp_rows_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
-    ICNV_HIP(hipGetLastError());
-    return ICNV_OK;
+    return tp_rows_untimed(a, s);
 }
 
 int launch_tp_rows(const TpArgs &a, hipStream_t s) {
     KernelTimer kt("table_cols_rows", s);
-    unsigned grid;
-    int rc;
-    if ((rc = tp_grid((a.n_rows + TP_NT - 1) / TP_NT, grid))) return rc;
-    hipLaunchKernelGGL(tp_rows_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
-    ICNV_HIP(hipGetLastError());
-    return ICNV_OK;
+    return tp_rows_untimed(a, s);
 }
 
 int launch_tp_parse(const TpArgs &a, hipStream_t s) {
     KernelTimer kt("table_parse_fields", s);
     unsigned grid;
     int rc;
-    if ((rc = tp_grid((a.n_fields + TP_NT - 1) / TP_NT, grid))) return rc;
+    if ((rc = tp_grid((a.n_fields + TP_NT - 1) / TP_NT, grid, "parse_table"))) return rc;
     hipLaunchKernelGGL(tp_parse_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
     ICNV_HIP(hipGetLastError());
     return ICNV_OK;
@@ -230,7 +201,7 @@ int launch_tp_transpose(const TpArgs &a, hipStream_t s) {
     KernelTimer kt("table_parse_transpose", s);
     unsigned grid;
     int rc;
-    if ((rc = tp_grid(((a.n_rows + TP_TILE - 1) / TP_TILE) * ((a.n_cols + TP_TILE - 1) / TP_TILE), grid))) return rc;
+    if ((rc = tp_grid(((a.n_rows + TP_TILE - 1) / TP_TILE) * ((a.n_cols + TP_TILE - 1) / TP_TILE), grid, "parse_table"))) return rc;
     hipLaunchKernelGGL(tp_transpose_kernel, dim3(grid), dim3(TP_NT), 0, s, a);
     ICNV_HIP(hipGetLastError());
     return ICNV_OK;
@@ -242,7 +213,7 @@ int launch_gather_matrix(const double *in, int64_t ld_in, const int32_t *genes, 
     const int64_t gene_blocks = (n_genes + TP_NT - 1) / TP_NT;
     unsigned grid;
     int rc;
-    if ((rc = tp_grid(gene_blocks * n_cells, grid))) return rc;
+    if ((rc = tp_grid(gene_blocks * n_cells, grid, "parse_table"))) return rc;
     hipLaunchKernelGGL(gather_matrix_kernel, dim3(grid), dim3(TP_NT), 0, s, in, ld_in, genes, n_genes, cells, gene_blocks, out, ld_out);
     ICNV_HIP(hipGetLastError());
     return ICNV_OK;

@@ -2,7 +2,7 @@
 // K22's passes parse and validate every entry into staged arrays; here the entries whose column the map keeps are compacted
 // in file order: the kept entries of every tile of SC_KEEP_TILE entries counted by ballot, the counts scanned by one workgroup, the
 // entries stored behind the kept ones before them.  No atomics; the order is the file's whatever the launch shape.
-// The host side is triplets_cols_api.hip.  DESIGN.md section 4 K26.
+// The host side is icnv_parse_triplets_cols_dev in sparse_counts_api.hip.  DESIGN.md section 4 K26.
 #include "icnv_internal.h"
 #include "sparse_counts_internal.h"
 

@@ -427,24 +427,34 @@ def _check_text(text_dev, text_host, n_bytes):
     return host
 
 
-def parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, line0=1):
+def parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, line0=1, col_map=None):
     """icnv_parse_table_dev: the first n_bytes of `text_dev` (contiguous CUDA uint8) and of `text_host` (a contiguous uint8
     numpy array or CPU tensor with the same bytes) are whole lines of a table with out.shape[0] numeric columns; row i of them
     goes to out[:, row0 + i].  out: a CUDA float64 (n_cols, ld) tensor with contiguous rows.  Returns (rows found, int64 label
-    ranges [rows, 2] into the bytes).  text_host None: no host copy exists; the ranges then still include a label's quotes.  On an IcnvError `out` is as it was.  Synchronises the stream."""
+    ranges [rows, 2] into the bytes).  text_host None: no host copy exists; the ranges then still include a label's quotes.  On an IcnvError `out` is as it was.  Synchronises the stream.
+    With col_map (parse_table_cols_into), icnv_parse_table_cols_dev: the table has col_map.numel() numeric columns, of which the
+    map selects out.shape[0]."""
     L = _lib.load()
+    if col_map is not None and not (isinstance(col_map, torch.Tensor) and col_map.is_cuda and col_map.dtype == torch.int32 and col_map.dim() == 1
+                                    and col_map.is_contiguous() and col_map.numel() >= 1):
+        raise TypeError("col_map must be a contiguous one-dimensional CUDA int32 tensor")
     host = _check_text(text_dev, text_host, n_bytes)
-    n_cols, _, ld = _check_matrix_ld(out)
+    n_out, _, ld = _check_matrix_ld(out)
     row0, max_rows = int(row0), int(max_rows)
     if row0 < 0 or max_rows < 1 or row0 + max_rows > out.shape[1]:
         raise ValueError("rows row0 .. row0 + max_rows - 1 must be columns of out")
-    if n_cols == 1:
+    if n_out == 1:
         ld = out.shape[1]
     sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
     ranges = np.zeros((max_rows, 2), dtype=np.int64)
     n_rows = ct.c_int64(0)
-    check(L.icnv_parse_table_dev(_ptr(text_dev), _host_text_ptr(host), int(n_bytes), sep_b, n_cols, int(line0), _ptr(out), int(ld), row0,
-                                 max_rows, ranges.ctypes.data_as(ct.POINTER(ct.c_int64)), ct.byref(n_rows), _stream()))
+    n_cols = n_out if col_map is None else int(col_map.numel())
+    args = (_ptr(text_dev), _host_text_ptr(host), int(n_bytes), sep_b, n_cols, int(line0), _ptr(out), int(ld), row0, max_rows,
+            ranges.ctypes.data_as(ct.POINTER(ct.c_int64)), ct.byref(n_rows))
+    if col_map is None:
+        check(L.icnv_parse_table_dev(*args, _stream()))
+    else:
+        check(L.icnv_parse_table_cols_dev(*args, _ptr(col_map), n_out, _stream()))
     return int(n_rows.value), ranges[:int(n_rows.value)]
 
 
@@ -478,24 +488,9 @@ def parse_table_cols_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows
     """icnv_parse_table_cols_dev (DESIGN K26): parse_table_into for the columns a map selects.  col_map: a contiguous CUDA
     int32 vector with one entry per numeric column of the FILE, the row of `out` (out.shape[0] = n_cols_out) that column goes
     to, or -1.  The fields of skipped columns are not examined.  Returns (rows found, label ranges)."""
-    L = _lib.load()
-    if not (isinstance(col_map, torch.Tensor) and col_map.is_cuda and col_map.dtype == torch.int32 and col_map.dim() == 1
-            and col_map.is_contiguous() and col_map.numel() >= 1):
+    if col_map is None:
         raise TypeError("col_map must be a contiguous one-dimensional CUDA int32 tensor")
-    host = _check_text(text_dev, text_host, n_bytes)
-    n_out, _, ld = _check_matrix_ld(out)
-    row0, max_rows = int(row0), int(max_rows)
-    if row0 < 0 or max_rows < 1 or row0 + max_rows > out.shape[1]:
-        raise ValueError("rows row0 .. row0 + max_rows - 1 must be columns of out")
-    if n_out == 1:
-        ld = out.shape[1]
-    sep_b = sep if isinstance(sep, bytes) else str(sep).encode("utf-8")
-    ranges = np.zeros((max_rows, 2), dtype=np.int64)
-    n_rows = ct.c_int64(0)
-    check(L.icnv_parse_table_cols_dev(_ptr(text_dev), _host_text_ptr(host), int(n_bytes), sep_b, int(col_map.numel()), int(line0), _ptr(out),
-                                      int(ld), row0, max_rows, ranges.ctypes.data_as(ct.POINTER(ct.c_int64)), ct.byref(n_rows), _ptr(col_map),
-                                      n_out, _stream()))
-    return int(n_rows.value), ranges[:int(n_rows.value)]
+    return parse_table_into(text_dev, text_host, n_bytes, sep, out, row0, max_rows, line0=line0, col_map=col_map)
 
 
 def gather_matrix(x, genes=None, cells=None, out=None):
@@ -683,7 +678,7 @@ def _table_columns(header_line, first_data_line, sep_b):
 
 def _parse_table_chunk(chunk, host, nb, sep_b, scratch, col_map, file_line):
     """The nb bytes of whole lines at the start of `chunk` (on the device; host: the same bytes, or None) through
-    parse_table_into -- parse_table_cols_into where col_map is given -- into `scratch`, a (rows of x, any) CUDA float64 block
+    parse_table_into -- with col_map where one is given -- into `scratch`, a (rows of x, any) CUDA float64 block
     that is replaced when the chunk may hold more rows than it has columns.  Returns (rows, label ranges, scratch).  A refusal
     is raised a second time with the file's line numbers; file_line() is then called for the lines of the file before the chunk."""
     n_cols = scratch.shape[0] if col_map is None else int(col_map.numel())
@@ -692,9 +687,7 @@ def _parse_table_chunk(chunk, host, nb, sep_b, scratch, col_map, file_line):
         scratch = torch.empty((scratch.shape[0], max_rows), dtype=torch.float64, device=chunk.device)
 
     def parse(line0=1):
-        if col_map is None:
-            return parse_table_into(chunk, host, nb, sep_b, scratch, 0, max_rows, line0=line0)
-        return parse_table_cols_into(chunk, host, nb, sep_b, scratch, 0, max_rows, col_map, line0=line0)
+        return parse_table_into(chunk, host, nb, sep_b, scratch, 0, max_rows, line0=line0, col_map=col_map)
     try:
         rows, ranges = parse()
     except _lib.IcnvError as exc:
@@ -2069,18 +2062,27 @@ def _triplet_slots(row, col, val, offset):
     return at, capacity
 
 
-def parse_triplets_into(text_dev, text_host, n_bytes, field, G, C, row, col, val, offset, line0=1):
+def parse_triplets_into(text_dev, text_host, n_bytes, field, G, C, row, col, val, offset, line0=1, col_map=None, n_cols_out=None):
     """icnv_parse_triplets_dev: the first n_bytes of `text_dev` (contiguous CUDA uint8) and of `text_host` (uint8 numpy array
     with the same bytes) are whole lines of the body of a coordinate file of a G x C matrix; entry k of them goes to slot
     offset + k of row / col / val (CUDA int32 of one length).  Returns the entries found.  On an IcnvError the arrays are as they
-    were.  Synchronises the stream."""
+    were.  Synchronises the stream.
+    With col_map and n_cols_out (parse_triplets_cols_into), icnv_parse_triplets_cols_dev: returns (kept, seen)."""
     L = _lib.load()
+    if col_map is not None and not (isinstance(col_map, torch.Tensor) and col_map.is_cuda and col_map.dtype == torch.int32 and col_map.dim() == 1
+                                    and col_map.is_contiguous() and col_map.numel() == int(C)):
+        raise TypeError("col_map must be a contiguous CUDA int32 vector with one entry per column of the matrix")
+    if col_map is not None and n_cols_out is None:
+        raise TypeError("n_cols_out must be given with col_map")
     host = _check_text(text_dev, text_host, n_bytes)
     at, capacity = _triplet_slots(row, col, val, offset)
-    n = ct.c_int64(0)
-    check(L.icnv_parse_triplets_dev(_ptr(text_dev), _host_text_ptr(host), int(n_bytes), int(field), int(G), int(C), int(line0), at[0], at[1],
-                                    at[2], capacity, ct.byref(n), _stream()))
-    return int(n.value)
+    n, seen = ct.c_int64(0), ct.c_int64(0)
+    args = (_ptr(text_dev), _host_text_ptr(host), int(n_bytes), int(field), int(G), int(C), int(line0), at[0], at[1], at[2], capacity, ct.byref(n))
+    if col_map is None:
+        check(L.icnv_parse_triplets_dev(*args, _stream()))
+        return int(n.value)
+    check(L.icnv_parse_triplets_cols_dev(*args, _ptr(col_map), int(n_cols_out), ct.byref(seen), _stream()))
+    return int(n.value), int(seen.value)
 
 
 def parse_triplets_cols_into(text_dev, text_host, n_bytes, field, G, C, row, col, val, offset, col_map, n_cols_out, line0=1):
@@ -2088,16 +2090,10 @@ def parse_triplets_cols_into(text_dev, text_host, n_bytes, field, G, C, row, col
     int32 vector of C entries, the new column (0 .. n_cols_out - 1) of each matrix column or -1.  Every entry of the chunk is validated; the kept ones
     go, in file order and with their new column, to the slots from `offset` on.  Returns (kept, seen).  When the arrays are
     too short for the kept entries the IcnvError's text holds their number ("N entries are kept")."""
-    L = _lib.load()
-    if not (isinstance(col_map, torch.Tensor) and col_map.is_cuda and col_map.dtype == torch.int32 and col_map.dim() == 1
-            and col_map.is_contiguous() and col_map.numel() == int(C)):
+    if col_map is None:
         raise TypeError("col_map must be a contiguous CUDA int32 vector with one entry per column of the matrix")
-    host = _check_text(text_dev, text_host, n_bytes)
-    at, capacity = _triplet_slots(row, col, val, offset)
-    kept, seen = ct.c_int64(0), ct.c_int64(0)
-    check(L.icnv_parse_triplets_cols_dev(_ptr(text_dev), _host_text_ptr(host), int(n_bytes), int(field), int(G), int(C), int(line0), at[0],
-                                         at[1], at[2], capacity, ct.byref(kept), _ptr(col_map), int(n_cols_out), ct.byref(seen), _stream()))
-    return int(kept.value), int(seen.value)
+    return parse_triplets_into(text_dev, text_host, n_bytes, field, G, C, row, col, val, offset, line0=line0, col_map=col_map,
+                               n_cols_out=n_cols_out)
 
 
 def csc_from_sorted_triplets(row, col, G, C):
